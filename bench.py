@@ -9,8 +9,13 @@ step    : ONE full reverse diffusion of one batch of 512 series (1000 x {score n
 N GPUs  : one process per GPU, each samples its own batch of 512 series (the sample batch is sharded;
           no data-path collective) -> weak scaling; value = N*512*K / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints the JSON line (`value`, `ms_per_step` = milliseconds per timed step).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32; the inputs are fixed by the
+arguments, so two builds can be compared output for output).  --full adds everything that is not the headline: the `roofline`
+(per-kernel HIP-event brackets, board power / clock), the `cpu_baseline` and, on the default one-GPU line, the `secondary` rows.
 
 `python bench.py --gpus N` with N > 1 and no launcher environment re-executes itself under torch.distributed.run
 (127.0.0.1 rendezvous on a free port), so both invocation styles print the same single JSON line from rank 0.
@@ -165,13 +170,13 @@ class BoardSampler:
 def secondary_rows():
     """The rows of the path that are not the headline (the training step, the other BASELINE.json shapes, the
     HBM-bound transforms), each measured by its own process AFTER the headline's timed region and reported inside the same
-    JSON line, so that the driver's single default run sees them too.  None of this touches `value` / `ms_per_step`.
+    JSON line of a --full run.  None of this touches `value` / `ms_per_step`.
     A row that fails reports {"error": ...}; the headline is printed regardless."""
     import subprocess
     me = os.path.abspath(__file__)
     quick = bool(os.environ.get("FDIFF_BENCH_SECONDARY_QUICK"))          # (tests: a few steps per row)
     nd = ["--diffusion-steps", "20"] if quick else []           # (otherwise each workload's own step count: 1000 / 2000)
-    common = ["--no-cpu-baseline", "--no-secondary", "--gpus", "1"]
+    common = ["--full", "--no-cpu-baseline", "--no-secondary", "--gpus", "1"]
     rows = {
         "train_nasdaq_T252_B64": [me, "--mode", "train", "--train-workload", "nasdaq", "--steps", "5" if quick else "100"],
         "train_ecg_T100_B64": [me, "--mode", "train", "--train-workload", "ecg", "--steps", "5" if quick else "100"],
@@ -227,6 +232,26 @@ def rank_report(dist, rank, world, dev_index):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy (float32) per array the timed path returned in its last step.  Above DUMP_BYTES in all,
+    every array keeps a fixed, seeded sample of its rows (axis 0), and DIR/<name>_rows.npy (float64) names the rows kept."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            row = a.nbytes // a.shape[0] + 8                   # (a row and its index in <name>_rows.npy)
+            keep = max(1, DUMP_BYTES * a.nbytes // total // row)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main_train(args, rank, local_rank, world):
     """configs[2]: batch-sharded training.  Every rank holds 64 synthetic series (weak scaling); a step = one optimizer step."""
     TR = TRAIN_WORKLOADS[args.train_workload]
@@ -279,7 +304,7 @@ def main_train(args, rank, local_rank, world):
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    steps = args.steps if args.steps != 2 else 50           # (2 is the sampling default: an optimizer step is 1000x shorter)
+    steps = args.steps
     warmup = max(args.warmup, 3)
     for i in range(warmup):
         one_step(i)
@@ -290,18 +315,24 @@ def main_train(args, rank, local_rank, world):
     barrier()
     elapsed = time.perf_counter() - t0
     assert torch.isfinite(loss).all() and torch.isfinite(model.flat_parameters).all(), "training produced non-finite values"
+    if args.dump_outputs and rank == 0:     # (before the --full profiling steps below move the parameters on)
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+                                         "parameters": model.flat_parameters.detach().float().cpu().numpy(),
+                                         "gradients": model.grads.detach().float().cpu().numpy()})
     # Roofline leg: the five per-layer kernels are launched 50 times per step between other kernels of the same stream, and an event
     # record is a barrier packet of a few us.  Measured on MI355X (profiles/r04_train_prof_brackets.txt): with EVERY launch bracketed
     # the per-kernel averages agree with rocprofv3 but the step takes 14 % longer; with a sampled subset (every 7th / 23rd launch) the
     # step is nearly undisturbed but a bracket whose neighbours are not bracketed mis-times its kernel by up to 40 us (k_tr_ffn_bwd
     # 82 instead of 42 us, k_tr_attn_bwd 69 instead of 97).  So the timed region above runs without brackets, and PROF_STEPS more
     # optimizer steps of the same loop follow with every launch bracketed: fd_prof_end names the kernel with the largest total time.
+    # (--full only: a plain run reports roofline None)
     PROF_STEPS = 5
-    _C.check(lib.fd_prof_begin(ctx), ctx)
-    _C.check(lib.fd_prof_stride(ctx, int(os.environ.get("FDIFF_BENCH_PROF_STRIDE", "1"))), ctx)
-    for i in range(PROF_STEPS):
-        one_step(steps + i)
-    barrier()
+    if args.full:
+        _C.check(lib.fd_prof_begin(ctx), ctx)
+        _C.check(lib.fd_prof_stride(ctx, int(os.environ.get("FDIFF_BENCH_PROF_STRIDE", "1"))), ctx)
+        for i in range(PROF_STEPS):
+            one_step(steps + i)
+        barrier()
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -322,7 +353,7 @@ def main_train(args, rank, local_rank, world):
         avg_us, cnt, flops = C.c_double(0), C.c_int(0), C.c_double(0)
         name = C.create_string_buffer(128)
         roof = None
-        if lib.fd_prof_end(ctx, name, C.byref(avg_us), C.byref(cnt), C.byref(flops)) == 0 and cnt.value > 0:
+        if args.full and lib.fd_prof_end(ctx, name, C.byref(avg_us), C.byref(cnt), C.byref(flops)) == 0 and cnt.value > 0:
             peak = 2500.0 if model.train_mode_effective == "bf16" else 157.3
             ach = flops.value / (avg_us.value * 1e-6) / 1e12
             roof = {"bound": "mfma", "kernel": name.value.decode(), "achieved": ach, "peak": peak, "unit": "TFLOP/s",
@@ -334,7 +365,7 @@ def main_train(args, rank, local_rank, world):
         out["roofline"] = roof
         if ranks_info is not None:
             out["ranks"] = ranks_info
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 from oracle import torch_cpu_baseline as cb
                 out["cpu_baseline"] = cb.time_train_steps(batch=B, T=T, C=CH, d_model=D, num_layers=L, n_head=H)
@@ -348,7 +379,7 @@ def main_train(args, rank, local_rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 2 sampling runs, 50 optimizer steps)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", default="sample", choices=["sample", "train"])
     ap.add_argument("--workload", default="ecg", choices=sorted(WORKLOADS))
@@ -359,8 +390,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-workload", default="nasdaq", choices=sorted(TRAIN_WORKLOADS))
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the other rows of the path that the default one-GPU run measures after its timed region")
+                    help="skip the other rows of the path that the --full one-GPU run measures after its timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: roofline, cpu_baseline, secondary rows (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 50 if args.mode == "train" else 2       # (an optimizer step is ~200x shorter than a sampling run)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -442,9 +479,10 @@ def main():
     for i in range(args.warmup):
         one_step(i)
     barrier()
-    prof = True
-    _C.check(lib.fd_prof_begin(ctx), ctx)
-    sampler = BoardSampler() if rank == 0 else None      # (a thread that reads two sysfs nodes twice a second: no device work)
+    prof = args.full                                     # (a plain run reports roofline None)
+    if prof:
+        _C.check(lib.fd_prof_begin(ctx), ctx)
+    sampler = BoardSampler() if rank == 0 and prof else None   # (a thread that reads two sysfs nodes twice a second: no device work)
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
@@ -454,6 +492,8 @@ def main():
     elapsed = time.perf_counter() - t0
     board = sampler.stop() if sampler else None
     assert torch.isfinite(X).all(), "sampler produced non-finite values"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"samples": X.cpu().numpy()})
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -514,12 +554,12 @@ def main():
         out["roofline"] = roof
         if ranks_info is not None:
             out["ranks"] = ranks_info
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(B, T, CH)
             except Exception as e:   # the GPU result must still be reported
                 out["cpu_baseline"] = {"error": repr(e)}
-        if world == 1 and args.workload == "ecg" and not args.no_secondary:
+        if world == 1 and args.workload == "ecg" and args.full and not args.no_secondary:
             del X
             torch.cuda.empty_cache()
             out["secondary"] = secondary_rows()

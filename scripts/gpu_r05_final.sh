@@ -10,7 +10,7 @@ timeout 2400 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|erro
 cp $GRAFT_REPO_ROOT/gpurun_out/parity_errors.log $OUT/parity_errors.txt 2>/dev/null
 bash scripts/gpu_round.sh $TAG 2>&1 | cut -c1-300 | tail -60
 cd $GRAFT_REPO_ROOT
-python bench.py --workload long --no-cpu-baseline --no-secondary > $OUT/bench_long.json 2> $OUT/bench_long.err; tail -1 $OUT/bench_long.json | cut -c1-500
+python bench.py --full --workload long --no-cpu-baseline --no-secondary > $OUT/bench_long.json 2> $OUT/bench_long.err; tail -1 $OUT/bench_long.json | cut -c1-500
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_long -o long -- python $GRAFT_REPO_ROOT/bench.py --workload long --no-cpu-baseline --no-secondary > $OUT/stats_long.log 2>&1)
 python scripts/kstats.py $OUT/stats_long/long_kernel_stats.csv 5
 rm -f $OUT/stats_long/long_kernel_trace.csv

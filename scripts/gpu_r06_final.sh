@@ -16,7 +16,7 @@ bash scripts/gpu_ab.sh $TAG 3 "FDIFF_TR_PERSIST=0" "FDIFF_TR_PERSIST=1" -- pytho
 for v in trpprof; do
   if [ -f fourierdiffusion_amd/libfdiff_hip_$v.so ]; then bash scripts/gpu_r06_clk.sh $TAG $v "nasdaq ecg" | cut -c1-700; fi
 done
-python bench.py --workload long --no-cpu-baseline --no-secondary > $OUT/bench_long.json 2> $OUT/bench_long.err; tail -1 $OUT/bench_long.json | cut -c1-500
+python bench.py --full --workload long --no-cpu-baseline --no-secondary > $OUT/bench_long.json 2> $OUT/bench_long.err; tail -1 $OUT/bench_long.json | cut -c1-500
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_long -o long -- python $GRAFT_REPO_ROOT/bench.py --workload long --no-cpu-baseline --no-secondary > $OUT/stats_long.log 2>&1)
 python scripts/kstats.py $OUT/stats_long/long_kernel_stats.csv 5
 rm -f $OUT/stats_long/long_kernel_trace.csv

@@ -4,7 +4,7 @@
 R=${1:-r01}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$R
 mkdir -p $OUT
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -1 $OUT/bench.json | cut -c1-600
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -1 $OUT/bench.json | cut -c1-600
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-secondary > $OUT/stats.log 2>&1
 python $GRAFT_REPO_ROOT/scripts/kstats.py $OUT/stats/bench_kernel_stats.csv 8
@@ -32,7 +32,7 @@ PY
 
 # ---- training line (BASELINE.json configs[2] per-GPU shard) + per-kernel stats at both training shapes
 cd $GRAFT_REPO_ROOT
-python bench.py --mode train > $OUT/bench_train.json 2> $OUT/bench_train.err; tail -1 $OUT/bench_train.json | cut -c1-700
+python bench.py --full --mode train > $OUT/bench_train.json 2> $OUT/bench_train.err; tail -1 $OUT/bench_train.json | cut -c1-700
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_train -o train_nasdaq -- python $GRAFT_REPO_ROOT/bench.py --mode train --no-cpu-baseline > $OUT/stats_train.log 2>&1
 python $GRAFT_REPO_ROOT/scripts/kstats.py $OUT/stats_train/train_nasdaq_kernel_stats.csv 8

@@ -16,7 +16,7 @@ statse() {  # name, env...
 }
 python -m pytest tests/test_gpu_train_bf16.py tests/test_gpu_train.py tests/test_gpu_backbones.py -m gpu -x -q 2>&1 | grep -E "passed|failed|Error" | tail -3
 for ts in 16 24 32; do
-FDIFF_TR_TS=$ts python bench.py --mode train --no-cpu-baseline 2>/dev/null | tail -1 | line "TS=$ts"
+FDIFF_TR_TS=$ts python bench.py --full --mode train --no-cpu-baseline 2>/dev/null | tail -1 | line "TS=$ts"
 FDIFF_TR_TS=$ts python scripts/shape_bench.py train ecg 64 2>/dev/null | tail -1
 done
 NK=24 stats serial FDIFF_TR_SERIAL=1

@@ -8,7 +8,7 @@ python -m pytest tests/test_gpu_train_bf16.py tests/test_gpu_train.py -m gpu -x 
 for ts in $SWEEP; do
   for mode in nasdaq ecg; do
     if [ $mode = nasdaq ]; then
-      FDIFF_TR_TS=$ts python bench.py --mode train --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('TS=$ts nasdaq ms/step', round(d['ms_per_step'],3), d['roofline']['kernel'][:12], round(d['roofline']['avg_kernel_us'],1), 'us frac', round(d['roofline']['frac'],4))"
+      FDIFF_TR_TS=$ts python bench.py --full --mode train --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('TS=$ts nasdaq ms/step', round(d['ms_per_step'],3), d['roofline']['kernel'][:12], round(d['roofline']['avg_kernel_us'],1), 'us frac', round(d['roofline']['frac'],4))"
     else
       FDIFF_TR_TS=$ts python scripts/shape_bench.py train ecg 64 2>/dev/null | tail -1
     fi

@@ -21,7 +21,7 @@ def _free_port() -> int:
 def _worker(rank: int, world: int, port: int, out_dir: str) -> None:
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     import torch.distributed as dist
     from fourierdiffusion_amd.dataloaders.datamodules import BatchLoader, DiffusionDataset
     from fourierdiffusion_amd.parallel import GradExchange, init_process_group, shard_range
@@ -165,12 +165,20 @@ def test_world2_fit_small_last_batch_matches_single_process(tmp_path, n, bs, acc
     res = [torch.load(tmp_path / f"fit_{r}.pt") for r in range(world)]
     single = tmp_path / "single"
     single.mkdir()
-    _fit_single(str(single), n, bs, accum)
+    mp.spawn(_fit_single_worker, args=(str(single), n, bs, accum), nprocs=1, join=True)
     ref = torch.load(single / "fit_0.pt")
     assert res[0]["steps"] == res[1]["steps"] == ref["steps"]
     assert torch.equal(res[0]["w"], res[1]["w"])
     assert torch.allclose(res[0]["w"], ref["w"], rtol=0, atol=1e-12)
     assert res[0]["loss"] == pytest.approx(ref["loss"], rel=1e-9)
+
+
+def _fit_single_worker(_rank, out_dir, n, bs, accum):
+    """The single-process run in a process of its own that sees no GPU, as the ranks above (the datasets live on the GPU when
+    one is visible; the stand-in model is CPU-only)."""
+    os.environ.update(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    sys.path.insert(0, ROOT)
+    _fit_single(out_dir, n, bs, accum)
 
 
 def _fit_single(out_dir, n, bs, accum):

@@ -113,7 +113,7 @@ def test_bench_two_rank_rehearsal(launcher):
     line with the whole-job value), driven both ways: plain `python bench.py --gpus 2` (self-launching) and under
     torch.distributed.run.  The box has one GPU, so both ranks share cuda:0 and rendezvous over gloo
     (FDIFF_BENCH_BACKEND); on the 8-GPU node the same code runs with backend "nccl" (= RCCL)."""
-    d = _run_bench(["--batch", "64"], launcher)
+    d = _run_bench(["--batch", "64", "--full"], launcher)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 128 and d["scaling"] == "weak"
     assert d["value"] > 0 and d["roofline"]["frac"] > 0 and "cpu_baseline" not in d
     assert d["metric"] == "sampled series/sec (T=100, C=12)"
@@ -122,7 +122,7 @@ def test_bench_two_rank_rehearsal(launcher):
 def test_bench_train_mode_two_rank_rehearsal():
     """--mode train (BASELINE.json configs[2]): data-parallel optimizer steps, gradient exchange through the GradExchange
     interface (gloo here; fd_allreduce_grads over RCCL on the 8-GPU node)."""
-    d = _run_bench(["--mode", "train", "--batch", "8", "--steps", "3"], launcher=False)
+    d = _run_bench(["--mode", "train", "--batch", "8", "--steps", "3", "--full"], launcher=False)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 16 and d["scaling"] == "weak"
     assert d["metric"] == "training series/sec (T=252, C=6)" and d["value"] > 0 and d["dtype"] == "bf16"
     # the roofline names the bracketed training kernel with the largest TOTAL time in the window (fd_prof_end)
@@ -139,7 +139,7 @@ def test_bench_strong_scaling_rehearsal():
 
 
 def test_bench_default_line_carries_the_secondary_rows():
-    """The driver runs `python bench.py` once: the default one-GPU line also reports the training step, the other BASELINE
+    """`python bench.py --full`: the default one-GPU line also reports the training step, the other BASELINE
     shapes (configs[3], configs[4]) and the HBM-bound transforms, each measured by its own process after the headline's timed
     region (`secondary`; FDIFF_BENCH_SECONDARY_QUICK shortens the rows for this test)."""
     import json
@@ -149,7 +149,7 @@ def test_bench_default_line_carries_the_secondary_rows():
     env = dict(os.environ, FDIFF_BENCH_SECONDARY_QUICK="1", PYTHONPATH=root)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--diffusion-steps", "20", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--diffusion-steps", "20", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -165,6 +165,41 @@ def test_bench_default_line_carries_the_secondary_rows():
     assert sec["sample_mimic_T256_B512"]["roofline"]["kernel"].startswith("k_mega")
     hb = sec["hbm_kernels"]["shapes"]
     assert set(hb) == {"B4096_T256_C28", "B512_T1024_C16", "B512_T100_C12"} and all(v["dft_TBps"] > 0.1 for v in hb.values())
+
+
+def _run_bench_1gpu(args):
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + args, capture_output=True, text=True,
+                       timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) is the headline alone; --dump-outputs writes what the last timed step returned, and the same
+    arguments give the same inputs, hence the same outputs; --steps is the number of timed steps in both modes."""
+    args = ["--steps", "2", "--warmup", "1", "--diffusion-steps", "20", "--batch", "64"]
+    a = _run_bench_1gpu(args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run_bench_1gpu(args + ["--dump-outputs", str(tmp_path / "b")])
+    for d in (a, b):
+        assert d["metric"] == "sampled series/sec (T=100, C=12)" and d["unit"] == "series/s" and d["higher_is_better"] is True
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "bf16" and d["roofline"] is None
+        assert "cpu_baseline" not in d and "secondary" not in d
+    xa, xb = np.load(tmp_path / "a" / "samples.npy"), np.load(tmp_path / "b" / "samples.npy")
+    assert xa.dtype == np.float32 and xa.shape == (64, 100, 12) and np.isfinite(xa).all() and xa.std() > 0
+    np.testing.assert_array_equal(xa, xb)
+    t = _run_bench_1gpu(["--mode", "train", "--steps", "2", "--warmup", "3", "--dump-outputs", str(tmp_path / "t")])
+    assert t["steps"] == 2 and t["ms_per_step"] > 0 and t["roofline"] is None and "cpu_baseline" not in t
+    for name in ("loss", "parameters", "gradients"):
+        v = np.load(tmp_path / "t" / f"{name}.npy")
+        assert v.dtype == np.float32 and np.isfinite(v).all(), name
+    assert np.load(tmp_path / "t" / "parameters.npy").shape == np.load(tmp_path / "t" / "gradients.npy").shape
 
 
 def test_ecg_datamodule_preprocessing_on_the_engine(tmp_path):
