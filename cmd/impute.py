@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""python cmd/impute.py model_id=XYZ mask.kind=forecast mask.horizon=20 ... -- conditional sampling from a trained score model
+(an extension, not in the reference): hides entries of the test split (mask.kind random / forecast), fills them in with
+DiffusionSampler.impute on the MI355X engine, maps the result back to the time domain and writes imputations.pt (the test
+split's shape) next to the checkpoint, with the MSE / MAE over the hidden entries under the key `impute` of results.yaml.
+With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+from __future__ import annotations
+
+import logging
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+import torch  # noqa: E402
+import yaml  # noqa: E402
+
+from fourierdiffusion_amd import _rng  # noqa: E402
+from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
+from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
+from fourierdiffusion_amd.sampling.masks import observation_mask  # noqa: E402
+from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
+from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
+
+
+def hidden_errors(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor) -> dict:
+    """MSE / MAE of X against the ground truth over the hidden entries (mask False), and the largest deviation on the observed
+    ones (the conditioning reproduces them up to f32 transform rounding)."""
+    hid = ~mask
+    diff = (X.double() - truth.double())
+    out = {"num_series": int(X.shape[0]), "hidden_fraction": float(hid.double().mean())}
+    if hid.any():
+        out["mse_hidden"] = float((diff[hid] ** 2).mean())
+        out["mae_hidden"] = float(diff[hid].abs().mean())
+    if mask.any():
+        out["max_abs_err_observed"] = float(diff[mask].abs().max())
+    return out
+
+
+class ImputationRunner:
+    def __init__(self, cfg) -> None:
+        self.random_seed: int = cfg.random_seed
+        torch.manual_seed(self.random_seed)
+        logging.info(f"Welcome in the imputation script! You are using the following config:\n{dict_to_str(cfg)}")
+        self.dist = init_process_group()
+        _rng.set_rank(self.dist.rank)
+        self.dev_index = bind_device()
+        self.model_path = Path(cfg.model_path)
+        self.model_id = cfg.model_id
+        if self.model_id == "latest":
+            runs = sorted(p for p in self.model_path.iterdir() if (p / "train_config.yaml").exists())
+            self.model_id = runs[-1].name
+        self.save_dir = self.model_path / self.model_id
+        if self.dist.is_main:
+            save_yaml(cfg, self.save_dir / "impute_config.yaml")
+        train_cfg = load_yaml(self.save_dir / "train_config.yaml")
+        self.datamodule = instantiate(train_cfg.datamodule)
+        self.fourier_transform: bool = self.datamodule.fourier_transform
+        self.datamodule.prepare_data()
+        self.datamodule.setup()
+        self.num_diffusion_steps: int = cfg.num_diffusion_steps
+        self.mask_cfg = cfg.mask
+        best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
+        model_type = get_model_type(train_cfg)
+        self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path)
+        self.score_model.to(device=torch.device("cuda", self.dev_index))
+        self.sampler = instantiate(cfg.sampler)(score_model=self.score_model)
+
+    def impute(self) -> None:
+        truth = self.datamodule.X_test.float()
+        # the mask from its own generator: every rank builds the same one, and torch's global generator (the Philox keys) is untouched
+        gen = torch.Generator().manual_seed(self.random_seed)
+        mask = observation_mask(self.mask_cfg.kind, tuple(truth.shape), p=float(self.mask_cfg.get("p", 0.5)),
+                                horizon=int(self.mask_cfg.get("horizon", 1)), generator=gen)
+        observed = truth.masked_fill(~mask, float("nan"))                          # the sampler never sees a hidden entry
+        lo, hi = shard_range(int(truth.shape[0]), self.dist.rank, self.dist.world)  # independent rows: no exchange
+        mean = std = None
+        if self.datamodule.standardize:
+            mean, std = self.datamodule.feature_mean_and_std
+        X = None
+        if hi > lo:
+            X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
+                                    feature_mean=mean, feature_std=std)
+            if std is not None:
+                X = destandardize_idft(X, mean, std) if self.fourier_transform else X * std.cpu() + mean.cpu()
+            elif self.fourier_transform:
+                X = idft(X)
+        if self.dist.world > 1:
+            import torch.distributed as dist
+            parts = [None] * self.dist.world
+            dist.all_gather_object(parts, X)                                        # host-side gather of the results
+            X = torch.cat([p for p in parts if p is not None], dim=0)
+        if self.dist.is_main:
+            results_path = self.save_dir / "results.yaml"
+            results = yaml.safe_load(open(results_path)) if results_path.exists() else None
+            results = results if isinstance(results, dict) else {}
+            results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **hidden_errors(X, truth, mask)}
+            logging.info(f"Saving imputations and errors to {self.save_dir}.\n{dict_to_str(results['impute'])}")
+            yaml.dump(data=results, stream=open(results_path, "w"))
+            torch.save(X, self.save_dir / "imputations.pt")
+
+
+def main(argv=None) -> None:
+    logging.basicConfig(level=logging.INFO, format="[%(asctime)s] %(message)s")
+    cfg = compose(Path(__file__).parent / "conf", "impute", overrides=list(sys.argv[1:] if argv is None else argv))
+    ImputationRunner(cfg).impute()
+
+
+if __name__ == "__main__":
+    main()

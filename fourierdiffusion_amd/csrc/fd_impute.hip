@@ -1,0 +1,361 @@
+// fd_impute.hip -- conditional sampling: imputation and forecasting from observed time-domain values (NOT in the reference;
+// Song et al. 2021, Sec. 5 and App. I.2, the "inpainter" of score_sde).  After every reverse step the observed coordinates are
+// replaced by the observation noised to the next time level.  The observations live in the time domain at data scale, the
+// diffusion state in the standardised frequency domain, so the projection is a transform round trip:
+//
+//   d  = alpha x0_obs + s G z - x                     (sample space; G along T as in fd_perturb)
+//   x' = x + dft(m . idft(sigma . d)) / sigma         (fourier = 0: x' = m ? alpha x0_obs + s G z : x)
+//
+// which is A^-1(m . A(x_obs) + (1 - m) . A(x)) with A(x) = idft(sigma . x + mu): mu cancels, and so does the value of y at
+// unobserved entries.
+//
+// The packed real DFT as a T x T matrix F (y = F x, rows [0, T/2] Re X_k, rows (T/2, T) Im X_k, ortho norm) has orthogonal rows,
+// F F^T = diag(r) with r = 1 at DC and Nyquist (T even) and 1/2 elsewhere, so idft = F^T diag(1/r): one basis per T serves both
+// directions.  It is built once on the device in double, rounded to f32, zero-padded to Tp = 16 ceil(T/16) and cached on the
+// context next to the FFT tables (F and F^T, both row-major, so that both products read 16-byte runs along their k axis).
+//
+// One workgroup per (series, block of 16 channels).  Phase 1 (elementwise, Philox groups of 4 elements as k_sde_step): the
+// reverse-SDE step (fd_sde_apply, the expression of k_sde_step), then d; x_new goes to `out`, sigma d / r to the LDS image U.
+// Phase 2: V = F^T U (v_mfma_f32_16x16x4_f32, 16 time rows x 16 channels per tile), masked into the LDS image W.  Phase 3:
+// Y = F W, out += Y / sigma.  Both LDS images are Tp x 16 floats in k-quad order, [(k / 4)][channel][k % 4], so that the
+// B operand of four consecutive MFMAs is one conflict-free ds_read_b128 per lane; LDS = 128 Tp bytes (128 KiB at T = 1024).
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "fd_common.h"
+#include "fd_philox.h"
+#include "fd_score.h"
+#include "fd_sde.h"
+
+namespace {
+
+constexpr int kThreads = 512;    // 8 waves: the row tiles of a product are dealt round-robin
+constexpr int kCB = 16;          // channels per workgroup = N of the MFMA tile
+
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+struct ImpArgs {
+    const float* x;          // (B,T,C) state before the step (may alias out)
+    const float* score;      // (B,T,C) score at t_i (STEP only)
+    const float* zstep;      // (B,T,C) injected predictor noise or nullptr (Philox at off_step)
+    const float* x0;         // (B,T,C) A^-1(where(m, y, 0))
+    const uint8_t* mask;     // (B,T,C) or (T,C), 1 = observed, time domain
+    const float* stdv;       // (T,C) feature std of the packed spectrum or nullptr (= 1)
+    const float* G;          // (T)
+    const float* zobs;       // (B,T,C) injected observation noise or nullptr (Philox at off_obs)
+    const float* basis;      // F (Tp x Tp) then F^T (Tp x Tp)
+    float* out;
+    int B, T, C, Tp, ncb, mask_per_series;
+    SdeCoef cf;
+    float alpha, s;
+    uint64_t seed, off_step, off_obs;
+};
+
+// 1 / r of packed row k: 1 at DC and Nyquist (T even), 2 at every other bin (the Hermitian pair it stands for)
+__device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k == T)) ? 1.0f : 2.0f; }
+
+// LDS image index of (k, channel) in k-quad order
+__device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB + c) * 4 + (k & 3); }
+
+template <bool STEP, bool FOURIER>
+__global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
+    extern __shared__ float lds[];
+    float* U = lds;                            // sigma d / r, frequency rows
+    float* W = lds + (size_t)a.Tp * kCB;       // m . idft(sigma d), time rows
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
+    const int T = a.T, C = a.C, Tp = a.Tp;
+    const size_t TC = (size_t)T * C, base = (size_t)b * TC;
+    const uint8_t* mrow = a.mask + (a.mask_per_series ? base : 0);
+
+    if (FOURIER)
+        for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
+    if (FOURIER) __syncthreads();
+
+    // ---- phase 1: step + d, over the Philox groups that touch this series (a group straddling two series is drawn by both)
+    const size_t g_lo = base / 4, g_hi = (base + TC + 3) / 4;
+    for (size_t g = g_lo + tid; g < g_hi; g += kThreads) {
+        int loc[4];
+        bool own[4], any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t e = g * 4 + j;
+            own[j] = false;
+            loc[j] = 0;
+            if (e >= base && e < base + TC) {
+                loc[j] = (int)(e - base);
+                const int c = loc[j] % C;
+                own[j] = c >= c0 && c < c0 + kCB;
+            }
+            any |= own[j];
+        }
+        if (!any) continue;
+        float zs[4] = {0.f, 0.f, 0.f, 0.f}, zo[4] = {0.f, 0.f, 0.f, 0.f};
+        if (STEP) {
+            if (a.zstep) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (own[j]) zs[j] = a.zstep[base + loc[j]];
+            } else {
+                fd_randn4(a.off_step + g, a.seed, zs);
+            }
+        }
+        if (a.s != 0.f) {        // the hard projection (s = 0) reads no observation noise
+            if (a.zobs) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (own[j]) zo[j] = a.zobs[base + loc[j]];
+            } else {
+                fd_randn4(a.off_obs + g, a.seed, zo);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!own[j]) continue;
+            const size_t e = base + loc[j];
+            const int t = loc[j] / C, c = loc[j] % C;
+            const float Gt = a.G[t];
+            float xv = a.x[e];
+            if (STEP) xv = fd_sde_apply(xv, a.score[e], zs[j], Gt, a.cf);
+            const float xo = a.alpha * a.x0[e] + a.s * (Gt * zo[j]);
+            if (FOURIER) {
+                a.out[e] = xv;
+                const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
+                U[quad_idx(t, c - c0)] = sd * (xo - xv) * inv_r(t, T);
+            } else {
+                a.out[e] = mrow[(size_t)t * C + c] ? xo : xv;
+            }
+        }
+    }
+    if (!FOURIER) return;
+    __syncthreads();     // U complete; out holds x_new (workgroup-scope release / acquire covers the global stores)
+
+    const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
+    const int li = lane & 15, kq = lane >> 4;
+    const int ntile = Tp / 16;
+    const float* Fm = a.basis;
+    const float* Ft = a.basis + (size_t)Tp * Tp;
+
+    // ---- phase 2: V = F^T U (row i of the tile = time t0 + i); W = m ? V : 0
+    for (int tile = wave; tile < ntile; tile += nw) {
+        const int t0 = tile * 16;
+        const float* arow = Ft + (size_t)(t0 + li) * Tp + 4 * kq;
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < Tp; k0 += 16) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(U + ((k0 / 4 + kq) * kCB + li) * 4);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+        }
+        // lane holds V[t0 + 4 kq + v][li], v = 0..3: one k-quad of W
+        const int c = c0 + li;
+        f32x4 w;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int t = t0 + 4 * kq + v;
+            const bool keep = t < T && c < C && mrow[(size_t)t * C + c];
+            w[v] = keep ? acc0[v] + acc1[v] : 0.f;
+        }
+        *reinterpret_cast<f32x4*>(W + ((t0 / 4 + kq) * kCB + li) * 4) = w;
+    }
+    __syncthreads();
+
+    // ---- phase 3: Y = F W (row i of the tile = packed row r0 + i); out += Y / sigma
+    for (int tile = wave; tile < ntile; tile += nw) {
+        const int r0 = tile * 16;
+        const float* arow = Fm + (size_t)(r0 + li) * Tp + 4 * kq;
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < Tp; k0 += 16) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(W + ((k0 / 4 + kq) * kCB + li) * 4);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+        }
+        const int c = c0 + li;
+        if (c >= C) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = r0 + 4 * kq + v;
+            if (r >= T) continue;
+            const size_t e = base + (size_t)r * C + c;
+            const float sd = a.stdv ? a.stdv[(size_t)r * C + c] : 1.0f;
+            a.out[e] = a.out[e] + (acc0[v] + acc1[v]) / sd;
+        }
+    }
+}
+
+// F[r][t] (packed row r, time t) and its transpose, zero outside [0, T)^2, in double then rounded
+__global__ __launch_bounds__(256) void k_impute_basis(float* __restrict__ Fm, float* __restrict__ Ft, int T, int Tp) {
+    const size_t n = (size_t)Tp * Tp;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const int r = (int)(i / Tp), t = (int)(i % Tp);
+        float v = 0.f;
+        if (r < T && t < T) {
+            const int n_real = T / 2 + 1;
+            const bool im = r >= n_real;
+            const int k = im ? r - n_real + 1 : r;
+            double sn, cs;
+            sincospi(2.0 * (double)(((long long)k * t) % T) / (double)T, &sn, &cs);
+            v = (float)((im ? -sn : cs) / sqrt((double)T));
+        }
+        Fm[i] = v;
+        Ft[(size_t)t * Tp + r] = v;
+    }
+}
+
+constexpr int kBasisKey = 2 << 20;     // ctx->fft_tw key -T - kBasisKey (fd_fourier.hip uses T, -T and -T - 2^20)
+
+const float* impute_basis(fd_ctx* ctx, int T, int Tp, hipStream_t s) {
+    const int key = -T - kBasisKey;
+    for (auto& e : ctx->fft_tw)
+        if (e.first == key) return reinterpret_cast<const float*>(e.second);
+    void* d = nullptr;
+    if (hipMalloc(&d, sizeof(float) * 2 * (size_t)Tp * Tp) != hipSuccess) return nullptr;
+    float* Fm = reinterpret_cast<float*>(d);
+    hipLaunchKernelGGL(k_impute_basis, dim3((unsigned)std::min<size_t>(((size_t)Tp * Tp + 255) / 256, 4096)), dim3(256), 0, s, Fm,
+                       Fm + (size_t)Tp * Tp, T, Tp);
+    // once per (context, T): later callers may use another stream
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipFree(d);
+        return nullptr;
+    }
+    ctx->fft_tw.emplace_back(key, d);
+    return Fm;
+}
+
+template <bool STEP, bool FOURIER>
+int launch_variant(fd_ctx* ctx, const ImpArgs& a, size_t lds, hipStream_t s) {
+    static unsigned long long attr_set = 0;
+    if (FOURIER && fd_first_on_device(attr_set, ctx->device))
+        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_impute<STEP, FOURIER>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((k_impute<STEP, FOURIER>), dim3((unsigned)(a.B * a.ncb)), dim3(kThreads), FOURIER ? lds : 0, s, a);
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
+}
+
+// fills the shape / conditioning fields of `a` and checks them
+int prepare(fd_ctx* ctx, ImpArgs& a, const float* x0, const uint8_t* mask, int mask_per_series, const float* stdv, int fourier,
+            const float* G, int B, int T, int C, hipStream_t s, const char* who) {
+    FD_REQUIRE(ctx, x0 && mask && G, "%s: null pointer", who);
+    FD_REQUIRE(ctx, B > 0 && T > 0 && C > 0, "%s: B=%d T=%d C=%d", who, B, T, C);
+    FD_REQUIRE(ctx, !fourier || T <= 1024, "%s: max_len %d > 1024 (the LDS images of one series)", who, T);
+    a.B = B; a.T = T; a.C = C;
+    a.Tp = (T + 15) / 16 * 16;
+    a.ncb = (C + kCB - 1) / kCB;
+    FD_REQUIRE(ctx, (long long)B * a.ncb < (1ll << 31), "%s: B=%d too large for one launch", who, B);
+    a.x0 = x0; a.mask = mask; a.mask_per_series = mask_per_series ? 1 : 0;
+    a.stdv = fourier ? stdv : nullptr;
+    a.G = G;
+    a.basis = nullptr;
+    if (fourier) {
+        a.basis = impute_basis(ctx, T, a.Tp, s);
+        if (!a.basis) return fd_fail(ctx, FD_ERR_HIP, "%s: could not build the transform basis of T=%d", who, T);
+    }
+    return FD_OK;
+}
+
+int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s) {
+    const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
+    if (step) return fourier ? launch_variant<true, true>(ctx, a, lds, s) : launch_variant<true, false>(ctx, a, lds, s);
+    return fourier ? launch_variant<false, true>(ctx, a, lds, s) : launch_variant<false, false>(ctx, a, lds, s);
+}
+
+__global__ __launch_bounds__(256) void k_fill_t(float* __restrict__ p, const float* __restrict__ ts, int B, size_t n) {
+    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (i < n) p[i] = ts[i / B];
+}
+
+// marginal mean coefficient and std of the perturbation kernel at t (sde.py:108-123, 187-210), in double
+void marginal_coef(const fd_sde_params& p, double t, double* alpha, double* sdev) {
+    if (p.kind == 0) {
+        const double lmc = -0.25 * t * t * ((double)p.p1 - (double)p.p0) - 0.5 * t * (double)p.p0;
+        *alpha = std::exp(lmc);
+        *sdev = std::sqrt(1.0 - std::exp(2.0 * lmc));
+    } else {
+        *alpha = 1.0;
+        *sdev = (double)p.p0 * std::pow((double)p.p1 / (double)p.p0, t);
+    }
+}
+
+}  // namespace
+
+extern "C" int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                 const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
+                                 uint64_t seed, uint64_t offset, float* out, int B, int T, int C, void* stream) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, x && out, "fd_impute_project: null pointer");
+    hipStream_t hs = (hipStream_t)stream;
+    ImpArgs a{};
+    if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, hs, "fd_impute_project")) return rc;
+    a.x = x; a.out = out;
+    a.zobs = z;
+    a.alpha = alpha; a.s = s;
+    a.seed = seed; a.off_obs = offset;
+    return launch(ctx, a, false, fourier != 0, hs);
+}
+
+extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                     float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                     const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps,
+                                     uint64_t seed, uint64_t offset, int B, int mode, void* stream) {
+    if (!m) return FD_ERR_ARG;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, sde && G && timesteps && x, "fd_sampler_run_impute: null pointer");
+    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_sampler_run_impute: unknown SDE kind %d", sde->kind);
+    FD_REQUIRE(ctx, n_steps > 0 && B > 0, "fd_sampler_run_impute: n_steps=%d B=%d", n_steps, B);
+    FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_impute: step size must be > 0 (sde.py:158)");
+    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_sampler_run_impute: unknown mode %d", mode);
+    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_sampler_run_impute: call fd_score_prepare first");
+    hipStream_t s = (hipStream_t)stream;
+    const int T = m->d.max_len, C = m->d.n_channels;
+    ImpArgs a{};
+    if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, "fd_sampler_run_impute"))
+        return rc;
+    // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
+    // at the next grid point; the last step projects hard (alpha = 1, s = 0)
+    std::vector<SdeCoef> cf(n_steps);
+    std::vector<float> al(n_steps), sd(n_steps);
+    for (int i = 0; i < n_steps; ++i) {
+        cf[i] = fd_sde_coef(*sde, (double)timesteps[i], dt);
+        double aa = 1.0, ss = 0.0;
+        if (i + 1 < n_steps) marginal_coef(*sde, (double)timesteps[i + 1], &aa, &ss);
+        al[i] = (float)aa;
+        sd[i] = (float)ss;
+    }
+    // workspace as fd_sampler_run's step-by-step path: [forward scratch | score | t vectors of every step | timesteps]
+    const size_t n = (size_t)B * T * C;
+    const size_t fwd = (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
+    const size_t own = fd_ws::padded(n * sizeof(float));
+    const size_t nt = (size_t)n_steps * B;
+    if (int rc = fd_ws_reserve(ctx, fwd + own + fd_ws::padded(nt * sizeof(float)) + fd_ws::padded((size_t)n_steps * sizeof(float))))
+        return rc;
+    float* score = (float*)((char*)ctx->ws + fwd);
+    float* tvec0 = (float*)((char*)ctx->ws + fwd + own);
+    float* ts = (float*)((char*)tvec0 + fd_ws::padded(nt * sizeof(float)));
+    // pageable source: the runtime stages the copy before returning
+    FD_HIP(ctx, hipMemcpyAsync(ts, timesteps, (size_t)n_steps * sizeof(float), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fill_t, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, tvec0, ts, B, nt);
+    FD_LAUNCH_CHECK(ctx);
+
+    // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run), observation noise behind them
+    const uint64_t per_step = (uint64_t)((n + 3) / 4);
+    a.x = x; a.out = x; a.score = score;
+    a.seed = seed;
+    for (int i = 0; i < n_steps; ++i) {
+        if (int rc = fd_score_forward_any(m, x, tvec0 + (size_t)i * B, score, B, mode, s)) return rc;
+        a.zstep = z_steps ? z_steps + (size_t)i * n : nullptr;
+        a.zobs = zobs_steps ? zobs_steps + (size_t)i * n : nullptr;
+        a.cf = cf[i];
+        a.alpha = al[i];
+        a.s = sd[i];
+        a.off_step = offset + (uint64_t)i * per_step;
+        a.off_obs = offset + (uint64_t)(n_steps + i) * per_step;
+        if (int rc = launch(ctx, a, true, fourier != 0, s)) return rc;
+    }
+    return FD_OK;
+}

@@ -13,6 +13,11 @@ default.yaml -- with num_samples = 10 000, cmd/conf/sample.yaml); series never i
 packs S series per workgroup and wants S x (number of CUs) of them per launch (512 at T = 100 on MI355X: 1190
 series/s against 600 with launches of 200).  Injected-noise calls (parity tests) keep one launch per batch;
 ``merge_batches=False`` / FDIFF_SAMPLER_MERGE=0 keep the reference's launches.
+
+Conditional sampling (an extension, not in the reference): ``impute`` fills in the unobserved entries of time-domain series
+(imputation, forecasting) by projecting the state onto the observations after every reverse step (Song et al. 2021, Sec. 5,
+App. I.2), the step and the projection fused in one engine launch (fd_sampler_run_impute); ``impute_project`` is the
+projection alone.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ from .. import _C, _rng
 from ..models.score_models import _PRECISIONS, ScoreModule
 from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
+from ..utils.fourier import dft, dft_standardize
 
 
 class DiffusionSampler:
@@ -101,6 +107,141 @@ class DiffusionSampler:
             _C.check(rc, ctx)
             all_samples.append(X)
         return torch.cat([x.cpu() for x in all_samples], dim=0)
+
+    # ------------------------------------------------------------ conditional sampling (extension, not in the reference)
+    def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,
+               fourier_transform: bool, feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
+               prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
+               obs_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+        """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
+        it back with the caller's destandardise / idft), one series per row of ``observed``.
+
+        observed (n, T, C): time-domain values at data scale (entries where ``mask`` is False are ignored, NaN allowed); mask: bool,
+        (n, T, C) or (T, C), True = observed.  fourier_transform / feature_mean / feature_std: the datamodule's representation
+        (``fourier_transform``, ``feature_mean_and_std`` when it standardises, else None).  Every reverse step of the grid of
+        ``sample`` is followed by the projection onto the observations noised to the next time level; the last one is exact, so
+        the observed entries of the result reproduce ``observed`` up to f32 transform rounding.  Launches of at most
+        ``sample_batch_size`` series; launch b's noise: prior_noise[b] (nb,T,C), step_noise[b] / obs_noise[b] (N,nb,T,C)
+        (slot N-1 of obs_noise is not read), else the engine's Philox stream, drawn in the order of ``sample``."""
+        if self.corrector_steps > 0:
+            raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
+        obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
+        model = self.score_model
+        model.eval()
+        sch = self.noise_scheduler
+        N = model.num_training_steps if num_diffusion_steps is None else num_diffusion_steps
+        sch.set_timesteps(N)
+        ctx, h = model._engine()
+        dev = model.device
+        ts_arr = (C.c_float * N)(*sch.timesteps.to(torch.float32).tolist())
+        dt = float(sch.step_size)
+        p = sch._c_params()
+        G = sch.G_on(dev)
+        mode = _PRECISIONS[model.precision_effective]
+        fstd = std if fourier_transform else None
+        n, bs = obs.shape[0], self.sample_batch_size
+        out: List[torch.Tensor] = []
+        for b, lo in enumerate(range(0, n, bs)):
+            nb = min(bs, n - lo)
+            X = self.sample_prior(nb, noise=None if prior_noise is None else prior_noise[b])
+            z = None if step_noise is None else self._noise(step_noise[b], (N, nb), "step_noise")
+            zo = None if obs_noise is None else self._noise(obs_noise[b], (N, nb), "obs_noise")
+            key, off = (0, 0) if (z is not None and zo is not None) else _rng.stream()
+            m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
+            x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
+            rc = _C.lib().fd_sampler_run_impute(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
+                                                _C.ptr(z), _C.ptr(zo), key, off, nb, mode, _C.stream_of(X))
+            _C.check(rc, ctx)
+            out.append(X)
+        return torch.cat([x.cpu() for x in out], dim=0)
+
+    def impute_project(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: Optional[float] = None, *,
+                       fourier_transform: bool, feature_std: Optional[torch.Tensor] = None,
+                       noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The projection of ``impute`` alone (its step-wise twin, as ``reverse_diffusion_step`` is ``sample``'s): X (B,T,C) in
+        sample space -> A^-1(m A(x_obs) + (1 - m) A(X)), x_obs = alpha x0_obs + s G z with (alpha, s) the perturbation kernel at
+        ``timestep`` (None: alpha = 1, s = 0, the exact projection).  x0_obs from ``observed_to_sample_space``; noise: injected
+        z (B,T,C) or None (Philox).  Returns a new device tensor."""
+        xd = _C.dev_f32(X.to(self.score_model.device), "X")
+        x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
+        if x0.shape != xd.shape or xd.dim() != 3:
+            raise ValueError(f"impute_project: X {tuple(xd.shape)} and x0_obs {tuple(x0.shape)} must be the same (B,T,C) shape")
+        B, T, Cn = xd.shape
+        m_u8, per_series = self._mask_u8(mask, B, T, Cn, xd.device)
+        std = None
+        if fourier_transform and feature_std is not None:
+            std = _C.dev_f32(feature_std.to(xd.device), "feature_std")
+            if tuple(std.shape) != (T, Cn):
+                raise ValueError(f"impute_project: feature_std must have shape {(T, Cn)}, got {tuple(std.shape)}")
+        sch = self.noise_scheduler
+        alpha, sdev = (1.0, 0.0) if timestep is None else sch.marginal_coef(timestep)
+        z = None if noise is None else self._noise(noise, (), "noise", B)
+        key, off = (0, 0) if (z is not None or sdev == 0.0) else _rng.stream()
+        out = torch.empty_like(xd)
+        h = _C.ctx(xd.device)
+        rc = _C.lib().fd_impute_project(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
+                                        int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha), float(sdev),
+                                        _C.ptr(z), key, off, out.data_ptr(), B, T, Cn, _C.stream_of(xd))
+        _C.check(rc, h)
+        return out
+
+    def observed_to_sample_space(self, observed: torch.Tensor, mask: torch.Tensor, *, fourier_transform: bool,
+                                 feature_mean: Optional[torch.Tensor] = None,
+                                 feature_std: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x0_obs = A^-1(where(mask, observed, 0)) on the device (what ``impute`` conditions on; the input of ``impute_project``)."""
+        obs, mask_u8, _, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
+        return self._x0_obs(obs, mask_u8, fourier_transform, mean, std)
+
+    def _conditioning(self, observed, mask, feature_mean, feature_std):
+        """Validated device copies: observed (n,T,C) f32, mask as uint8 (n,T,C) or (T,C), per-series flag, mean, std."""
+        if not isinstance(observed, torch.Tensor) or not isinstance(mask, torch.Tensor):
+            raise ValueError("observed and mask must be torch tensors")
+        T, Cn = self.max_len, self.n_channels
+        if observed.dim() != 3 or tuple(observed.shape[1:]) != (T, Cn):
+            raise ValueError(f"observed must have shape (n, {T}, {Cn}), got {tuple(observed.shape)}")
+        if not observed.is_floating_point():
+            raise ValueError(f"observed must be a floating-point tensor, got {observed.dtype}")
+        n = observed.shape[0]
+        if n == 0:
+            raise ValueError("observed is an empty batch")
+        dev = self.score_model.device
+        m_u8, per_series = self._mask_u8(mask, n, T, Cn, dev)
+        if (feature_mean is None) != (feature_std is None):
+            raise ValueError("feature_mean and feature_std go together (both or neither)")
+        mean = std = None
+        if feature_std is not None:
+            mean = _C.dev_f32(feature_mean.to(dev), "feature_mean")
+            std = _C.dev_f32(feature_std.to(dev), "feature_std")
+            if tuple(mean.shape) != (T, Cn) or tuple(std.shape) != (T, Cn):
+                raise ValueError(f"feature_mean / feature_std must have shape {(T, Cn)}, got {tuple(mean.shape)} / {tuple(std.shape)}")
+        return _C.dev_f32(observed.to(dev), "observed"), m_u8, per_series, mean, std
+
+    @staticmethod
+    def _mask_u8(mask: torch.Tensor, n: int, T: int, Cn: int, dev) -> tuple:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+            raise ValueError(f"mask must be a bool tensor, got {getattr(mask, 'dtype', type(mask))}")
+        if tuple(mask.shape) == (n, T, Cn):
+            per_series = True
+        elif tuple(mask.shape) == (T, Cn):
+            per_series = False
+        else:
+            raise ValueError(f"mask must have shape {(n, T, Cn)} or {(T, Cn)}, got {tuple(mask.shape)}")
+        return mask.to(device=dev, dtype=torch.uint8).contiguous(), per_series
+
+    def _noise(self, z: torch.Tensor, lead: tuple, name: str, nb: Optional[int] = None) -> torch.Tensor:
+        zd = _C.dev_f32(z.to(self.score_model.device), name)
+        want = tuple(lead) + ((nb,) if nb is not None else ()) + (self.max_len, self.n_channels)
+        if tuple(zd.shape) != want:
+            raise ValueError(f"{name} must have shape {want}, got {tuple(zd.shape)}")
+        return zd
+
+    @staticmethod
+    def _x0_obs(obs: torch.Tensor, m_u8: torch.Tensor, fourier_transform: bool, mean, std) -> torch.Tensor:
+        y0 = torch.where(m_u8.bool(), obs, torch.zeros((), dtype=obs.dtype, device=obs.device))   # NaN at unobserved entries: gone
+        if fourier_transform:
+            return dft_standardize(y0, mean, std) if std is not None else dft(y0)
+        return ((y0 - mean) / std).contiguous() if std is not None else y0.contiguous()
 
     def _launch_sizes(self, total: int, mode: int) -> List[int]:
         """`total` series cut into launches the device runs full: multiples of (series per workgroup of the persistent kernel at a

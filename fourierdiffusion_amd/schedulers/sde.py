@@ -104,6 +104,16 @@ class SDE(abc.ABC):
         _C.check(rc, h)
         return mean, std
 
+    def marginal_coef(self, t: float) -> Tuple[float, float]:
+        """(alpha(t), s(t)) of the perturbation kernel x_t = alpha x_0 + s G z, as Python floats (VP sde.py:187-210: alpha =
+        exp(lmc), s = sqrt(1 - exp(2 lmc)); VE sde.py:108-123: alpha = 1, s = sigma_min (sigma_max / sigma_min)^t)."""
+        p0, p1 = self._params()
+        t = float(t)
+        if self.kind == 0:
+            lmc = -0.25 * t * t * (p1 - p0) - 0.5 * t * p0
+            return math.exp(lmc), math.sqrt(1.0 - math.exp(2.0 * lmc))
+        return 1.0, p0 * (p1 / p0) ** t
+
     def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
         """mean(x0, t) + noise -- the noise is already scaled by the caller (sde.py:66-77)."""
         mean, _ = self.marginal_prob(original_samples, timesteps)

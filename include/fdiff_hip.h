@@ -300,6 +300,30 @@ int fd_sampler_run_pc(fd_score* m, const fd_sde_params* sde, const float* G, con
                       float* x, const float* z_steps, const float* zc_steps, int n_corr, float snr, uint64_t seed,
                       uint64_t offset, int B, int mode, void* stream);
 
+/* Conditional sampling extension (NOT in the reference): imputation and forecasting from observed time-domain values
+ * (Song et al. 2021, Sec. 5 / App. I.2, score_sde's inpainter).  y (T,C) observations at data scale, m its 0/1 mask (1 =
+ * observed, time domain), x0_obs = A^-1(where(m, y, 0)) in sample space with A(x) = idft(sigma x + mu) (fourier != 0) or
+ * sigma x + mu.  The projection at time level tau, z ~ N(0, I) in sample space:
+ *   d  = alpha(tau) x0_obs + s(tau) G z - x ;  x' = x + dft(m . idft(sigma . d)) / sigma   (fourier == 0: x' = m ? x_obs : x)
+ * i.e. A^-1(m A(x_obs) + (1 - m) A(x)) with x_obs = alpha x0_obs + s G z (mu cancels).  mask_u8: (B,T,C) when mask_per_series,
+ * else one (T,C) mask for every series.  feat_std: the (T,C) feature std of the standardised spectrum, NULL = 1 (read only
+ * when fourier != 0).  T <= 1024 when fourier != 0.
+ *   fd_impute_project    : the projection alone (out may alias x); z == NULL -> Philox (seed; element e at offset + e/4).
+ *   fd_sampler_run_impute: fd_sampler_run with a projection behind every step, the reverse step and the projection fused in one
+ *                          launch: step i projects at tau = t_{i+1} (alpha, s of marginal_prob; VE alpha = 1), the last step
+ *                          hard (alpha = 1, s = 0).  One score launch per step (bf16: the persistent kernel in single-step mode).
+ *                          Philox (seed): predictor noise of step i at offset + i*ceil(BTC/4) + e/4 (as fd_sampler_run),
+ *                          observation noise at offset + (n_steps + i)*ceil(BTC/4) + e/4.  z_steps, zobs_steps: injected
+ *                          (n_steps,B,T,C) noise or NULL (slot n_steps-1 of zobs_steps is not read).  No host synchronisation
+ *                          in the loop (the first call for a T builds the transform basis and waits for it). */
+int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                      const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z, uint64_t seed,
+                      uint64_t offset, float* out, int B, int T, int C, void* stream);
+int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt,
+                          float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
+                          int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B,
+                          int mode, void* stream);
+
 /* ------------------------------------------------------------ a11 optimiser
  * torch.optim.AdamW defaults + diffusers cosine-warmup + Lightning global-norm clip
  * (score_models.py:122-130, cmd/conf/trainer/default.yaml:4), fused over the flat buffer.
