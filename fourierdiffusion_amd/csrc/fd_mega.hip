@@ -32,9 +32,9 @@ void fd_mega_temb_table(const fd_mega_params& P, float* table, hipStream_t s) {
                        table, P.D);
 }
 
-template <int KS1, int DT, int KSO, int MT, class SH, int NW = 8>
+template <int KS1, int DT, int KSO, int MT, class SH, bool ODE, int NW = 8>
 static int launch_mega_t(fd_ctx* ctx, const fd_mega_params& P, int grid, size_t lds, hipStream_t s) {
-    auto kern = k_mega<KS1, DT, KSO, MT, SH, NW>;
+    auto kern = k_mega<KS1, DT, KSO, MT, SH, NW, ODE>;
     static unsigned long long attr = 0;
     if (fd_first_on_device(attr, ctx->device))
         FD_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (NW == 8 ? 160 : 80) * 1024));
@@ -66,11 +66,13 @@ static bool shape_matches(const fd_mega_params& P, int ks1, int dt, int kso, int
 #define FD_MEGA_GO(K, T_, O, M_, SH, NAME)                                                             \
     do {                                                                                               \
         if (describe) {                                                                                \
-            snprintf(describe, 192, "k_mega<%d,%d,%d,%d,%s> S=%d NPG=%d rot=%d grid=%d lds=%zu%s%s", K, T_, O, M_, NAME, P.S, \
-                     P.NPG, P.rot, grid, lds, SH::FFN32 ? " ffn32 (H by 32x32x16 MFMAs on token-tile pairs)" : "", FD_MEGA_NOTE); \
+            snprintf(describe, 192, "k_mega<%d,%d,%d,%d,%s%s> S=%d NPG=%d rot=%d grid=%d lds=%zu%s%s", K, T_, O, M_, NAME,     \
+                     P.mode == FD_MEGA_ODE ? ",ode" : "", P.S, P.NPG, P.rot, grid, lds,                          \
+                     SH::FFN32 ? " ffn32 (H by 32x32x16 MFMAs on token-tile pairs)" : "", FD_MEGA_NOTE);       \
             return FD_OK;                                                                              \
         }                                                                                              \
-        return launch_mega_t<K, T_, O, M_, SH>(ctx, P, grid, lds, s);                                  \
+        if (P.mode == FD_MEGA_ODE) return launch_mega_t<K, T_, O, M_, SH, true>(ctx, P, grid, lds, s);    \
+        return launch_mega_t<K, T_, O, M_, SH, false>(ctx, P, grid, lds, s);                           \
     } while (0)
 
 int fd_mega_launch(fd_ctx* ctx, const fd_mega_params& P, int ks1, int dt, int kso, int mt, int nw, int grid, size_t lds,
@@ -89,12 +91,12 @@ int fd_mega_launch(fd_ctx* ctx, const fd_mega_params& P, int ks1, int dt, int ks
     char rtc_note[160] = "";
     if (jit != FD_MEGA_RTC_OFF) {
         fd_mega_rtc_key key{};
-        key.ks1 = ks1; key.dt = dt; key.kso = kso; key.mt = mt;
+        key.ks1 = ks1; key.dt = dt; key.kso = kso; key.mt = mt; key.ode = P.mode == FD_MEGA_ODE;
         key.T = P.T; key.D = P.D; key.C = P.C; key.H = P.H; key.S = P.S; key.NPG = P.NPG; key.rot = P.rot; key.L = P.L; key.F = P.F;
         const int ntile = P.S * P.KT;
         key.ffn32 = (FD_MEGA_FFN32 && dt == 2 * ks1 - 1 && P.off_ffn32 != 0 &&
                      ((mt == 4 && ntile >= 12 && (ntile & 1) == 0) || (mt == 3 && ntile == 12))) ? 1 : 0;
-        const bool wanted = jit >= FD_MEGA_RTC_ALWAYS || (P.mode == FD_MEGA_SAMPLE && P.nsteps >= FD_MEGA_RTC_MIN_STEPS);
+        const bool wanted = jit >= FD_MEGA_RTC_ALWAYS || (P.mode != FD_MEGA_FORWARD && P.nsteps >= FD_MEGA_RTC_MIN_STEPS);
         if (wanted) {
             void* fn = nullptr;
             std::string why;

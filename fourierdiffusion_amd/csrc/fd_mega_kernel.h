@@ -252,7 +252,9 @@ __global__ __launch_bounds__(64) void k_temb_table(const float* __restrict__ par
 // NW = waves per workgroup (8: one workgroup per CU, up to 16 token tiles).  A 4-wave form (two co-resident
 // workgroups per CU, one series each) was measured: the younger workgroup of each CU loses issue arbitration and
 // finishes 25 % later than the older one, 0.65 vs 0.565 ms per diffusion step -- only NW = 8 is instantiated.
-template <int KS1, int DT, int KSO, int MT, class SH, int NW>
+// ODE: the probability-flow ODE loop (P.mode == FD_MEGA_ODE) -- its own instantiation, so that the epilogue of the other modes
+// compiles exactly as without it (a run-time branch moved the SGPR spills and scratch of the SDE loop).
+template <int KS1, int DT, int KSO, int MT, class SH, int NW, bool ODE = false>
 __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
     constexpr int KSX = KS1;                     // x-fragment blocks per token tile (the host's LDS plan; the pair form needs less)
     // head_dim 8 (the d_model 64 / 8 heads class, KSO = 2): a head's dims fill its 8 k-slots, so there is no free slot for the softmax
@@ -435,7 +437,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
     for (int i = threadIdx.x; i < NTILE * KSX * 64; i += NTH) reinterpret_cast<u32x4*>(xfr)[i] = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
 
-    const int nsteps = (P.mode == FD_MEGA_SAMPLE) ? P.nsteps : 1;
+    const int nsteps = (ODE || P.mode == FD_MEGA_SAMPLE) ? P.nsteps : 1;
     if (P.clk_out && blockIdx.x == 0 && wave == 0 && lane == 0) {     // (stored at once: nothing stays live across the kernel)
         P.clk_out[0] = __builtin_readcyclecounter();
         P.clk_out[1] = wall_clock64();
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
             for (int sw = wave; sw < S; sw += NW) {       // one wave per series
                 const int b = b0 + sw;
                 float tv = 0.f;
-                if (b < P.B) tv = (P.mode == FD_MEGA_SAMPLE) ? P.steps[step].t : P.tvec[b];
+                if (b < P.B) tv = (ODE || P.mode == FD_MEGA_SAMPLE) ? P.steps[step].t : P.tvec[b];
                 time_embed_wave(tv, P.params, P.tW, P.td_w, P.td_b, temb + (S + sw) * D, temb + sw * D, D, lane);
             }
         }
@@ -1590,7 +1592,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                     const int c0 = 16 * ct + 4 * g;
                     if (valid && c0 < C) {
                         const size_t e0 = ((size_t)(b0 + ser) * T + t) * C + c0;      // element index in (B,T,C)
-                        if (P.mode == FD_MEGA_SAMPLE) {
+                        if (!ODE && P.mode == FD_MEGA_SAMPLE) {
                             // The noise stream is the standalone fd_sde_step's: Philox counter q yields the normals of
                             // elements 4q..4q+3 of the flattened (B,T,C) array.  C % 4 == 0: this lane's 4 channels are
                             // exactly one counter and one aligned float4; otherwise they straddle two counters.
@@ -1629,6 +1631,21 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                         P.x[e0 + r] = xv - (-cf.a_x * xv - (gk * gk) * sc[r]) * cf.dt + cf.sqrt_dt * (gk * z);
                                     }
                                 }
+                            }
+                        } else if (ODE) {
+                            // probability-flow ODE stage: this lane owns elements e0 .. e0+3 in every evaluation, so its Heun
+                            // state (ode_x0 / ode_v0 at the same indices) needs no synchronisation between the two stages
+                            const fd_ode_step_coef oc = reinterpret_cast<const fd_ode_step_coef*>(P.steps)[step];
+                            const float gk = oc.g * P.G[t];
+                            if ((C & 3) == 0) {
+                                const float4 xv = *reinterpret_cast<const float4*>(P.x + e0);
+                                *reinterpret_cast<float4*>(P.x + e0) =
+                                    fd_ode_stage4(xv, sc[0], sc[1], sc[2], sc[3], gk, oc, P.ode_x0 + e0, P.ode_v0 + e0);
+                            } else {
+#pragma unroll
+                                for (int r = 0; r < 4; ++r)
+                                    if (c0 + r < C)
+                                        P.x[e0 + r] = fd_ode_stage1(P.x[e0 + r], sc[r], gk, oc, P.ode_x0 + e0 + r, P.ode_v0 + e0 + r);
                             }
                         } else {
 #pragma unroll

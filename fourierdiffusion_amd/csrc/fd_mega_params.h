@@ -1,5 +1,6 @@
-// fd_mega_params.h -- parameter block of the persistent series-resident kernel (fd_mega_kernel.h).  Plain data only: this header is
-// also handed to hiprtc (fd_mega_rtc.hip), which has no host headers.
+// fd_mega_params.h -- parameter block of the persistent series-resident kernel (fd_mega_kernel.h).  Plain data and the one-line
+// probability-flow velocity shared by every ODE epilogue: this header is also handed to hiprtc (fd_mega_rtc.hip), which has no host
+// headers.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <cstddef>
@@ -10,10 +11,56 @@
 #endif
 #define FD_MEGA_FORWARD 0   // one score-network forward: x, tvec -> score_out
 #define FD_MEGA_SAMPLE 1    // nsteps x {forward, reverse-SDE step}, x updated in place
+#define FD_MEGA_ODE 2       // nsteps x {forward, probability-flow ODE stage}: nsteps counts score evaluations, x updated in place
 
 struct fd_sde_step_coef {
     float a_x, g, dt, sqrt_dt, t;   // SdeCoef of fd_sde.h + the timestep itself (time embedding)
 };
+
+// Probability-flow ODE (Song et al. 2021, Sec. 4.3): one row per score evaluation.  Stages: FD_ODE_EULER x' = x + h v;
+// FD_ODE_HEUN_PREDICT x0 = x, v0 = v, x' = x + h v;  FD_ODE_HEUN_CORRECT x' = x0 + h/2 (v0 + v)  (x0, v0: (B,T,C) workspace,
+// the same element owned by the same lane in both stages).  t sits where fd_sde_step_coef keeps it, so the time-embedding
+// table builder (k_temb_table) reads either row type.
+#define FD_ODE_EULER 0
+#define FD_ODE_HEUN_PREDICT 1
+#define FD_ODE_HEUN_CORRECT 2
+struct fd_ode_step_coef {
+    float a_x, g;   // SdeCoef of fd_sde.h at this evaluation's t
+    float h;        // t_{i+1} - t_i of the step the evaluation belongs to (< 0 sampling, > 0 encoding)
+    int stage;      // FD_ODE_*
+    float t;        // time of the evaluation (time embedding)
+};
+static_assert(sizeof(fd_ode_step_coef) == sizeof(fd_sde_step_coef) &&
+                  __builtin_offsetof(fd_ode_step_coef, t) == __builtin_offsetof(fd_sde_step_coef, t),
+              "fd_ode_step_coef must keep t where fd_sde_step_coef has it");
+
+// velocity of the probability-flow ODE: v = -a x - 0.5 (g G_k)^2 s  (fd_sde_apply's drift with the score term halved)
+__device__ __forceinline__ float fd_ode_velocity(float x, float s, float a_x, float gk) {
+    return -a_x * x - (0.5f * (gk * gk)) * s;
+}
+// one ODE stage on one element (x: state, s: score, gk = g G_k); x0 / v0 point at the element's Heun state
+__device__ __forceinline__ float fd_ode_stage1(float x, float s, float gk, const fd_ode_step_coef& c, float* x0, float* v0) {
+    const float v = fd_ode_velocity(x, s, c.a_x, gk);
+    if (c.stage == FD_ODE_HEUN_CORRECT) return *x0 + (0.5f * c.h) * (*v0 + v);
+    if (c.stage == FD_ODE_HEUN_PREDICT) { *x0 = x; *v0 = v; }
+    return x + c.h * v;
+}
+// the same on four consecutive elements of one row (16-byte aligned: C % 4 == 0)
+__device__ __forceinline__ float4 fd_ode_stage4(float4 x, float s0, float s1, float s2, float s3, float gk, const fd_ode_step_coef& c,
+                                                float* x0, float* v0) {
+    const float4 v = {fd_ode_velocity(x.x, s0, c.a_x, gk), fd_ode_velocity(x.y, s1, c.a_x, gk), fd_ode_velocity(x.z, s2, c.a_x, gk),
+                      fd_ode_velocity(x.w, s3, c.a_x, gk)};
+    if (c.stage == FD_ODE_HEUN_CORRECT) {
+        const float4 a = *reinterpret_cast<const float4*>(x0), b = *reinterpret_cast<const float4*>(v0);
+        const float hh = 0.5f * c.h;
+        return float4{a.x + hh * (b.x + v.x), a.y + hh * (b.y + v.y), a.z + hh * (b.z + v.z), a.w + hh * (b.w + v.w)};
+    }
+    if (c.stage == FD_ODE_HEUN_PREDICT) {
+        *reinterpret_cast<float4*>(x0) = x;
+        *reinterpret_cast<float4*>(v0) = v;
+    }
+    return float4{x.x + c.h * v.x, x.y + c.h * v.y, x.z + c.h * v.z, x.w + c.h * v.w};
+}
 
 struct fd_mega_params {
     // shapes
@@ -55,4 +102,7 @@ struct fd_mega_params {
     const float* temb_table;             // (nsteps, D) time embedding of every step's t (sampler mode: t is shared by all
                                          // series, fd_mega_temb_table fills it before the launch) or null
     unsigned long long seed, offset, ctr_per_step, n_elem;
+    // probability-flow ODE (FD_MEGA_ODE): `steps` then holds fd_ode_step_coef rows; Heun state (B,T,C), null for Euler
+    float* ode_x0;
+    float* ode_v0;
 };

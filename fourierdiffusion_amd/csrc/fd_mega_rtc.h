@@ -17,6 +17,7 @@
 struct fd_mega_rtc_key {
     int ks1, dt, kso, mt;                        // tile class of the model (fd_bf16_images) and token tiles per wave
     int T, D, C, H, S, NPG, rot, L, F, ffn32;    // ShapeStatic<...> arguments
+    int ode;                                     // 1: the probability-flow ODE instantiation (k_mega's ODE argument)
 };
 
 int fd_mega_rtc_mode();

@@ -3,6 +3,7 @@
 // The reference syncs the device every step (`timesteps[0].item()`, sampler.py:37) and draws the prior on
 // the CPU (sde.py:85); here the whole loop is enqueued on one stream with per-step coefficients computed on
 // the host up front, and the noise comes from the on-device Philox stream unless injected.
+#include "fd_ode.h"
 #include "fd_philox.h"
 #include "fd_score.h"
 #include "fd_sde.h"
@@ -86,6 +87,54 @@ extern "C" int fd_sampler_run(fd_score* m, const fd_sde_params* sde, const float
         if (int rc = fd_sde_step(ctx, sde, G, x, score, z, seed, offset + (uint64_t)i * per_step,
                                  (double)timesteps[i], dt, x, B, T, C, stream))
             return rc;
+    }
+    return FD_OK;
+}
+
+// Probability-flow ODE loop (fd_ode.hip; not in the reference): Euler (n_steps evaluations) or Heun (2 n_steps) over the grid
+// timesteps[0 .. n_steps], in place on x, in the dispatch order of fd_sampler_run.  Step by step: one score launch and one stage
+// launch per evaluation, the Heun state in two (B,T,C) workspace buffers behind the score.
+extern "C" int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                  int solver, float* x, int B, int mode, void* stream) {
+    if (!m) return FD_ERR_ARG;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, sde && G && timesteps && x, "fd_sampler_run_ode: null pointer");
+    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_sampler_run_ode: unknown SDE kind %d", sde->kind);
+    FD_REQUIRE(ctx, n_steps > 0 && B > 0, "fd_sampler_run_ode: n_steps=%d B=%d", n_steps, B);
+    FD_REQUIRE(ctx, solver == 0 || solver == 1, "fd_sampler_run_ode: solver %d (0 Euler, 1 Heun)", solver);
+    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_sampler_run_ode: unknown mode %d", mode);
+    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_sampler_run_ode: call fd_score_prepare first");
+    std::vector<fd_ode_step_coef> rows;
+    if (int rc = fd_ode_table(ctx, sde, timesteps, n_steps, solver, &rows)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const bool fused = mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && !getenv("FDIFF_SAMPLER_STEPWISE");
+    if (fused) {
+        const int rc = fd_sampler_run_ode_mega(m, rows, G, x, B, s);
+        if (rc != FD_ERR_UNSUPPORTED) return rc;
+    }
+    if (fused) {
+        const int rc = fd_sampler_run_ode_layers(m, rows, G, x, B, s);
+        if (rc != FD_ERR_UNSUPPORTED) return rc;
+    }
+
+    const int T = m->d.max_len, C = m->d.n_channels;
+    const int n_eval = (int)rows.size();
+    const size_t n = (size_t)B * T * C;
+    const size_t fwd = (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
+    const size_t buf = fd_ws::padded(n * sizeof(float));
+    std::vector<float> t_eval(n_eval);
+    for (int k = 0; k < n_eval; ++k) t_eval[k] = rows[k].t;
+    float* tvec0 = nullptr;
+    size_t tstride = 0;
+    if (int rc = step_table(ctx, fwd, (solver ? 3 : 1) * buf, t_eval.data(), n_eval, B, s, &tvec0, &tstride)) return rc;
+    float* score = (float*)((char*)ctx->ws + fwd);
+    float* x0 = solver ? (float*)((char*)ctx->ws + fwd + buf) : nullptr;
+    float* v0 = solver ? (float*)((char*)ctx->ws + fwd + 2 * buf) : nullptr;
+    for (int k = 0; k < n_eval; ++k) {
+        float* tvec = tvec0 + (size_t)k * tstride;
+        if (!tstride) hipLaunchKernelGGL(k_fill, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, t_eval[k]);
+        if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
+        if (int rc = fd_ode_stage(ctx, G, x, score, x0, v0, rows[k], B, T, C, s)) return rc;
     }
     return FD_OK;
 }

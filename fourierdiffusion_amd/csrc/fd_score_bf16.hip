@@ -22,6 +22,7 @@
 #include "fd_gemm_f32.h"
 #include "fd_bf16_images.h"
 #include "fd_mega.h"
+#include "fd_ode.h"
 #include "fd_philox.h"
 #include "fd_score.h"
 #include "fd_sde.h"
@@ -1388,8 +1389,13 @@ struct StepFuseArgs {
     fd_sde_step_coef cf;
     unsigned long long seed, ctr0;
     int M, T, C, D, KSE, CT;
+    // probability-flow ODE form (ODE = true): the evaluation's row and the Heun state (B,T,C) (null for Euler)
+    fd_ode_step_coef oc;
+    float* x0;
+    float* v0;
 };
-template <int KS1, int DT>
+// ODE: the epilogue runs the probability-flow ODE stage of fd_ode.hip instead of the Euler-Maruyama step (no noise)
+template <int KS1, int DT, bool ODE = false>
 __global__ __launch_bounds__(256) void k_unembed_step_embed(const StepFuseArgs A) {
     constexpr int XS = 41;                                  // floats per token row of the x stash (C <= 40; odd: conflict-free columns)
     __shared__ float xs_all[4][16 * XS];
@@ -1424,7 +1430,7 @@ __global__ __launch_bounds__(256) void k_unembed_step_embed(const StepFuseArgs A
             hf[ks] = __builtin_bit_cast(bf16x8, pk);
         }
         const float Gk = A.G[t];
-        const float gk = A.cf.g * Gk;
+        const float gk = (ODE ? A.oc.g : A.cf.g) * Gk;
         for (int ct = 0; ct < A.CT; ++ct) {
             f32x4 sc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1433,7 +1439,23 @@ __global__ __launch_bounds__(256) void k_unembed_step_embed(const StepFuseArgs A
             if (c0 < C) {
                 const size_t e0 = (size_t)mc * C + c0;
                 float o[4] = {0.f, 0.f, 0.f, 0.f};
-                if ((C & 3) == 0) {
+                if constexpr (ODE) {
+                    // (only valid rows: a padding lane shares row M-1 with a valid one and must not touch its Heun state)
+                    if (valid && (C & 3) == 0) {
+                        const float4 xv = *reinterpret_cast<const float4*>(A.x + e0);
+                        const float4 r = fd_ode_stage4(xv, sc[0], sc[1], sc[2], sc[3], gk, A.oc, A.x0 + e0, A.v0 + e0);
+                        *reinterpret_cast<float4*>(A.x + e0) = r;
+                        o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
+                    } else if (valid) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (c0 + r < C) {
+                                o[r] = fd_ode_stage1(A.x[e0 + r], sc[r], gk, A.oc, A.x0 + e0 + r, A.v0 + e0 + r);
+                                A.x[e0 + r] = o[r];
+                            }
+                        }
+                    }
+                } else if ((C & 3) == 0) {
                     const float4 xv = *reinterpret_cast<const float4*>(A.x + e0);
                     float z[4];
                     if (A.z) {
@@ -1528,6 +1550,15 @@ __global__ __launch_bounds__(256) void k_unembed_step_embed(const StepFuseArgs A
     }
 }
 
+template <bool ODE>
+static void launch_step_fuse(const fd_bf16_images* im, const StepFuseArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.M + 63) / 64)), block(256);
+    if (im->ks1 == 3 && im->dt == 5) hipLaunchKernelGGL((k_unembed_step_embed<3, 5, ODE>), grid, block, 0, s, a);
+    else if (im->ks1 == 2 && im->dt == 4) hipLaunchKernelGGL((k_unembed_step_embed<2, 4, ODE>), grid, block, 0, s, a);
+    else if (im->ks1 == 1 && im->dt == 2) hipLaunchKernelGGL((k_unembed_step_embed<1, 2, ODE>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_unembed_step_embed<1, 1, ODE>), grid, block, 0, s, a);
+}
+
 // fd_sampler_run's loop for the persistent kernel's model family when the persistent kernel itself does not fit (T > 256):
 // per diffusion step the 2 L layer launches + ONE launch for unembed / reverse-SDE step / next embedding.  Returns
 // FD_ERR_UNSUPPORTED (x untouched) when this model has no such path.
@@ -1570,13 +1601,7 @@ int fd_sampler_run_layers(fd_score* m, const fd_sde_params* sde, const float* G,
     A.img_unemb = im->mimg + im->off_unemb; A.img_emb = im->mimg + im->off_emb;
     A.seed = seed; A.M = M; A.T = T; A.C = C; A.D = D; A.KSE = im->kse; A.CT = im->ct;
     const unsigned long long per_step = (unsigned long long)((n + 3) / 4);
-    auto launch = [&](const StepFuseArgs& a) {
-        const dim3 grid((unsigned)((M + 63) / 64)), block(256);
-        if (k35) hipLaunchKernelGGL((k_unembed_step_embed<3, 5>), grid, block, 0, s, a);
-        else if (k24) hipLaunchKernelGGL((k_unembed_step_embed<2, 4>), grid, block, 0, s, a);
-        else if (k12) hipLaunchKernelGGL((k_unembed_step_embed<1, 2>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_unembed_step_embed<1, 1>), grid, block, 0, s, a);
-    };
+    auto launch = [&](const StepFuseArgs& a) { launch_step_fuse<false>(im, a, s); };
     // first step's embedding
     static const bool xrows_on = !(getenv("FDIFF_ATT_XROWS") && atoi(getenv("FDIFF_ATT_XROWS")) == 0);
     const bool rows0 = xrows_on && lb.xrb && m->d.num_layers > 0 && m->d.d_model / m->d.n_head <= 7 && (im->ks1 == 3 || im->ks1 == 2) &&
@@ -1726,6 +1751,106 @@ int fd_sampler_run_mega(fd_score* m, const fd_sde_params* sde, const float* G, c
         }
         return fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
     }
+}
+
+// Probability-flow ODE loops of fd_sampler_run_ode (fd_ode.hip) in the two fused forms above: the device table holds one
+// fd_ode_step_coef per score evaluation (t where the SDE rows keep it: the time-embedding table is built from it unchanged), the
+// Heun state lives in two (B,T,C) workspace buffers behind it.  FD_ERR_UNSUPPORTED (x untouched) exactly where the SDE forms return it.
+static int ode_tables(fd_ctx* ctx, const fd_score* m, const std::vector<fd_ode_step_coef>& rows, size_t base, size_t n, hipStream_t s,
+                      fd_ode_step_coef** tabd, float** temb, float** x0, float** v0) {
+    const size_t ne = rows.size();
+    const size_t tab_bytes = fd_ws::padded(sizeof(fd_ode_step_coef) * ne);
+    const size_t temb_bytes = fd_ws::padded(sizeof(float) * ne * m->d.d_model);
+    const size_t buf = fd_ws::padded(n * sizeof(float));
+    const bool heun = rows[0].stage != FD_ODE_EULER;
+    if (int rc = fd_ws_reserve(ctx, base + tab_bytes + temb_bytes + (heun ? 2 * buf : 0))) return rc;
+    char* p = (char*)ctx->ws + base;
+    *tabd = reinterpret_cast<fd_ode_step_coef*>(p);
+    *temb = reinterpret_cast<float*>(p + tab_bytes);
+    *x0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes) : nullptr;
+    *v0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes + buf) : nullptr;
+    // pageable source: the runtime stages the copy before returning
+    FD_HIP(ctx, hipMemcpyAsync(*tabd, rows.data(), sizeof(fd_ode_step_coef) * ne, hipMemcpyHostToDevice, s));
+    fd_mega_params MP;
+    memset(&MP, 0, sizeof MP);
+    MP.params = m->params; MP.tW = m->tW; MP.td_w = m->td_w; MP.td_b = m->td_b; MP.D = m->d.d_model;
+    MP.steps = reinterpret_cast<const fd_sde_step_coef*>(*tabd); MP.nsteps = (int)ne;
+    fd_mega_temb_table(MP, *temb, s);
+    return FD_OK;
+}
+
+int fd_sampler_run_ode_mega(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    const MegaPlan pl = plan_mega(m, B);
+    if (!pl.ok || getenv("FDIFF_NO_MEGA")) return FD_ERR_UNSUPPORTED;
+    if (int rc = fd_bf16_refresh(m, s)) return rc;
+    const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
+    fd_ode_step_coef* tabd;
+    float *temb, *x0, *v0;
+    if (int rc = ode_tables(ctx, m, rows, 0, n, s, &tabd, &temb, &x0, &v0)) return rc;
+    fd_mega_params MP;
+    if (int rc = fill_mega_params(m, pl, B, MP)) return rc;
+    MP.mode = FD_MEGA_ODE;
+    MP.nsteps = (int)rows.size();
+    MP.x = x;
+    MP.G = G;
+    MP.steps = reinterpret_cast<const fd_sde_step_coef*>(tabd);
+    MP.temb_table = temb;
+    MP.ode_x0 = x0;
+    MP.ode_v0 = v0;
+    MP.n_elem = n;
+    const double T = m->d.max_len, D = m->d.d_model, F = m->d.dim_ff, C = m->d.n_channels, L = m->d.num_layers;
+    const double per_fwd = T * (L * (2 * D * 3 * D + 2 * D * D + 4 * D * F + 4 * T * D) + 4 * C * D) + 2 * D * D;
+    fd_prof_scope scope(ctx, s, "k_mega (persistent score-net + probability-flow ODE loop)", per_fwd * B * (double)rows.size());
+    if (ctx->prof_on) {
+        if (!ctx->prof_clk) FD_HIP(ctx, hipMalloc((void**)&ctx->prof_clk, 4 * sizeof(unsigned long long)));
+        FD_HIP(ctx, hipMemsetAsync(ctx->prof_clk, 0, 4 * sizeof(unsigned long long), s));
+        MP.clk_out = ctx->prof_clk;
+    }
+    return fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
+}
+
+int fd_sampler_run_ode_layers(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    const fd_bf16_images* im = m->bf16;
+    if (!im || !im->supported || !im->mega || getenv("FDIFF_SAMPLER_UNFUSED_STEP")) return FD_ERR_UNSUPPORTED;
+    const bool k35 = im->ks1 == 3 && im->dt == 5, k24 = im->ks1 == 2 && im->dt == 4, k12 = im->ks1 == 1 && im->dt == 2,
+               k11 = im->ks1 == 1 && im->dt == 1;
+    if (!(k35 || k24 || k12 || k11) || m->d.n_channels > 40 || m->d.d_model % 4 != 0) return FD_ERR_UNSUPPORTED;
+    if (int rc = fd_bf16_refresh(m, s)) return rc;
+    const int T = m->d.max_len, C = m->d.n_channels, D = m->d.d_model;
+    const int M = B * T;
+    const int ne = (int)rows.size();
+    const size_t fwd = fd_score_f32_workspace(m, B, false);
+    fd_ode_step_coef* tabd;
+    float *temb, *x0, *v0;
+    if (int rc = ode_tables(ctx, m, rows, fwd, (size_t)M * C, s, &tabd, &temb, &x0, &v0)) return rc;
+    fd_ws ws(ctx);
+    LayerBufs lb = carve_layer_bufs(m, B, ws);
+    StepFuseArgs A{};
+    A.x = x; A.G = G; A.pos = m->params + m->pos;
+    A.img_unemb = im->mimg + im->off_unemb; A.img_emb = im->mimg + im->off_emb;
+    A.M = M; A.T = T; A.C = C; A.D = D; A.KSE = im->kse; A.CT = im->ct;
+    A.x0 = x0; A.v0 = v0;
+    static const bool xrows_on = !(getenv("FDIFF_ATT_XROWS") && atoi(getenv("FDIFF_ATT_XROWS")) == 0);
+    const bool rows0 = xrows_on && lb.xrb && m->d.num_layers > 0 && m->d.d_model / m->d.n_head <= 7 && (im->ks1 == 3 || im->ks1 == 2) &&
+                       im->kso == 3;      // (as fd_sampler_run_layers)
+    A.h = nullptr; A.hn = lb.h0; A.hn_rows = rows0 ? lb.xrb : nullptr; A.temb = temb;
+    launch_step_fuse<true>(im, A, s);      // first evaluation's embedding
+    lb.xrb_ok = rows0;
+    for (int k = 0; k < ne; ++k) {
+        if (int rc = bf16_layer_stack(m, B, lb, s)) return rc;
+        A.h = lb.h0;
+        A.hn = (k + 1 < ne) ? lb.h1 : nullptr;
+        A.hn_rows = (rows0 && k + 1 < ne) ? lb.xrb : nullptr;
+        A.temb = temb + (size_t)(k + 1 < ne ? k + 1 : k) * D;
+        A.oc = rows[k];
+        launch_step_fuse<true>(im, A, s);
+        lb.xrb_ok = rows0 && k + 1 < ne;
+        std::swap(lb.h0, lb.h1);
+    }
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
 }
 
 // Which kernel path serves a batch of B series in `mode` (no launch, no device work).  The parity tests use it to assert

@@ -18,6 +18,11 @@ Conditional sampling (an extension, not in the reference): ``impute`` fills in t
 (imputation, forecasting) by projecting the state onto the observations after every reverse step (Song et al. 2021, Sec. 5,
 App. I.2), the step and the projection fused in one engine launch (fd_sampler_run_impute); ``impute_project`` is the
 projection alone.
+
+Probability-flow ODE (an extension, not in the reference): ``sample_ode`` integrates the deterministic ODE with the reverse SDE's
+marginals (Song et al. 2021, Sec. 4.3) by Euler or Heun, the whole loop one engine call (fd_sampler_run_ode); ``encode`` /
+``decode`` run it data -> latents and back.  ``ODESampler`` is a DiffusionSampler whose ``sample`` is ``sample_ode``
+(hydra: ``sampler=ode``).
 """
 from __future__ import annotations
 
@@ -107,6 +112,75 @@ class DiffusionSampler:
             _C.check(rc, ctx)
             all_samples.append(X)
         return torch.cat([x.cpu() for x in all_samples], dim=0)
+
+    # ------------------------------------------------------------ probability-flow ODE (extension, not in the reference)
+    _SOLVERS = {"euler": 0, "heun": 1}
+
+    def sample_ode(self, num_samples: int, num_diffusion_steps: Optional[int] = None, solver: str = "heun",
+                   prior_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+        """Samples by the probability-flow ODE from t = 1 to t = eps on ``linspace(1, eps, N + 1)`` (N steps: N score evaluations
+        for Euler, 2N for Heun).  Batching, launch merging and the prior as ``sample``; prior_noise[b] (bs,T,C) injects the prior
+        draws of batch b.  Returns a CPU tensor (n, max_len, n_channels) in sample space."""
+        model = self.score_model
+        N = model.num_training_steps if num_diffusion_steps is None else int(num_diffusion_steps)
+        mode = _PRECISIONS[model.precision_effective]
+        num_batches = max(1, num_samples // self.sample_batch_size)
+        sizes = [min(num_samples - b * self.sample_batch_size, self.sample_batch_size) for b in range(num_batches)]
+        if self.merge_batches and num_batches > 1 and prior_noise is None:
+            sizes = self._launch_sizes(sum(sizes), mode)
+        grid = self._ode_grid(N, to_noise=False)
+        out: List[torch.Tensor] = []
+        for b, bs in enumerate(sizes):
+            X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
+            out.append(self._run_ode(X, grid, solver))
+        return torch.cat([x.cpu() for x in out], dim=0)
+
+    def encode(self, X: torch.Tensor, num_diffusion_steps: int, solver: str = "heun") -> torch.Tensor:
+        """Latents of X (n, max_len, n_channels) in sample space: the probability-flow ODE from t = eps to t = 1.  Deterministic;
+        ``decode`` inverts it up to the discretisation error.  Launches of at most ``sample_batch_size`` series; returns a CPU
+        tensor."""
+        return self._map_ode(X, self._ode_grid(int(num_diffusion_steps), to_noise=True), solver, "X")
+
+    def decode(self, latents: torch.Tensor, num_diffusion_steps: int, solver: str = "heun") -> torch.Tensor:
+        """Series in sample space from latents at t = 1: the probability-flow ODE from t = 1 to t = eps (``sample_ode`` from given
+        latents).  Returns a CPU tensor."""
+        return self._map_ode(latents, self._ode_grid(int(num_diffusion_steps), to_noise=False), solver, "latents")
+
+    def _ode_grid(self, N: int, to_noise: bool):
+        if N < 1:
+            raise ValueError(f"num_diffusion_steps must be >= 1, got {N}")
+        sch = self.noise_scheduler
+        if sch.G is None:
+            raise RuntimeError("the noise scheduler has no noise scaling yet (set_noise_scaling)")
+        ts = torch.linspace(sch.eps, 1.0, N + 1) if to_noise else torch.linspace(1.0, sch.eps, N + 1)
+        return (C.c_float * (N + 1))(*ts.to(torch.float32).tolist()), N
+
+    def _map_ode(self, X: torch.Tensor, grid, solver: str, name: str) -> torch.Tensor:
+        if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (self.max_len, self.n_channels):
+            raise ValueError(f"{name} must be a tensor of shape (n, {self.max_len}, {self.n_channels}), got "
+                             f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
+        dev = self.score_model.device
+        out: List[torch.Tensor] = []
+        for lo in range(0, X.shape[0], self.sample_batch_size):
+            xb = X[lo:lo + self.sample_batch_size].to(device=dev, dtype=torch.float32).contiguous().clone()
+            out.append(self._run_ode(xb, grid, solver))
+        return torch.cat([x.cpu() for x in out], dim=0)
+
+    def _run_ode(self, X: torch.Tensor, grid, solver: str) -> torch.Tensor:
+        """X (bs,T,C) device float32, integrated in place over ``grid`` (ctypes float[N+1], N)."""
+        if solver not in self._SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}")
+        model = self.score_model
+        model.eval()
+        sch = self.noise_scheduler
+        ctx, h = model._engine()
+        ts_arr, N = grid
+        p = sch._c_params()
+        mode = _PRECISIONS[model.precision_effective]
+        rc = _C.lib().fd_sampler_run_ode(h, C.byref(p), sch.G_on(X.device).data_ptr(), ts_arr, N, self._SOLVERS[solver], X.data_ptr(),
+                                         X.shape[0], mode, _C.stream_of(X))
+        _C.check(rc, ctx)
+        return X
 
     # ------------------------------------------------------------ conditional sampling (extension, not in the reference)
     def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,
@@ -278,3 +352,18 @@ class DiffusionSampler:
             return self.noise_scheduler.prior_sampling((batch_size, self.max_len, self.n_channels), noise=noise,
                                                        device=self.score_model.device)
         raise NotImplementedError("Scheduler not recognized.")
+
+
+class ODESampler(DiffusionSampler):
+    """A DiffusionSampler whose ``sample`` integrates the probability-flow ODE (``sample_ode``) with the constructor's ``solver``
+    ("heun" or "euler"): ``python cmd/sample.py sampler=ode num_diffusion_steps=50``."""
+
+    def __init__(self, score_model: ScoreModule, sample_batch_size: int, solver: str = "heun", merge_batches: bool = True) -> None:
+        super().__init__(score_model=score_model, sample_batch_size=sample_batch_size, merge_batches=merge_batches)
+        if solver not in self._SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}")
+        self.solver = solver
+
+    def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None,
+               prior_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+        return self.sample_ode(num_samples, num_diffusion_steps, solver=self.solver, prior_noise=prior_noise)

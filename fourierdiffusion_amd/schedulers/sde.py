@@ -181,6 +181,26 @@ class SDE(abc.ABC):
         return SamplingOutput(prev_sample=out)
 
 
+    # ------------------------------------------------------------ probability-flow ODE (extension, not in the reference)
+    def ode_drift(self, model_output: torch.Tensor, timestep: float, sample: torch.Tensor) -> torch.Tensor:
+        """Velocity of the probability-flow ODE (Song et al. 2021, Sec. 4.3), v = -a x - 0.5 (g G)^2 score: the drift of ``step``
+        with the score term halved and no noise.  The step-wise twin of ``DiffusionSampler.sample_ode``; returns a new device
+        tensor."""
+        assert self.G is not None
+        xd = _C.dev_f32(sample, "sample")
+        sd = _C.dev_f32(model_output.to(xd.device), "model_output")
+        if sd.shape != xd.shape or xd.dim() != 3:
+            raise ValueError(f"ode_drift: sample {tuple(xd.shape)} and model_output {tuple(sd.shape)} must be the same (B,T,C) shape")
+        B, T, Cn = xd.shape
+        out = torch.empty_like(xd)
+        h = _C.ctx(xd.device)
+        p = self._c_params()
+        rc = _C.lib().fd_pf_ode_drift(h, C.byref(p), self.G_on(xd.device).data_ptr(), xd.data_ptr(), sd.data_ptr(), float(timestep),
+                                      out.data_ptr(), B, T, Cn, _C.stream_of(xd))
+        _C.check(rc, h)
+        return out
+
+
 class VEScheduler(SDE):
     """Variance-exploding SDE: std(t) = sigma_min (sigma_max/sigma_min)^t * G (sde.py:90-165)."""
 

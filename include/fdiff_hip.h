@@ -324,6 +324,25 @@ int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G,
                           int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B,
                           int mode, void* stream);
 
+/* Probability-flow ODE extension (NOT in the reference, whose only sampler is Euler-Maruyama over the reverse SDE; Song et al. 2021,
+ * Sec. 4.3): the deterministic ODE with the reverse SDE's marginals.  With a = a_x(t), g = g(t) of the SDE (VP: a = beta/2,
+ * g = sqrt(beta); VE: a = 0, g = sigma_min sqrt(2 ln(sigma_max/sigma_min)) (sigma_max/sigma_min)^t) and s the score:
+ *   v(x, t) = -a x - 0.5 (g G_k)^2 s(x, t)          (fd_sde_step's drift with the score term halved)
+ * On a strictly monotone grid t_0 .. t_N, h_i = t_{i+1} - t_i (h < 0: noise -> data, sampling / decoding; h > 0: data -> noise,
+ * encoding):
+ *   Euler (solver 0): x_{i+1} = x_i + h_i v(x_i, t_i)                                               N score evaluations
+ *   Heun  (solver 1): x~ = x_i + h_i v_i, v_i = v(x_i, t_i);  x_{i+1} = x_i + h_i/2 (v_i + v(x~, t_{i+1}))    2N evaluations
+ * (the last step is corrected too).  No random numbers are drawn.
+ *   fd_pf_ode_drift   : v_out = v(x, t) for the given score (out may alias x or score).  The step-wise building block.
+ *   fd_sampler_run_ode: the whole Euler / Heun loop in place on x (B,T,C).  timesteps: HOST float[n_steps + 1], strictly monotone
+ *                       and finite (FD_ERR_ARG otherwise).  Same dispatch as fd_sampler_run (bf16 transformer: the persistent
+ *                       kernel, then the long-series fused launch, then per-op launches; FDIFF_SAMPLER_STEPWISE and
+ *                       FDIFF_SAMPLER_UNFUSED_STEP select the later forms); no host synchronisation inside the loop. */
+int fd_pf_ode_drift(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const float* x, const float* score, double t,
+                    float* v_out, int B, int T, int C, void* stream);
+int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
+                       float* x, int B, int mode, void* stream);
+
 /* ------------------------------------------------------------ a11 optimiser
  * torch.optim.AdamW defaults + diffusers cosine-warmup + Lightning global-norm clip
  * (score_models.py:122-130, cmd/conf/trainer/default.yaml:4), fused over the flat buffer.
