@@ -86,6 +86,7 @@ _PROTOS = {
     "fd_score_set_train_mode": (C.c_int, [_vp, C.c_int]),
     "fd_score_forward_train": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _vp]),
     "fd_score_backward": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "fd_score_input_vjp": (C.c_int, [_vp, _vp, _vp, _vp]),
     "fd_score_train_plan": (C.c_int, [_vp, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     "fd_score_train_dsm_supported": (C.c_int, [_vp, C.c_int]),
     "fd_score_train_dsm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
@@ -102,6 +103,8 @@ _PROTOS = {
                                         C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
     "fd_pf_ode_drift": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "fd_prior_logp": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_likelihood_run": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "fd_grad_sqnorm": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "fd_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_float, C.c_int64,

@@ -302,7 +302,9 @@ int fd_bb_forward(fd_score* m, const float* x, const float* t, float* out, int B
     return FD_OK;
 }
 
-int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s) {
+// dx_only != null: the input-only mode of fd_score_input_vjp -- the same chain down to d h, then d x = d h W_emb into dx_only; no
+// parameter gradient is formed and `grads` is not touched
+int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s, float* dx_only) {
     fd_ctx* ctx = m->ctx;
     const int B = m->saved_B;
     const int T = m->d.max_len, C = m->d.n_channels, D = m->d.d_model, L = m->d.num_layers;
@@ -315,14 +317,17 @@ int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate,
     bb_carve(m, B, true, (char*)ctx->ws, &b);
     size_t gsk_n = 0;
     float* gsk = fd_gemm_scratch(ctx, &gsk_n);
-    if (!accumulate) FD_HIP(ctx, hipMemsetAsync(grads, 0, sizeof(float) * (size_t)m->nparams, s));
+    const bool wg = dx_only == nullptr;
+    if (wg && !accumulate) FD_HIP(ctx, hipMemsetAsync(grads, 0, sizeof(float) * (size_t)m->nparams, s));
     const size_t R = mlp ? (size_t)B : (size_t)B * T;
     const int Ri = (int)R;
     const int Cout = mlp ? T * C : C;
     const float inv_keep = (p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
     // ---- unembedder
-    fdgemm::linear_bwd_weight(dout, b.hL, grads + m->un_w, Ri, Cout, D, true, s, b.skp, kSkp);
-    if (int rc = fd_colsum_det(ctx, dout, grads + m->un_b, Ri, Cout, s)) return rc;
+    if (wg) {
+        fdgemm::linear_bwd_weight(dout, b.hL, grads + m->un_w, Ri, Cout, D, true, s, b.skp, kSkp);
+        if (int rc = fd_colsum_det(ctx, dout, grads + m->un_b, Ri, Cout, s)) return rc;
+    }
     fdgemm::linear_bwd_input(dout, P + m->un_w, b.dh, Ri, Cout, D, false, s, gsk, gsk_n);
     for (int i = L - 1; i >= 0; --i) {
         const fd_bb_off& o = m->bb[i];
@@ -331,12 +336,16 @@ int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate,
             // h_out = h + drop1(f), f = act W2^T + b2, act = drop0(relu(h W1^T + b1))
             hipLaunchKernelGGL(k_drop_copy, dim3(ew_grid(ctx, (R * D + 3) / 4)), dim3(256), 0, s, b.dh, b.dtmp, R * D, p, m->saved_seed,
                                fd_dropout_site_offset(m->saved_offset, i, 1));
-            if (int rc = fd_colsum_det(ctx, b.dtmp, grads + o.d, Ri, D, s)) return rc;
-            fdgemm::linear_bwd_weight(b.dtmp, b.act[i], grads + o.c, Ri, D, F, true, s, b.skp, kSkp);
+            if (wg) {
+                if (int rc = fd_colsum_det(ctx, b.dtmp, grads + o.d, Ri, D, s)) return rc;
+                fdgemm::linear_bwd_weight(b.dtmp, b.act[i], grads + o.c, Ri, D, F, true, s, b.skp, kSkp);
+            }
             fdgemm::linear_bwd_input(b.dtmp, P + o.c, b.dact, Ri, D, F, false, s);
             hipLaunchKernelGGL(k_relu_drop_bwd, dim3(ew_grid(ctx, R * F)), dim3(256), 0, s, b.dact, b.act[i], R * F, inv_keep);
-            if (int rc = fd_colsum_det(ctx, b.dact, grads + o.b, Ri, F, s)) return rc;
-            fdgemm::linear_bwd_weight(b.dact, b.h[i], grads + o.a, Ri, F, D, true, s, b.skp, kSkp);
+            if (wg) {
+                if (int rc = fd_colsum_det(ctx, b.dact, grads + o.b, Ri, F, s)) return rc;
+                fdgemm::linear_bwd_weight(b.dact, b.h[i], grads + o.a, Ri, F, D, true, s, b.skp, kSkp);
+            }
             fdgemm::linear_bwd_input(b.dact, P + o.a, b.dh, Ri, F, D, true, s, gsk, gsk_n);       // + residual path already in dh
         } else {
             const int G = 4 * D;
@@ -353,16 +362,23 @@ int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate,
                 hipLaunchKernelGGL((k_lstm_bwd_rec<128>), dim3(B), dim3(4 * 128), lds, s, b.dh, b.act[i], b.aux[i], P + o.b, b.dact, T, D);
             }
             // b_ih and b_hh enter the pre-activations identically
-            if (int rc = fd_colsum_det(ctx, b.dact, grads + o.c, Ri, G, s)) return rc;
-            if (int rc = fd_colsum_det(ctx, b.dact, grads + o.d, Ri, G, s)) return rc;
-            fdgemm::linear_bwd_weight(b.dact, b.h[i], grads + o.a, Ri, G, D, true, s, b.skp, kSkp);
-            hipLaunchKernelGGL(k_shift_time, dim3(ew_grid(ctx, R * D)), dim3(256), 0, s, b.hs[i], b.hprev, B, T, D);
-            fdgemm::linear_bwd_weight(b.dact, b.hprev, grads + o.b, Ri, G, D, true, s, b.skp, kSkp);
+            if (wg) {
+                if (int rc = fd_colsum_det(ctx, b.dact, grads + o.c, Ri, G, s)) return rc;
+                if (int rc = fd_colsum_det(ctx, b.dact, grads + o.d, Ri, G, s)) return rc;
+                fdgemm::linear_bwd_weight(b.dact, b.h[i], grads + o.a, Ri, G, D, true, s, b.skp, kSkp);
+                hipLaunchKernelGGL(k_shift_time, dim3(ew_grid(ctx, R * D)), dim3(256), 0, s, b.hs[i], b.hprev, B, T, D);
+                fdgemm::linear_bwd_weight(b.dact, b.hprev, grads + o.b, Ri, G, D, true, s, b.skp, kSkp);
+            }
             fdgemm::linear_bwd_input(b.dact, P + o.a, b.dh, Ri, G, D, true, s);                    // + residual path already in dh
         }
     }
     // ---- embedder + time embedding (no positional table in these backbones)
     const int Cin = mlp ? T * C : C;
+    if (!wg) {      // d x = d h W_emb (the MLP embedder acts on the flattened (B, T*C) series)
+        fdgemm::linear_bwd_input(b.dh, P + m->emb_w, dx_only, Ri, D, Cin, false, s, gsk, gsk_n);
+        FD_LAUNCH_CHECK(ctx);
+        return FD_OK;
+    }
     fdgemm::linear_bwd_weight(b.dh, m->saved_x, grads + m->emb_w, Ri, D, Cin, true, s, b.skp, kSkp);
     if (int rc = fd_colsum_det(ctx, b.dh, grads + m->emb_b, Ri, D, s)) return rc;
     const float* dtemb = b.dh;

@@ -83,6 +83,10 @@ struct fd_ctx {
     std::vector<prof_kernel> prof_kernels;
     struct prof_event { int kernel; hipEvent_t a, b; };
     std::vector<prof_event> prof_events;
+    // stage state of fd_likelihood_run (fd_likelihood.hip): outside the arena, which the training forward and its VJP own between
+    // them; grow-only
+    void* ll_buf = nullptr;
+    size_t ll_bytes = 0;
 };
 
 float* fd_gemm_scratch(fd_ctx* ctx, size_t* n_floats);   // fd_ctx.hip

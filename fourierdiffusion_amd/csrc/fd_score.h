@@ -87,7 +87,7 @@ int fd_score_forward_bf16(fd_score* m, const float* x, const float* t, float* ou
 // fd_backbones.hip: the reference's other two score backbones (MLPScoreModule / LSTMScoreModule), exact-f32
 int fd_bb_forward(fd_score* m, const float* x, const float* t, float* out, int B, hipStream_t s, bool train, float p,
                   uint64_t seed, uint64_t offset);
-int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s);
+int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s, float* dx_only = nullptr);
 size_t fd_bb_workspace(const fd_score* m, int B, bool train);
 // any backbone, eval mode (sampler loop, fd_score_forward)
 int fd_score_forward_any(fd_score* m, const float* x, const float* t, float* out, int B, int mode, hipStream_t s);
@@ -99,6 +99,8 @@ void fd_train_bf16_forward_plan(const fd_score* m, int B, char* out, size_t n); 
 int fd_score_forward_train_bf16(fd_score* m, const float* x, const float* t, float* out, int B, float p, uint64_t seed,
                                 uint64_t offset, hipStream_t s);
 int fd_score_backward_bf16(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s);
+// input-only backward of the bf16 path (fd_score_input_vjp): dx = (d s / d x)^T dout, no parameter gradient, no side stream
+int fd_score_input_vjp_bf16(fd_score* m, const float* dout, float* dx, hipStream_t s);
 int fd_score_train_dsm_bf16(fd_score* m, const float* x, const float* t, const float* target, const float* stdv, int lw,
                             float grad_weight, int B, float p, uint64_t seed, uint64_t offset, float* loss_out, float* grads,
                             int accumulate, hipStream_t s);

@@ -715,3 +715,92 @@ extern "C" int fd_score_backward(fd_score* m, const float* dout, float* grads, i
     FD_LAUNCH_CHECK(ctx);
     return fd_take_deferred(ctx);
 }
+
+// Input-only backward (fd_score_input_vjp): dx = (d s / d x)^T dout for the last training forward.  The layer loop of
+// fd_score_backward without any parameter gradient (no linear_bwd_weight, column sum, LayerNorm parameter sum or embedding-side
+// backward); it ends with d x = d h W_emb.  The MLP / LSTM backbones and the bf16 path have the same mode (fd_bb_backward,
+// fd_score_input_vjp_bf16).  `grads` is neither read nor written.
+extern "C" int fd_score_input_vjp(fd_score* m, const float* dout, float* dx, void* stream) {
+    if (!m) return FD_ERR_ARG;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, dout && dx, "fd_score_input_vjp: null pointer");
+    if (!m->have_saved) return fd_fail(ctx, FD_ERR_STATE, "fd_score_input_vjp: no training forward to differentiate");
+    hipStream_t s = (hipStream_t)stream;
+    if (ctx->ws_gen != m->saved_ws_gen || ctx->ws != m->saved_ws)
+        return fd_fail(ctx, FD_ERR_STATE, "fd_score_input_vjp: another engine call used the context workspace after "
+                       "fd_score_forward_train (the saved activations live there)");
+    if (m->backbone != FD_BACKBONE_TRANSFORMER) {
+        m->have_saved = false;
+        return fd_bb_backward(m, dout, nullptr, 0, s, dx);
+    }
+    if (m->saved_bf16) {
+        m->have_saved = false;
+        return fd_score_input_vjp_bf16(m, dout, dx, s);
+    }
+    const int B = m->saved_B;
+    const int T = m->d.max_len, C = m->d.n_channels, D = m->d.d_model, H = m->d.n_head, F = m->d.dim_ff;
+    const int L = m->d.num_layers, hd = D / H;
+    const int M = B * T;
+    const float p = m->saved_p;
+    const float* P = m->params;
+    const size_t fwd_bytes = fd_score_f32_workspace(m, B, true);
+    if (ctx->ws_bytes < fwd_bytes + fd_score_bwd_workspace(m, B))
+        return fd_fail(ctx, FD_ERR_STATE, "fd_score_input_vjp: workspace was resized since the training forward");
+    m->have_saved = false;
+    fd_ws ws(ctx, /*reader=*/true);
+    fd_saved sv;
+    fd_score_carve_saved(m, B, ws, sv);
+    ws.off = fwd_bytes;                       // (the carve of fd_score_backward; dtemb and the split-K block are not used)
+    float* dh = ws.take<float>((size_t)M * D);
+    float* ds = ws.take<float>((size_t)M * D);
+    float* tmp = ws.take<float>((size_t)M * D);
+    float* dact = ws.take<float>((size_t)M * F);
+    float* dqkv = ws.take<float>((size_t)M * 3 * D);
+    float* Dq = ws.take<float>((size_t)B * H * T);
+    size_t gsk_n = 0;
+    float* gsk = fd_gemm_scratch(ctx, &gsk_n);
+    const float inv_keep = (p > 0.f) ? 1.0f / (1.0f - p) : 1.0f;
+    // LayerNorm backward, input side only: k_ln_bwd's per-block parameter partials go to scratch and are never summed
+    auto ln_bwd_input = [&](const float* dy, const float* x, const float* mr, const float* gamma, float* dxo) -> int {
+        int tokens_per_block = (M + ctx->num_cu - 1) / ctx->num_cu;
+        tokens_per_block = std::min(64, std::max(8, (tokens_per_block + 3) & ~3));
+        const int nblk = (M + tokens_per_block - 1) / tokens_per_block;
+        float* part = fd_red_scratch(ctx, (size_t)nblk * 2 * D);
+        if (!part) return fd_fail(ctx, FD_ERR_HIP, "fd_score_input_vjp: reduction scratch allocation failed");
+        hipLaunchKernelGGL(k_ln_bwd, dim3(nblk), dim3(256), 8 * D * sizeof(float), s, dy, x, mr, gamma, dxo, part, M, D, tokens_per_block);
+        return FD_OK;
+    };
+    auto dropout_bwd = [&](const float* src, float* dst, int layer, int site) {
+        const size_t n = (size_t)M * D;
+        hipLaunchKernelGGL(k_dropout_copy, dim3(ew_grid(ctx, (n + 3) / 4)), dim3(256), 0, s, src, dst, n, p, m->saved_seed,
+                           fd_dropout_site_offset(m->saved_offset, layer, site));
+    };
+
+    fdgemm::linear_bwd_input(dout, P + m->un_w, dh, M, C, D, false, s);
+    for (int i = L - 1; i >= 0; --i) {
+        const fd_layer_off& lo = m->layers[i];
+        const fd_saved_layer& A = sv.layers[i];
+        if (int rc = ln_bwd_input(dh, A.s2, A.mr2, P + lo.n2_w, ds)) return rc;
+        dropout_bwd(ds, tmp, i, 3);
+        fdgemm::linear_bwd_input(tmp, P + lo.l2_w, dact, M, D, F, false, s);
+        hipLaunchKernelGGL(k_relu_drop_bwd, dim3(ew_grid(ctx, (size_t)M * F)), dim3(256), 0, s, dact, A.hact, (size_t)M * F,
+                           inv_keep);
+        fdgemm::linear_bwd_input(dact, P + lo.l1_w, ds, M, F, D, true, s, gsk, gsk_n);
+        if (int rc = ln_bwd_input(ds, A.s1, A.mr1, P + lo.n1_w, dh)) return rc;
+        dropout_bwd(dh, tmp, i, 1);
+        fdgemm::linear_bwd_input(tmp, P + lo.out_w, ds, M, D, D, false, s);
+        {
+            const size_t n = (size_t)B * H * T;
+            hipLaunchKernelGGL(k_attn_rowdot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ds, A.att, Dq, B, T, H, hd);
+            const uint64_t off0 = fd_dropout_site_offset(m->saved_offset, i, 0);
+            if (hd <= 8) attn_bwd_t<8>(A.qkv, ds, A.lse, Dq, dqkv, B, T, H, hd, p, m->saved_seed, off0, s);
+            else if (hd <= 16) attn_bwd_t<16>(A.qkv, ds, A.lse, Dq, dqkv, B, T, H, hd, p, m->saved_seed, off0, s);
+            else if (hd <= 32) attn_bwd_t<32>(A.qkv, ds, A.lse, Dq, dqkv, B, T, H, hd, p, m->saved_seed, off0, s);
+            else attn_bwd_t<64>(A.qkv, ds, A.lse, Dq, dqkv, B, T, H, hd, p, m->saved_seed, off0, s);
+        }
+        fdgemm::linear_bwd_input(dqkv, P + lo.in_w, dh, M, 3 * D, D, true, s);
+    }
+    fdgemm::linear_bwd_input(dh, P + m->emb_w, dx, M, D, C, false, s);      // h0 = x W_emb^T + ...: d x = d h W_emb
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
+}

@@ -2896,8 +2896,12 @@ int tr_forward_t(fd_score* m, const float* x, const float* t, float* out, int B,
     return FD_OK;
 }
 
+// dx_only != null: the input-only mode of fd_score_input_vjp.  The d x chain (k_tr_ffn_bwd, k_tr_attn_bwd, the first layer's d x)
+// runs as in training; none of the weight-gradient, reduce or embedding-gradient launches, no side stream, `grads` untouched;
+// it ends with d x = d h W_emb into dx_only.
 template <int KS1, int DT, int KSO>
-int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s, TrBufs& tb, bool head_done) {
+int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s, TrBufs& tb, bool head_done,
+                  float* dx_only = nullptr) {
     fd_ctx* ctx = m->ctx;
     const fd_bf16_images* im = m->bf16;
     const int B = m->saved_B;
@@ -2905,12 +2909,15 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
     const int M = B * T;
     const float* P = m->params;
     const TrDims d = make_dims(m, B, m->saved_p, m->saved_seed);
-    if (!accumulate && !head_done)
+    const bool wg = dx_only == nullptr;
+    if (wg && !accumulate && !head_done)
         FD_HIP(ctx, hipMemsetAsync(grads, 0, sizeof(float) * (size_t)(L > 0 ? m->layers[0].in_w : m->nparams), s));
     // ---- unembedder (the fused loss head, fd_score_train_dsm, has already produced tb.dh and these two gradients)
     if (!head_done) {
-        fdgemm::linear_bwd_weight(dout, tb.hL, grads + m->un_w, M, C, D, true, s, tb.skp, kSkpFloats);
-        if (int rc = fd_colsum_det(ctx, dout, grads + m->un_b, M, C, s)) return rc;
+        if (wg) {
+            fdgemm::linear_bwd_weight(dout, tb.hL, grads + m->un_w, M, C, D, true, s, tb.skp, kSkpFloats);
+            if (int rc = fd_colsum_det(ctx, dout, grads + m->un_b, M, C, s)) return rc;
+        }
         fdgemm::linear_bwd_input(dout, P + m->un_w, tb.dh, M, C, D, false, s);
     }
     const size_t scr = std::max((size_t)TW * KS1 * 1024, (size_t)4 * DT * 1024);
@@ -2939,9 +2946,9 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
     }
     // side stream: the weight gradients of layer l only need that layer's k_tr_ffn_bwd / k_tr_attn_bwd outputs, so they run
     // beside the input-gradient chain of layers l-1 .. 0 (both are latency-bound and leave most CUs idle on their own)
-    if (!ctx->side_stream) FD_HIP(ctx, side_stream_create(&ctx->side_stream));
-    if (!ctx->side_stream2) FD_HIP(ctx, side_stream_create(&ctx->side_stream2));
-    while ((int)ctx->side_events.size() < L + 3) {
+    if (wg && !ctx->side_stream) FD_HIP(ctx, side_stream_create(&ctx->side_stream));
+    if (wg && !ctx->side_stream2) FD_HIP(ctx, side_stream_create(&ctx->side_stream2));
+    while (wg && (int)ctx->side_events.size() < L + 3) {
         hipEvent_t e;
         FD_HIP(ctx, hipEventCreateWithFlags(&e, kTrEventFlags));
         ctx->side_events.push_back(e);
@@ -3031,7 +3038,7 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
             // kernel is a packet of its own between this kernel and the next layer's k_tr_ffn_bwd (6-7 us of an idle chip per
             // layer in the kernel trace); bound to the launch itself (hipExtLaunchKernelGGL's stop event) it is the kernel's own
             // completion signal.  FDIFF_TR_EXT_EVENT=0: the recorded event.
-            hipEvent_t stop_ev = (ext_event && !serial) ? ctx->side_events[l] : nullptr;
+            hipEvent_t stop_ev = (wg && ext_event && !serial) ? ctx->side_events[l] : nullptr;
             if (attn_oh) hipExtLaunchKernelGGL((k_tr_attn_bwd<KS1, DT, 4, 1>), dim3(2 * d.NP, B), dim3(256), lds_ab, s, nullptr, stop_ev, 0, d, ab);
             else if (attn_nw == 8) hipExtLaunchKernelGGL((k_tr_attn_bwd<KS1, DT, 8, 0>), dim3(d.NP, B), dim3(512), lds_ab, s, nullptr, stop_ev, 0, d, ab);
             else hipExtLaunchKernelGGL((k_tr_attn_bwd<KS1, DT, 4, 0>), dim3(d.NP, B), dim3(256), lds_ab, s, nullptr, stop_ev, 0, d, ab);
@@ -3053,6 +3060,7 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
             }
 #endif
         }
+        if (!wg) continue;
         WgLayer w{};
         w.x0T = b.x0T; w.attT = b.attT; w.doT = b.doT; w.dqkvT = b.dqkvT;
         w.stage = b.stage; w.active = b.active;
@@ -3103,6 +3111,11 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
         else
             hipLaunchKernelGGL(k_tr_sum_parts, dim3((unsigned)((nn / 4 + 256) / 256)), dim3(256), 0, s, tb.dres[0], tb.dxp[0], attn_parts,
                            tb.part_stride, tb.dh, nn);
+    }
+    if (!wg) {      // d x = d h W_emb
+        fdgemm::linear_bwd_input(tb.dh, P + m->emb_w, dx_only, M, D, C, false, s);
+        FD_LAUNCH_CHECK(ctx);
+        return FD_OK;
     }
     if (L > 0) {
         VecRedArgs va{};
@@ -3234,6 +3247,18 @@ int fd_score_backward_bf16(fd_score* m, const float* dout, float* grads, int acc
 #define CALL_B(K, T_, O) tr_backward_t<K, T_, O>(m, dout, grads, accumulate, s, tb, false)
     FD_TR_DISPATCH(CALL_B);
 #undef CALL_B
+}
+
+int fd_score_input_vjp_bf16(fd_score* m, const float* dout, float* dx, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    if (int rc = fd_train_async_check(ctx)) return rc;
+    const size_t need = fd_train_bf16_workspace(m, m->saved_B);
+    if (ctx->ws_bytes < need) return fd_fail(ctx, FD_ERR_STATE, "fd_score_input_vjp: workspace was resized since the training forward");
+    TrBufs tb;
+    tr_carve(m, m->saved_B, (char*)ctx->ws, &tb, m->saved_mask_set);
+#define CALL_V(K, T_, O) tr_backward_t<K, T_, O>(m, dout, nullptr, 0, s, tb, false, dx)
+    FD_TR_DISPATCH(CALL_V);
+#undef CALL_V
 }
 
 // ---- forward + denoising score-matching loss + backward as ONE call (fd_score_train_dsm) ----

@@ -386,6 +386,17 @@ class ScoreModule:
         _C.check(rc, ctx)
         return grads
 
+    def input_vjp(self, dscore: torch.Tensor) -> torch.Tensor:
+        """d x = (d score / d x)^T dscore for the last training-mode forward (fd_score_input_vjp): a new device tensor shaped like
+        the forward's input.  Consumes that forward as ``backward`` does; no parameter gradient is formed, ``grads`` and a pending
+        ``zero_grad()`` are left as they are."""
+        ctx, h = self._engine()
+        d = _C.dev_f32(dscore, "dscore")
+        dx = torch.empty_like(d)
+        rc = _C.lib().fd_score_input_vjp(h, d.data_ptr(), dx.data_ptr(), _C.stream_of(d))
+        _C.check(rc, ctx)
+        return dx
+
     def grad_views(self) -> "OrderedDict[str, torch.Tensor]":
         assert self.grads is not None
         return OrderedDict((name, self.grads[off:off + numel].view(*shape))

@@ -23,10 +23,15 @@ Probability-flow ODE (an extension, not in the reference): ``sample_ode`` integr
 marginals (Song et al. 2021, Sec. 4.3) by Euler or Heun, the whole loop one engine call (fd_sampler_run_ode); ``encode`` /
 ``decode`` run it data -> latents and back.  ``ODESampler`` is a DiffusionSampler whose ``sample`` is ``sample_ode``
 (hydra: ``sampler=ode``).
+
+Likelihood (an extension, not in the reference): ``log_likelihood`` evaluates log p(x) under the probability-flow ODE
+(Song et al. 2021, Sec. 4.3, App. D.2): the ODE runs data -> latents with the divergence integral along it, one engine call
+per launch (fd_likelihood_run); ``sampling.likelihood.to_data_space`` maps the result to the series as the user holds them.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -37,6 +42,7 @@ from ..models.score_models import _PRECISIONS, ScoreModule
 from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
 from ..utils.fourier import dft, dft_standardize
+from .likelihood import ESTIMATORS, EXACT_MAX_DIMS, LikelihoodResult, drift_divergence
 
 
 class DiffusionSampler:
@@ -181,6 +187,100 @@ class DiffusionSampler:
                                          X.shape[0], mode, _C.stream_of(X))
         _C.check(rc, ctx)
         return X
+
+    # ------------------------------------------------------------ likelihood (extension, not in the reference)
+    def log_likelihood(self, X: torch.Tensor, num_diffusion_steps: int = 100, solver: str = "heun", *, estimator: str = "rademacher",
+                       n_probes: int = 1, probes: Optional[torch.Tensor] = None, seed: Optional[int] = None) -> LikelihoodResult:
+        """Log-density of every series of X (n, max_len, n_channels), in sample space, under the probability-flow ODE:
+        log p_1(x_1) + the divergence integral along the ODE from t = eps to t = 1 on ``linspace(eps, 1, N + 1)`` (the grid and
+        solver of ``encode``).  The trace of the score Jacobian is estimated per series with ``n_probes`` Hutchinson probes
+        (``rademacher`` or ``gaussian``, from the engine's Philox: one key from ``_rng.stream()``, or ``seed`` as the key), or
+        exactly (``exact``: the T*C basis vectors, T*C <= EXACT_MAX_DIMS).  probes (n, n_probes, T, C) injects the probes.
+        The probes of a series run as replicated rows of one launch: a launch holds max(1, sample_batch_size // replicas) series.
+        Returns a ``LikelihoodResult``; ``to_data_space`` converts ``log_prob`` to the series as the user holds them."""
+        T, Cn = self.max_len, self.n_channels
+        if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (T, Cn):
+            raise ValueError(f"X must be a tensor of shape (n, {T}, {Cn}), got "
+                             f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
+        n = int(X.shape[0])
+        if n == 0:
+            raise ValueError("X is an empty batch")
+        if solver not in self._SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}")
+        if estimator not in ESTIMATORS:
+            raise ValueError(f"estimator must be one of {ESTIMATORS}, got {estimator!r}")
+        N = int(num_diffusion_steps)
+        if N < 1:
+            raise ValueError(f"num_diffusion_steps must be >= 1, got {N}")
+        if estimator == "exact":
+            if T * Cn > EXACT_MAX_DIMS:
+                raise ValueError(f"estimator='exact' replicates each series T*C = {T * Cn} times; it is allowed up to "
+                                 f"{EXACT_MAX_DIMS} dimensions: use a Hutchinson estimator")
+            if probes is not None:
+                raise ValueError("probes cannot be injected with estimator='exact'")
+            reps = T * Cn
+        else:
+            if int(n_probes) < 1:
+                raise ValueError(f"n_probes must be >= 1, got {n_probes}")
+            reps = int(n_probes)
+            if probes is not None and (not isinstance(probes, torch.Tensor) or tuple(probes.shape) != (n, reps, T, Cn)):
+                raise ValueError(f"probes must be a tensor of shape {(n, reps, T, Cn)}, got "
+                                 f"{tuple(probes.shape) if isinstance(probes, torch.Tensor) else type(probes)}")
+        sch = self.noise_scheduler
+        if sch.G is None:
+            raise RuntimeError("the noise scheduler has no noise scaling yet (set_noise_scaling)")
+        ts = torch.linspace(sch.eps, 1.0, N + 1).to(torch.float32)
+        if not bool((ts[1:] > ts[:-1]).all()):
+            raise ValueError(f"the likelihood grid linspace({sch.eps}, 1, {N + 1}) is not strictly increasing in float32")
+        kind, p0, p1 = sch.kind, *sch._params()
+        drift = drift_divergence(kind, float(p0), float(p1), ts.tolist(), solver, T * Cn)
+
+        model = self.score_model
+        ctx, h = model._engine()
+        dev = model.device
+        mode = _PRECISIONS[model.precision_effective]
+        p = sch._c_params()
+        G = sch.G_on(dev)
+        ts_arr = (C.c_float * (N + 1))(*ts.tolist())
+        if probes is None and estimator != "exact":
+            key, off = (int(seed), 0) if seed is not None else _rng.stream()
+        per_launch = max(1, self.sample_batch_size // reps)
+        prior, score, lat = [], [], []
+        for lo in range(0, n, per_launch):
+            nb = min(per_launch, n - lo)
+            rows = nb * reps
+            x = X[lo:lo + nb].to(device=dev, dtype=torch.float32).repeat_interleave(reps, dim=0).contiguous()
+            if estimator == "exact":
+                e = torch.eye(T * Cn, device=dev, dtype=torch.float32).view(T * Cn, T, Cn).repeat(nb, 1, 1).contiguous()
+            elif probes is not None:
+                e = _C.dev_f32(probes[lo:lo + nb].to(device=dev, dtype=torch.float32).reshape(rows, T, Cn).contiguous(), "probes")
+            else:
+                e = torch.empty((rows, T, Cn), device=dev, dtype=torch.float32)
+                _C.check(_C.lib().fd_randn(ctx, e.data_ptr(), e.numel(), key, off, _C.stream_of(e)), ctx)
+                off += (e.numel() + 3) // 4
+                if estimator == "rademacher":
+                    e = torch.where(e >= 0, 1.0, -1.0).to(torch.float32).contiguous()
+            sdiv = torch.empty(rows, device=dev, dtype=torch.float32)
+            rc = _C.lib().fd_likelihood_run(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], x.data_ptr(), e.data_ptr(),
+                                            sdiv.data_ptr(), rows, mode, _C.stream_of(x))
+            _C.check(rc, ctx)
+            x1 = x.view(nb, reps, T, Cn)[:, 0].contiguous()
+            lp = torch.empty(nb, device=dev, dtype=torch.float32)
+            _C.check(_C.lib().fd_prior_logp(ctx, C.byref(p), G.data_ptr(), x1.data_ptr(), lp.data_ptr(), nb, T, Cn, _C.stream_of(x1)), ctx)
+            prior.append(lp.cpu())
+            score.append(sdiv.view(nb, reps).cpu())
+            lat.append(x1.cpu())
+        sd = torch.cat(score).to(torch.float64)
+        if estimator == "exact":
+            div, se = sd.sum(dim=1), None
+        else:
+            div = sd.mean(dim=1)
+            se = sd.std(dim=1) / math.sqrt(reps) if reps > 1 else None
+        prior_lp = torch.cat(prior).to(torch.float64)
+        delta = div + drift
+        return LikelihoodResult(log_prob=prior_lp + delta, prior_log_prob=prior_lp, delta_log_prob=delta, latents=torch.cat(lat),
+                                std_err=se, estimator=estimator, n_probes=reps if estimator != "exact" else 0,
+                                num_diffusion_steps=N, solver=solver)
 
     # ------------------------------------------------------------ conditional sampling (extension, not in the reference)
     def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,

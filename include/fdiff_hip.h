@@ -263,6 +263,10 @@ int fd_score_forward_train(fd_score* m, const float* x, const float* t, float* o
                            float dropout_p, uint64_t seed, uint64_t offset, void* stream);
 /* dout (B,T,C) -> grads (flat, same layout as params; ACCUMULATED into if accumulate != 0) */
 int fd_score_backward(fd_score* m, const float* dout, float* grads, int accumulate, void* stream);
+/* Input vector-Jacobian product of the last fd_score_forward_train: dx (B,T,C) = (d out / d x)^T dout.  Consumes the saved
+ * forward as fd_score_backward does (same checks and error codes); forms no parameter gradient and touches no gradient buffer.
+ * Every backbone and training arithmetic.  (Not in the reference; the likelihood loop below is its user.) */
+int fd_score_input_vjp(fd_score* m, const float* dout, float* dx, void* stream);
 
 /* One optimisation step's device work in one call: fd_score_forward_train -> fd_dsm_loss -> fd_score_backward
  * (the body of get_sde_loss_fn's loss_fn + loss.backward(), src/fdiff/utils/losses.py:39-125 and
@@ -342,6 +346,25 @@ int fd_pf_ode_drift(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const
                     float* v_out, int B, int T, int C, void* stream);
 int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
                        float* x, int B, int mode, void* stream);
+
+/* Likelihood extension (NOT in the reference; Song et al. 2021, Sec. 4.3 and App. D.2): the exact log-density of the
+ * probability-flow ODE above,
+ *   log p_0(x_0) = log p_1(x_1) + int_eps^1 div v(x(t), t) dt,   div v = -a T C - 0.5 g^2 tr(diag(G_k^2) ds/dx)
+ * with the trace estimated per row b as e_b^T diag(G_k^2) (ds/dx) e_b for a probe e_b (Hutchinson; the basis vectors give it exactly).
+ *   fd_prior_logp    : out[b] = sum_{t,c} log N(x_btc; 0, (sigma_p G_t)^2), sigma_p = 1 (VP) or sigma_max (VE): the density of
+ *                      fd_prior_sample.  out: device float[B].
+ *   fd_likelihood_run: integrates the ODE in place on x (B,T,C) from data to latents over the HOST grid timesteps[0 .. n_steps]
+ *                      (strictly increasing, finite; FD_ERR_ARG otherwise) by Euler or Heun exactly as fd_sampler_run_ode, and
+ *                      writes score_div[b] = sum_i w_i (-0.5 g(t_i)^2) <(ds/dx)^T (G^2 e_b), e_b> over the same quadrature (Heun:
+ *                      the trapezoid of its two stages).  probes: device (B,T,C), e_b per row (replicate a series over rows for
+ *                      several probes).  The drift part of the divergence, -T C sum_i w_i a(t_i), is the caller's (host, float64).
+ *                      Each evaluation is fd_score_forward_train (dropout 0) + fd_score_input_vjp + one fused stage kernel; mode
+ *                      FD_MODE_BF16 runs the bf16 training kernels where the model has them (else exact f32).  Per-row sums in
+ *                      float64, fixed order: bit-reproducible.  The stage state lives in a context-owned buffer outside the
+ *                      workspace (grown on first use: synchronising).  No host synchronisation inside the loop. */
+int fd_prior_logp(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const float* x, float* out, int B, int T, int C, void* stream);
+int fd_likelihood_run(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
+                      float* x, const float* probes, float* score_div, int B, int mode, void* stream);
 
 /* ------------------------------------------------------------ a11 optimiser
  * torch.optim.AdamW defaults + diffusers cosine-warmup + Lightning global-norm clip
