@@ -4,7 +4,8 @@ score model (an extension, not in the reference): DiffusionSampler.log_likelihoo
 a Hutchinson or exact divergence, on the MI355X engine), mapped to the series as the datamodule holds them (time domain, data
 scale), so that a time-domain and a frequency-domain model are compared on one number.  Writes the key `likelihood` of
 results.yaml: mean and standard error over series of the data-space NLL, bits per dimension, the sample-space NLL and the
-settings.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/impute.py does."""
+settings; solver=rk45 (adaptive, rtol / atol) adds nfe_mean, nfe_max and n_not_converged and takes the NLL over the converged
+series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/impute.py does."""
 from __future__ import annotations
 
 import logging
@@ -72,26 +73,38 @@ class LikelihoodRunner:
             mean, std = self.datamodule.feature_mean_and_std
             Xs = (Xs - mean.to(dev)) / std.to(dev)
         lo, hi = shard_range(int(X.shape[0]), self.dist.rank, self.dist.world)     # independent rows: no exchange
-        lp = torch.empty(0, dtype=torch.float64)
+        adaptive = str(cfg.solver) == "rk45"
+        kw = dict(rtol=float(cfg.rtol), atol=float(cfg.atol), max_evals=int(cfg.max_evals)) if adaptive else {}
+        lp, nfe = torch.empty(0, dtype=torch.float64), torch.empty(0, dtype=torch.int64)
         if hi > lo:
             res = self.sampler.log_likelihood(Xs[lo:hi], int(cfg.num_diffusion_steps), str(cfg.solver), estimator=str(cfg.estimator),
-                                              n_probes=int(cfg.n_probes))
-            lp = res.log_prob
+                                              n_probes=int(cfg.n_probes), **kw)
+            lp, nfe = res.log_prob, res.nfe
         if self.dist.world > 1:
             import torch.distributed as dist
             parts = [None] * self.dist.world
-            dist.all_gather_object(parts, lp)                                        # host-side gather of the results
-            lp = torch.cat([p for p in parts if p is not None and p.numel()], dim=0)
+            dist.all_gather_object(parts, (lp, nfe))                                 # host-side gather of the results
+            lp = torch.cat([p[0] for p in parts if p is not None and p[0].numel()], dim=0)
+            nfe = torch.cat([p[1] for p in parts if p is not None and p[1].numel()], dim=0)
         if self.dist.is_main:
             T, C = int(X.shape[1]), int(X.shape[2])
+            n_series = int(lp.numel())
+            if adaptive:      # a series whose integration did not converge has log_prob NaN: the NLL is over the others
+                ok = ~torch.isnan(lp)
+                extra = {"nfe_mean": float(nfe.double().mean()), "nfe_max": int(nfe.max()), "n_not_converged": int((~ok).sum()),
+                         "rtol": float(cfg.rtol), "atol": float(cfg.atol), "max_evals": int(cfg.max_evals)}
+                lp = lp[ok]
             lp_data = to_data_space(lp, self.fourier_transform, None if std is None else std.cpu(), max_len=T, n_channels=C)
             nll, nll_se = mean_se(-lp_data)
             bpd, bpd_se = mean_se(bits_per_dim(lp_data, T, C))
             nll_s, nll_s_se = mean_se(-lp)
-            out = {"num_series": int(lp.numel()), "nll_data": nll, "nll_data_se": nll_se, "bits_per_dim": bpd, "bits_per_dim_se": bpd_se,
-                   "nll_sample": nll_s, "nll_sample_se": nll_s_se, "num_diffusion_steps": int(cfg.num_diffusion_steps),
+            out = {"num_series": n_series, "nll_data": nll, "nll_data_se": nll_se, "bits_per_dim": bpd, "bits_per_dim_se": bpd_se,
+                   "nll_sample": nll_s, "nll_sample_se": nll_s_se,
+                   "num_diffusion_steps": None if adaptive else int(cfg.num_diffusion_steps),
                    "solver": str(cfg.solver), "estimator": str(cfg.estimator), "n_probes": int(cfg.n_probes),
                    "fourier_transform": bool(self.fourier_transform), "precision": self.score_model.precision_effective}
+            if adaptive:
+                out.update(extra)
             results_path = self.save_dir / "results.yaml"
             results = yaml.safe_load(open(results_path)) if results_path.exists() else None
             results = results if isinstance(results, dict) else {}

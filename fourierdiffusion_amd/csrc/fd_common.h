@@ -87,6 +87,8 @@ struct fd_ctx {
     // them; grow-only
     void* ll_buf = nullptr;
     size_t ll_bytes = 0;
+    // fd_likelihood_run_adaptive: pinned host words the running-row counts of its attempts are copied to
+    int* ll_host = nullptr;
 };
 
 float* fd_gemm_scratch(fd_ctx* ctx, size_t* n_floats);   // fd_ctx.hip

@@ -34,6 +34,7 @@ extern "C" int fd_ctx_destroy(fd_ctx* ctx) {
     if (ctx->trp_flags) (void)hipFree(ctx->trp_flags);
     if (ctx->prof_clk) (void)hipFree(ctx->prof_clk);
     if (ctx->ll_buf) (void)hipFree(ctx->ll_buf);
+    if (ctx->ll_host) (void)hipHostFree(ctx->ll_host);
     for (hipEvent_t e : ctx->side_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->tr_readers_event)
         if (e) (void)hipEventDestroy(e);

@@ -18,6 +18,8 @@ import torch
 # estimator="exact" replicates every series over its T*C basis vectors: refused above this many dimensions per series
 EXACT_MAX_DIMS = 1024
 ESTIMATORS = ("rademacher", "gaussian", "exact")
+# solver="rk45": the cap on score evaluations per row when the caller gives none (a row that would pass it stops, not converged)
+RK45_MAX_EVALS = 20000
 
 
 @dataclass
@@ -26,7 +28,10 @@ class LikelihoodResult:
 
     log_prob = prior_log_prob + delta_log_prob; delta_log_prob = drift part + the mean over probes of the score part of the
     divergence integral.  latents: x_1 (n, T, C), float32.  std_err: the standard error of the probe mean (n_probes > 1, else
-    None)."""
+    None).  nfe: score evaluations per series (rk45: the maximum over its rows, counted as scipy's nfev; Euler / Heun: N / 2N).
+    converged: bool per series (rk45: every row reached t = 1; a series that did not has log_prob NaN).  grid: rk45's accepted
+    times per row, float64 (n, replicas, S), t = eps first, NaN-padded (None for Euler / Heun).  rtol / atol: rk45's tolerances.
+    num_diffusion_steps is None for rk45."""
     log_prob: torch.Tensor
     prior_log_prob: torch.Tensor
     delta_log_prob: torch.Tensor
@@ -34,8 +39,13 @@ class LikelihoodResult:
     std_err: Optional[torch.Tensor]
     estimator: str
     n_probes: int
-    num_diffusion_steps: int
+    num_diffusion_steps: Optional[int]
     solver: str
+    nfe: Optional[torch.Tensor] = None
+    converged: Optional[torch.Tensor] = None
+    grid: Optional[torch.Tensor] = None
+    rtol: Optional[float] = None
+    atol: Optional[float] = None
 
     def bits_per_dim(self, max_len: int, n_channels: int) -> torch.Tensor:
         return bits_per_dim(self.log_prob, max_len, n_channels)
@@ -58,6 +68,13 @@ def ode_weights(ts: Sequence[float], solver: str) -> list:
 def drift_a(kind: int, p0: float, p1: float, t: float) -> float:
     """a(t) of the drift -a x: VP beta(t) / 2, VE 0 (as fd_sde_coef, in float64)."""
     return 0.5 * (p0 + t * (p1 - p0)) if kind == 0 else 0.0
+
+
+def drift_integral(kind: int, p0: float, p1: float, t0: float, t1: float, dims: int) -> float:
+    """The exact drift part of the divergence integral, -dims int_t0^t1 a(t) dt (float64; a is linear in t)."""
+    if kind != 0:
+        return 0.0
+    return -dims * 0.5 * (p0 * (t1 - t0) + 0.5 * (p1 - p0) * (t1 * t1 - t0 * t0))
 
 
 def drift_divergence(kind: int, p0: float, p1: float, ts: Sequence[float], solver: str, dims: int) -> float:

@@ -42,7 +42,7 @@ from ..models.score_models import _PRECISIONS, ScoreModule
 from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
 from ..utils.fourier import dft, dft_standardize
-from .likelihood import ESTIMATORS, EXACT_MAX_DIMS, LikelihoodResult, drift_divergence
+from .likelihood import ESTIMATORS, EXACT_MAX_DIMS, RK45_MAX_EVALS, LikelihoodResult, drift_divergence, drift_integral
 
 
 class DiffusionSampler:
@@ -175,7 +175,8 @@ class DiffusionSampler:
     def _run_ode(self, X: torch.Tensor, grid, solver: str) -> torch.Tensor:
         """X (bs,T,C) device float32, integrated in place over ``grid`` (ctypes float[N+1], N)."""
         if solver not in self._SOLVERS:
-            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}")
+            hint = " (rk45 is available for log_likelihood only)" if solver == "rk45" else ""
+            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}{hint}")
         model = self.score_model
         model.eval()
         sch = self.noise_scheduler
@@ -189,14 +190,21 @@ class DiffusionSampler:
         return X
 
     # ------------------------------------------------------------ likelihood (extension, not in the reference)
+    _LL_SOLVERS = {"euler": 0, "heun": 1, "rk45": 2}
+
     def log_likelihood(self, X: torch.Tensor, num_diffusion_steps: int = 100, solver: str = "heun", *, estimator: str = "rademacher",
-                       n_probes: int = 1, probes: Optional[torch.Tensor] = None, seed: Optional[int] = None) -> LikelihoodResult:
+                       n_probes: int = 1, probes: Optional[torch.Tensor] = None, seed: Optional[int] = None, rtol: float = 1e-5,
+                       atol: float = 1e-5, max_evals: int = RK45_MAX_EVALS) -> LikelihoodResult:
         """Log-density of every series of X (n, max_len, n_channels), in sample space, under the probability-flow ODE:
         log p_1(x_1) + the divergence integral along the ODE from t = eps to t = 1 on ``linspace(eps, 1, N + 1)`` (the grid and
         solver of ``encode``).  The trace of the score Jacobian is estimated per series with ``n_probes`` Hutchinson probes
         (``rademacher`` or ``gaussian``, from the engine's Philox: one key from ``_rng.stream()``, or ``seed`` as the key), or
         exactly (``exact``: the T*C basis vectors, T*C <= EXACT_MAX_DIMS).  probes (n, n_probes, T, C) injects the probes.
         The probes of a series run as replicated rows of one launch: a launch holds max(1, sample_batch_size // replicas) series.
+        solver="rk45" integrates adaptively instead (num_diffusion_steps is ignored): every row (series x probe) is one ODE on
+        [x, divergence integral], run by Dormand-Prince 5(4) with the step control of scipy's RK45 at rtol / atol, at most
+        max_evals score evaluations per row (Song et al. 2021 report likelihoods at rtol = atol = 1e-5).  A series any of whose
+        rows stops early (max_evals, or a step under scipy's min_step) has converged False and log_prob NaN.
         Returns a ``LikelihoodResult``; ``to_data_space`` converts ``log_prob`` to the series as the user holds them."""
         T, Cn = self.max_len, self.n_channels
         if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (T, Cn):
@@ -205,13 +213,22 @@ class DiffusionSampler:
         n = int(X.shape[0])
         if n == 0:
             raise ValueError("X is an empty batch")
-        if solver not in self._SOLVERS:
-            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}")
+        if solver not in self._LL_SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(self._LL_SOLVERS)}, got {solver!r}")
         if estimator not in ESTIMATORS:
             raise ValueError(f"estimator must be one of {ESTIMATORS}, got {estimator!r}")
-        N = int(num_diffusion_steps)
-        if N < 1:
-            raise ValueError(f"num_diffusion_steps must be >= 1, got {N}")
+        adaptive = solver == "rk45"
+        if adaptive:
+            rtol, atol, max_evals = float(rtol), float(atol), int(max_evals)
+            if not (math.isfinite(rtol) and rtol > 0 and math.isfinite(atol) and atol > 0):
+                raise ValueError(f"rk45 needs finite rtol > 0 and atol > 0, got rtol={rtol}, atol={atol}")
+            if max_evals < 8:
+                raise ValueError(f"max_evals must be >= 8 (the initial step and one attempt), got {max_evals}")
+            N = None
+        else:
+            N = int(num_diffusion_steps)
+            if N < 1:
+                raise ValueError(f"num_diffusion_steps must be >= 1, got {N}")
         if estimator == "exact":
             if T * Cn > EXACT_MAX_DIMS:
                 raise ValueError(f"estimator='exact' replicates each series T*C = {T * Cn} times; it is allowed up to "
@@ -229,11 +246,20 @@ class DiffusionSampler:
         sch = self.noise_scheduler
         if sch.G is None:
             raise RuntimeError("the noise scheduler has no noise scaling yet (set_noise_scaling)")
-        ts = torch.linspace(sch.eps, 1.0, N + 1).to(torch.float32)
-        if not bool((ts[1:] > ts[:-1]).all()):
-            raise ValueError(f"the likelihood grid linspace({sch.eps}, 1, {N + 1}) is not strictly increasing in float32")
         kind, p0, p1 = sch.kind, *sch._params()
-        drift = drift_divergence(kind, float(p0), float(p1), ts.tolist(), solver, T * Cn)
+        if adaptive:
+            t0 = float(sch.eps)
+            if not (math.isfinite(t0) and t0 < 1.0):
+                raise ValueError(f"rk45 integrates from eps to 1: need eps < 1, got {sch.eps}")
+            # every row integrates the drift part itself (exactly: a(t) is linear); the exact estimator sums rows, so it is
+            # removed from all but one (float32 parameters, as the engine reads them)
+            p0f, p1f = (float(C.c_float(v).value) for v in (p0, p1))
+            drift = drift_integral(kind, p0f, p1f, t0, 1.0, T * Cn)
+        else:
+            ts = torch.linspace(sch.eps, 1.0, N + 1).to(torch.float32)
+            if not bool((ts[1:] > ts[:-1]).all()):
+                raise ValueError(f"the likelihood grid linspace({sch.eps}, 1, {N + 1}) is not strictly increasing in float32")
+            drift = drift_divergence(kind, float(p0), float(p1), ts.tolist(), solver, T * Cn)
 
         model = self.score_model
         ctx, h = model._engine()
@@ -241,7 +267,10 @@ class DiffusionSampler:
         mode = _PRECISIONS[model.precision_effective]
         p = sch._c_params()
         G = sch.G_on(dev)
-        ts_arr = (C.c_float * (N + 1))(*ts.tolist())
+        if not adaptive:
+            ts_arr = (C.c_float * (N + 1))(*ts.tolist())
+        gcap = 1 + (max_evals - 2) // 6 if adaptive else 0
+        nfes, stats, grids = [], [], []
         if probes is None and estimator != "exact":
             key, off = (int(seed), 0) if seed is not None else _rng.stream()
         per_launch = max(1, self.sample_batch_size // reps)
@@ -260,10 +289,23 @@ class DiffusionSampler:
                 off += (e.numel() + 3) // 4
                 if estimator == "rademacher":
                     e = torch.where(e >= 0, 1.0, -1.0).to(torch.float32).contiguous()
-            sdiv = torch.empty(rows, device=dev, dtype=torch.float32)
-            rc = _C.lib().fd_likelihood_run(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], x.data_ptr(), e.data_ptr(),
-                                            sdiv.data_ptr(), rows, mode, _C.stream_of(x))
-            _C.check(rc, ctx)
+            if adaptive:
+                sdiv = torch.empty(rows, device=dev, dtype=torch.float64)
+                nfe = torch.empty(rows, device=dev, dtype=torch.int32)
+                st = torch.empty(rows, device=dev, dtype=torch.int32)
+                grid = torch.empty((rows, gcap), device=dev, dtype=torch.float64)
+                rc = _C.lib().fd_likelihood_run_adaptive(h, C.byref(p), G.data_ptr(), t0, 1.0, rtol, atol, max_evals, x.data_ptr(),
+                                                         e.data_ptr(), sdiv.data_ptr(), nfe.data_ptr(), st.data_ptr(),
+                                                         grid.data_ptr(), gcap, rows, mode, _C.stream_of(x))
+                _C.check(rc, ctx)
+                nfes.append(nfe.view(nb, reps).cpu())
+                stats.append(st.view(nb, reps).cpu())
+                grids.append(grid.view(nb, reps, gcap).cpu())
+            else:
+                sdiv = torch.empty(rows, device=dev, dtype=torch.float32)
+                rc = _C.lib().fd_likelihood_run(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], x.data_ptr(),
+                                                e.data_ptr(), sdiv.data_ptr(), rows, mode, _C.stream_of(x))
+                _C.check(rc, ctx)
             x1 = x.view(nb, reps, T, Cn)[:, 0].contiguous()
             lp = torch.empty(nb, device=dev, dtype=torch.float32)
             _C.check(_C.lib().fd_prior_logp(ctx, C.byref(p), G.data_ptr(), x1.data_ptr(), lp.data_ptr(), nb, T, Cn, _C.stream_of(x1)), ctx)
@@ -271,6 +313,8 @@ class DiffusionSampler:
             score.append(sdiv.view(nb, reps).cpu())
             lat.append(x1.cpu())
         sd = torch.cat(score).to(torch.float64)
+        if adaptive:
+            sd = sd - drift      # the score part of every row (its drift part is the exact one to rounding)
         if estimator == "exact":
             div, se = sd.sum(dim=1), None
         else:
@@ -278,9 +322,21 @@ class DiffusionSampler:
             se = sd.std(dim=1) / math.sqrt(reps) if reps > 1 else None
         prior_lp = torch.cat(prior).to(torch.float64)
         delta = div + drift
-        return LikelihoodResult(log_prob=prior_lp + delta, prior_log_prob=prior_lp, delta_log_prob=delta, latents=torch.cat(lat),
+        log_prob = prior_lp + delta
+        if adaptive:
+            nfe_s = torch.cat(nfes).amax(dim=1).to(torch.int64)
+            converged = (torch.cat(stats) == 1).all(dim=1)
+            grid = torch.cat(grids)
+            width = int((~torch.isnan(grid)).sum(dim=2).max())
+            grid = grid[:, :, :width].contiguous()
+            log_prob = torch.where(converged, log_prob, torch.full_like(log_prob, float("nan")))
+        else:
+            nfe_s = torch.full((n,), N if solver == "euler" else 2 * N, dtype=torch.int64)
+            converged, grid, rtol, atol = torch.ones(n, dtype=torch.bool), None, None, None
+        return LikelihoodResult(log_prob=log_prob, prior_log_prob=prior_lp, delta_log_prob=delta, latents=torch.cat(lat),
                                 std_err=se, estimator=estimator, n_probes=reps if estimator != "exact" else 0,
-                                num_diffusion_steps=N, solver=solver)
+                                num_diffusion_steps=N, solver=solver, nfe=nfe_s, converged=converged, grid=grid, rtol=rtol,
+                                atol=atol)
 
     # ------------------------------------------------------------ conditional sampling (extension, not in the reference)
     def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,

@@ -365,6 +365,21 @@ int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, co
 int fd_prior_logp(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const float* x, float* out, int B, int T, int C, void* stream);
 int fd_likelihood_run(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
                       float* x, const float* probes, float* score_div, int B, int mode, void* stream);
+/*   fd_likelihood_run_adaptive: the same integral with adaptive steps: every row b is one ODE on y_b = [x_b, acc_b] from t0 to t1
+ *                      (finite, t0 < t1), dacc/dt = div v (drift part included), integrated by Dormand-Prince 5(4) with the step
+ *                      control of scipy.integrate.RK45 (select_initial_step, min_step = 10 ulp(t), RMS error norm over the T*C + 1
+ *                      components with scale atol + rtol max(|y|, |y_new|), SAFETY 0.9, factors in [0.2, 10]).  Each row has its
+ *                      own grid.  x is integrated in place to the latents (a row that stops early keeps its last accepted state);
+ *                      device outputs: div_out[b] (double) the whole divergence integral, nfe_out[b] scipy's nfev (2 + 6 per
+ *                      attempted step), status_out[b] 1 converged, 2 step under min_step, 3 the next attempt would pass
+ *                      max_evals (>= 8); grid_out (nullable) (B, grid_cap) doubles: the accepted times, t0 first, NaN-padded,
+ *                      grid_cap >= 1 + (max_evals - 2) / 6.  rtol, atol > 0.  Evaluations and precision as fd_likelihood_run;
+ *                      controller state float64 per row, x and the stage vectors fp32; fixed-order reductions: bit-reproducible,
+ *                      and a row's result does not depend on the other rows of the launch.  SYNCHRONISES the stream once per
+ *                      attempted step (the running-row count of attempt k is read while attempt k + 1 is queued). */
+int fd_likelihood_run_adaptive(fd_score* m, const fd_sde_params* sde, const float* G, double t0, double t1, double rtol, double atol,
+                               int max_evals, float* x, const float* probes, double* div_out, int* nfe_out, int* status_out,
+                               double* grid_out, int grid_cap, int B, int mode, void* stream);
 
 /* ------------------------------------------------------------ a11 optimiser
  * torch.optim.AdamW defaults + diffusers cosine-warmup + Lightning global-norm clip

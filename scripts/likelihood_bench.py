@@ -4,7 +4,12 @@ stage kernel k_ll_stage) on the default-width model (D = 72, L = 10, H = 12), ra
 and at a T = 252 training shape (C = 8), in bf16 and fp32, with its pieces timed alone: the training forward (dropout 0), forward +
 fd_score_input_vjp, and forward + fd_score_backward (the parameter backward the VJP is compared against) at the same B.  The
 stage's share is the evaluation minus forward + VJP.  Runs alternated over `--reps` rounds, the median kept.  One JSON line per
-(shape, precision); `--out FILE` also writes them as a JSON list."""
+(shape, precision); `--out FILE` also writes them as a JSON list.
+
+`--rk45 RTOL` times the adaptive solver instead (fd_likelihood_run_adaptive, k_ll_rk_stage) against Heun at the same B, in ms per
+launched score evaluation: rk45 launches 2 + 6 attempts, one attempt more than its slowest row needs (the host reads the running-
+row count of attempt k while attempt k + 1 runs).  waste = 1 - sum of per-row nfe / (B x launched evaluations): the share of
+row-evaluations spent on rows already finished."""
 from __future__ import annotations
 
 import argparse
@@ -36,7 +41,10 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--only", choices=["ecg", "t252"], default=None)
     ap.add_argument("--out", default=None, help="also write the records to this JSON file")
+    ap.add_argument("--rk45", type=float, default=None, help="time solver='rk45' at this rtol = atol against Heun")
     args = ap.parse_args()
+    if args.rk45 is not None:
+        return bench_rk45(args)
     from fourierdiffusion_amd.sampling.sampler import DiffusionSampler
     from fourierdiffusion_amd.utils.dataclasses import DiffusableBatch
     from tests.gpu_util import make_model
@@ -86,6 +94,50 @@ def main() -> None:
             rec["backward_ms"] = rec["forward_backward_ms"] - rec["forward_ms"]
             rec["vjp_over_backward"] = rec["vjp_ms"] / rec["backward_ms"]
             rec["stage_and_host_ms"] = rec["likelihood_eval_ms"] - rec["forward_vjp_ms"]
+            print(json.dumps(rec), flush=True)
+            out.append(rec)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def bench_rk45(args) -> None:
+    from fourierdiffusion_amd.sampling.sampler import DiffusionSampler
+    from tests.gpu_util import make_model
+    shapes = {"ecg": dict(T=100, C=12, D=72, L=10, H=12), "t252": dict(T=252, C=8, D=72, L=10, H=12)}
+    B, E, tol = args.batch, args.evals, args.rk45
+    out = []
+    for name, cfg in shapes.items():
+        if args.only and name != args.only:
+            continue
+        for prec in ("bf16", "fp32"):
+            m, _, _ = make_model(cfg, precision=prec)
+            s = DiffusionSampler(score_model=m, sample_batch_size=B)
+            X = torch.randn((B, cfg["T"], cfg["C"]), generator=torch.Generator().manual_seed(0))
+            res = {}
+
+            def heun():
+                return timed(lambda: s.log_likelihood(X, E // 2, "heun", seed=1), 1) / (2 * (E // 2))
+
+            def rk45():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res["r"] = s.log_likelihood(X, solver="rk45", rtol=tol, atol=tol, seed=1)
+                torch.cuda.synchronize()
+                launched = int(res["r"].nfe.max()) + 6
+                return (time.perf_counter() - t0) / launched
+            heun(), rk45()      # warm-up
+            times = {"heun": [], "rk45": []}
+            for _ in range(args.reps):
+                times["heun"].append(heun())
+                times["rk45"].append(rk45())
+            r = res["r"]
+            launched = int(r.nfe.max()) + 6
+            rec = {"shape": name, "T": cfg["T"], "C": cfg["C"], "B": B, "precision": prec, "rtol": tol, "reps": args.reps,
+                   "heun_ms_per_eval": 1e3 * statistics.median(times["heun"]), "rk45_ms_per_eval": 1e3 * statistics.median(times["rk45"]),
+                   "nfe_mean": float(r.nfe.double().mean()), "nfe_max": int(r.nfe.max()), "launched_evals": launched,
+                   "waste": 1.0 - float(r.nfe.double().sum()) / (B * launched), "n_not_converged": int((~r.converged).sum())}
+            rec["rk45_over_heun"] = rec["rk45_ms_per_eval"] / rec["heun_ms_per_eval"]
             print(json.dumps(rec), flush=True)
             out.append(rec)
     if args.out:

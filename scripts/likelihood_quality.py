@@ -5,8 +5,11 @@ datamodule holds them), with a closed-form anchor: the multivariate Gaussian fit
 
 Two default-width transformers (D = 72, L = 10, H = 12, VP-SDE) are trained for `--epochs` on SyntheticDatamodule (sines, generated
 locally from the seed; standardised), one on the series and one on their spectra (Fourier noise scaling).  Each then evaluates the
-first `--num-series` held-out series at N = 25, 50, 100, 200 steps.  Rows: mean data-space NLL per series and bits per dimension with
-their standard errors over series (the probe noise is inside them).  One JSON line per row; `--out FILE` writes the table."""
+first `--num-series` held-out series at N = 25, 50, 100, 200 steps, then adaptively (solver="rk45") at each of `--rtols`
+(rtol = atol): mean and max NFE, series not converged within `--max-evals` (left out of the NLL), and the difference to the
+Heun-200 row.  Rows: mean data-space NLL per series and bits per dimension with their standard errors over series (the probe noise
+is inside them).  `--precision` sets the likelihood arithmetic (default: the model's).  One JSON line per row; `--out FILE` writes
+the table."""
 from __future__ import annotations
 
 import argparse
@@ -38,6 +41,9 @@ def main() -> None:
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--C", type=int, default=4)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--rtols", default="1e-3,1e-5", help="rk45 tolerances (comma-separated; empty: no rk45 rows)")
+    ap.add_argument("--max-evals", type=int, default=20000)
+    ap.add_argument("--precision", choices=["bf16", "fp32"], default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from fourierdiffusion_amd.dataloaders.datamodules import SyntheticDatamodule
@@ -87,7 +93,10 @@ def main() -> None:
         mean, std = dm.feature_mean_and_std
         X = dm.X_test[:n].float().cuda()
         Xs = ((dft(X) if fourier else X) - mean) / std
+        if args.precision:
+            model.precision = args.precision
         sampler = DiffusionSampler(score_model=model, sample_batch_size=256)
+        heun200 = None
         for N in STEPS:
             t0 = time.perf_counter()
             res = sampler.log_likelihood(Xs, N, "heun", seed=args.seed)
@@ -97,7 +106,21 @@ def main() -> None:
             b, bse = mean_se(bits_per_dim(lp, T, C))
             emit({"model": f"{tag} domain", "steps": N, "evals": 2 * N, "nll_data": nll, "nll_data_se": se, "bits_per_dim": b,
                   "bits_per_dim_se": bse, "nll_sample": mean_se(-res.log_prob)[0], "ms_per_series": 1e3 * sec / n,
-                  "finite": bool(torch.isfinite(lp).all())})
+                  "finite": bool(torch.isfinite(lp).all()), "precision": model.precision_effective})
+            if N == 200:
+                heun200 = nll
+        for rtol in [float(r) for r in args.rtols.split(",") if r.strip()]:
+            t0 = time.perf_counter()
+            res = sampler.log_likelihood(Xs, solver="rk45", rtol=rtol, atol=rtol, max_evals=args.max_evals, seed=args.seed)
+            sec = time.perf_counter() - t0
+            ok = res.converged
+            lp = to_data_space(res.log_prob[ok], fourier, std.cpu())
+            nll, se = mean_se(-lp) if lp.numel() > 1 else (float("nan"), float("nan"))
+            b, bse = mean_se(bits_per_dim(lp, T, C)) if lp.numel() > 1 else (float("nan"), float("nan"))
+            emit({"model": f"{tag} domain", "solver": "rk45", "rtol": rtol, "nfe_mean": float(res.nfe.double().mean()),
+                  "nfe_max": int(res.nfe.max()), "n_not_converged": int((~ok).sum()), "nll_data": nll, "nll_data_se": se,
+                  "bits_per_dim": b, "bits_per_dim_se": bse, "minus_heun200": None if heun200 is None else nll - heun200,
+                  "ms_per_series": 1e3 * sec / n, "precision": model.precision_effective})
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"T": T, "C": C, "epochs": args.epochs, "num_series": n, "rows": rows}, f, indent=1)
