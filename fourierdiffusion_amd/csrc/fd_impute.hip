@@ -265,11 +265,6 @@ int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s
     return fourier ? launch_variant<false, true>(ctx, a, lds, s) : launch_variant<false, false>(ctx, a, lds, s);
 }
 
-__global__ __launch_bounds__(256) void k_fill_t(float* __restrict__ p, const float* __restrict__ ts, int B, size_t n) {
-    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
-    if (i < n) p[i] = ts[i / B];
-}
-
 // marginal mean coefficient and std of the perturbation kernel at t (sde.py:108-123, 187-210), in double
 void marginal_coef(const fd_sde_params& p, double t, double* alpha, double* sdev) {
     if (p.kind == 0) {
@@ -303,14 +298,11 @@ extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, cons
                                      float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                                      const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps,
                                      uint64_t seed, uint64_t offset, int B, int mode, void* stream) {
-    if (!m) return FD_ERR_ARG;
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute")) return rc;
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, sde && G && timesteps && x, "fd_sampler_run_impute: null pointer");
-    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_sampler_run_impute: unknown SDE kind %d", sde->kind);
-    FD_REQUIRE(ctx, n_steps > 0 && B > 0, "fd_sampler_run_impute: n_steps=%d B=%d", n_steps, B);
+    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_impute: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_impute: n_steps=%d", n_steps);
     FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_impute: step size must be > 0 (sde.py:158)");
-    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_sampler_run_impute: unknown mode %d", mode);
-    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_sampler_run_impute: call fd_score_prepare first");
     hipStream_t s = (hipStream_t)stream;
     const int T = m->d.max_len, C = m->d.n_channels;
     ImpArgs a{};
@@ -327,27 +319,22 @@ extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, cons
         al[i] = (float)aa;
         sd[i] = (float)ss;
     }
-    // workspace as fd_sampler_run's step-by-step path: [forward scratch | score | t vectors of every step | timesteps]
+    // workspace as fd_sampler_run's step-by-step path
     const size_t n = (size_t)B * T * C;
-    const size_t fwd = (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
-    const size_t own = fd_ws::padded(n * sizeof(float));
-    const size_t nt = (size_t)n_steps * B;
-    if (int rc = fd_ws_reserve(ctx, fwd + own + fd_ws::padded(nt * sizeof(float)) + fd_ws::padded((size_t)n_steps * sizeof(float))))
-        return rc;
+    const size_t fwd = fd_loop_fwd_workspace(m, B);
+    float* tvec0 = nullptr;
+    size_t tstride = 0;
+    if (int rc = fd_step_table(ctx, fwd, fd_ws::padded(n * sizeof(float)), timesteps, n_steps, B, s, &tvec0, &tstride)) return rc;
     float* score = (float*)((char*)ctx->ws + fwd);
-    float* tvec0 = (float*)((char*)ctx->ws + fwd + own);
-    float* ts = (float*)((char*)tvec0 + fd_ws::padded(nt * sizeof(float)));
-    // pageable source: the runtime stages the copy before returning
-    FD_HIP(ctx, hipMemcpyAsync(ts, timesteps, (size_t)n_steps * sizeof(float), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fill_t, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, tvec0, ts, B, nt);
-    FD_LAUNCH_CHECK(ctx);
 
     // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run), observation noise behind them
     const uint64_t per_step = (uint64_t)((n + 3) / 4);
     a.x = x; a.out = x; a.score = score;
     a.seed = seed;
     for (int i = 0; i < n_steps; ++i) {
-        if (int rc = fd_score_forward_any(m, x, tvec0 + (size_t)i * B, score, B, mode, s)) return rc;
+        float* tvec = tvec0 + (size_t)i * tstride;
+        if (!tstride) fd_fill(tvec, B, timesteps[i], s);
+        if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
         a.zstep = z_steps ? z_steps + (size_t)i * n : nullptr;
         a.zobs = zobs_steps ? zobs_steps + (size_t)i * n : nullptr;
         a.cf = cf[i];

@@ -18,11 +18,6 @@ namespace {
 
 constexpr int kBlock = 256;
 
-__global__ __launch_bounds__(kBlock) void k_ll_fill(float* __restrict__ p, int n, float v) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 // dout = G_k^2 e  (built once per run: the input of the VJP is linear, the per-evaluation factor -0.5 g^2 is applied in k_ll_stage)
 __global__ __launch_bounds__(kBlock) void k_ll_dout(const float* __restrict__ G, const float* __restrict__ probe,
                                                       float* __restrict__ dout, size_t n, int T, int C) {
@@ -94,13 +89,13 @@ __global__ __launch_bounds__(kBlock) void k_ll_prior(const float* __restrict__ G
     if (threadIdx.x == 0) out[blockIdx.x] = (float)(s - 0.5 * (double)n_row * log(2.0 * M_PI));
 }
 
-// The stage state of one run, outside the arena (the training forward and its VJP own the arena between them): grow-only,
-// freed with the context
-struct LlBufs {
-    float *tvec, *dout, *score, *dx, *x0, *v0;
-    double *acc, *d0;
-};
-int ll_grow(fd_ctx* ctx, size_t need) {
+// The state of one run, outside the arena (the training forward and its VJP own the arena between them): grow-only, freed with the
+// context.  layout(take) points the run's buffers at consecutive shares of ctx->ll_buf, take(bytes) returning the next one; it runs
+// twice, first to size the buffer.
+template <class Layout>
+int ll_carve(fd_ctx* ctx, Layout layout) {
+    size_t need = 0;
+    layout([&](size_t bytes) -> char* { need += fd_ws::padded(bytes); return nullptr; });
     if (ctx->ll_bytes < need) {
         if (ctx->ll_buf) (void)hipFree(ctx->ll_buf);      // (synchronising: an earlier run on any stream has finished with it)
         ctx->ll_buf = nullptr;
@@ -108,22 +103,26 @@ int ll_grow(fd_ctx* ctx, size_t need) {
         FD_HIP(ctx, hipMalloc(&ctx->ll_buf, need));
         ctx->ll_bytes = need;
     }
+    char* p = (char*)ctx->ll_buf;
+    layout([&](size_t bytes) { char* q = p; p += fd_ws::padded(bytes); return q; });
     return FD_OK;
 }
+
+struct LlBufs {
+    float *tvec, *dout, *score, *dx, *x0, *v0;
+    double *acc, *d0;
+};
 int ll_buffers(fd_ctx* ctx, int B, size_t n, bool heun, LlBufs* o) {
-    auto fl = [](size_t k) { return fd_ws::padded(k * sizeof(float)); };
-    if (int rc = ll_grow(ctx, fl(B) + (heun ? 5 : 3) * fl(n) + 2 * fd_ws::padded((size_t)B * sizeof(double)))) return rc;
-    char* p = (char*)ctx->ll_buf;
-    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-    o->tvec = (float*)take(fl(B));
-    o->dout = (float*)take(fl(n));
-    o->score = (float*)take(fl(n));
-    o->dx = (float*)take(fl(n));
-    o->x0 = heun ? (float*)take(fl(n)) : nullptr;
-    o->v0 = heun ? (float*)take(fl(n)) : nullptr;
-    o->acc = (double*)take(fd_ws::padded((size_t)B * sizeof(double)));
-    o->d0 = (double*)take(fd_ws::padded((size_t)B * sizeof(double)));
-    return FD_OK;
+    return ll_carve(ctx, [&](auto take) {
+        o->tvec = (float*)take(B * sizeof(float));
+        o->dout = (float*)take(n * sizeof(float));
+        o->score = (float*)take(n * sizeof(float));
+        o->dx = (float*)take(n * sizeof(float));
+        o->x0 = heun ? (float*)take(n * sizeof(float)) : nullptr;
+        o->v0 = heun ? (float*)take(n * sizeof(float)) : nullptr;
+        o->acc = (double*)take(B * sizeof(double));
+        o->d0 = (double*)take(B * sizeof(double));
+    });
 }
 
 // restores the model's training arithmetic when the run returns
@@ -134,6 +133,18 @@ struct TrainModeScope {
     ~TrainModeScope() { m->train_mode = saved; }
 };
 
+// The frame of both runs around body(): the evaluations run in the training arithmetic (bf16: the bf16 training kernels where the
+// model has them, else -- other backbones, widths -- the exact-f32 ones), and dout = G^2 e is built first
+template <class Body>
+int ll_frame(fd_score* m, int mode, const float* G, const float* probes, float* dout, int B, hipStream_t s, Body body) {
+    const bool bf16 = mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && fd_train_bf16_supported(m);
+    TrainModeScope tm(m, bf16 ? FD_MODE_BF16 : FD_MODE_F32);
+    const int T = m->d.max_len, C = m->d.n_channels;
+    const size_t n = (size_t)B * T * C;
+    const unsigned ew = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)m->ctx->num_cu * 16);
+    hipLaunchKernelGGL(k_ll_dout, dim3(ew), dim3(kBlock), 0, s, G, probes, dout, n, T, C);
+    return body();
+}
 
 // ---------------------------------------------------------------- adaptive integration (Dormand-Prince 5(4), scipy's RK45)
 // Each row b is one ODE on the augmented state y_b = [x_b (T*C values), acc_b] from t0 to t_bound:
@@ -429,21 +440,17 @@ struct RkBufs {
     int* count;
 };
 int rk_buffers(fd_ctx* ctx, int B, size_t n, int gcap, RkBufs* o) {
-    auto fl = [](size_t k) { return fd_ws::padded(k * sizeof(float)); };
-    const size_t rows = fd_ws::padded((size_t)B * sizeof(RkRow)), grid = fd_ws::padded((size_t)B * gcap * sizeof(double));
-    if (int rc = ll_grow(ctx, fl(B) + 11 * fl(n) + rows + grid + fd_ws::padded(sizeof(int)))) return rc;
-    char* p = (char*)ctx->ll_buf;
-    auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
-    o->tvec = (float*)take(fl(B));
-    o->dout = (float*)take(fl(n));
-    o->score = (float*)take(fl(n));
-    o->dx = (float*)take(fl(n));
-    o->xin = (float*)take(fl(n));
-    o->K = (float*)take(7 * fl(n));
-    o->row = (RkRow*)take(rows);
-    o->grid = (double*)take(grid);
-    o->count = (int*)take(fd_ws::padded(sizeof(int)));
-    return FD_OK;
+    return ll_carve(ctx, [&](auto take) {
+        o->tvec = (float*)take(B * sizeof(float));
+        o->dout = (float*)take(n * sizeof(float));
+        o->score = (float*)take(n * sizeof(float));
+        o->dx = (float*)take(n * sizeof(float));
+        o->xin = (float*)take(n * sizeof(float));
+        o->K = (float*)take(7 * fd_ws::padded(n * sizeof(float)));
+        o->row = (RkRow*)take(B * sizeof(RkRow));
+        o->grid = (double*)take((size_t)B * gcap * sizeof(double));
+        o->count = (int*)take(sizeof(int));
+    });
 }
 
 // the two completion events of the host loop (destroyed on every return)
@@ -471,48 +478,38 @@ extern "C" int fd_prior_logp(fd_ctx* ctx, const fd_sde_params* sde, const float*
 
 extern "C" int fd_likelihood_run(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
                                  float* x, const float* probes, float* score_div, int B, int mode, void* stream) {
-    if (!m) return FD_ERR_ARG;
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_likelihood_run")) return rc;
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, sde && G && timesteps && x && probes && score_div, "fd_likelihood_run: null pointer");
-    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_likelihood_run: unknown SDE kind %d", sde->kind);
-    FD_REQUIRE(ctx, n_steps > 0 && B > 0, "fd_likelihood_run: n_steps=%d B=%d", n_steps, B);
+    FD_REQUIRE(ctx, G && timesteps && x && probes && score_div, "fd_likelihood_run: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_likelihood_run: n_steps=%d", n_steps);
     FD_REQUIRE(ctx, solver == 0 || solver == 1, "fd_likelihood_run: solver %d (0 Euler, 1 Heun)", solver);
-    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_likelihood_run: unknown mode %d", mode);
     FD_REQUIRE(ctx, (double)timesteps[1] > (double)timesteps[0], "fd_likelihood_run: the grid must increase (data -> latents)");
-    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_likelihood_run: call fd_score_prepare first");
     std::vector<fd_ode_step_coef> rows;
     if (int rc = fd_ode_table(ctx, sde, timesteps, n_steps, solver, &rows)) return rc;
-    // bf16: the bf16 training kernels where the model has them, else (other backbones, widths) the exact-f32 ones
-    const bool bf16 = mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && fd_train_bf16_supported(m);
-    TrainModeScope tm(m, bf16 ? FD_MODE_BF16 : FD_MODE_F32);
     hipStream_t s = (hipStream_t)stream;
     const int T = m->d.max_len, C = m->d.n_channels;
-    const size_t n = (size_t)B * T * C;
     LlBufs b;
-    if (int rc = ll_buffers(ctx, B, n, solver == 1, &b)) return rc;
-    const unsigned ew = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)ctx->num_cu * 16);
-    hipLaunchKernelGGL(k_ll_dout, dim3(ew), dim3(kBlock), 0, s, G, probes, b.dout, n, T, C);
-    FD_HIP(ctx, hipMemsetAsync(b.acc, 0, (size_t)B * sizeof(double), s));
-    for (const fd_ode_step_coef& c : rows) {
-        hipLaunchKernelGGL(k_ll_fill, dim3((B + kBlock - 1) / kBlock), dim3(kBlock), 0, s, b.tvec, B, c.t);
-        if (int rc = fd_score_forward_train(m, x, b.tvec, b.score, B, 0.f, 0, 0, s)) return rc;
-        if (int rc = fd_score_input_vjp(m, b.dout, b.dx, s)) return rc;
-        hipLaunchKernelGGL(k_ll_stage, dim3(B), dim3(kBlock), 0, s, G, x, b.score, b.dx, probes, b.x0, b.v0, b.acc, b.d0, score_div, T,
-                           C, c);
-        FD_LAUNCH_CHECK(ctx);
-    }
-    return FD_OK;
+    if (int rc = ll_buffers(ctx, B, (size_t)B * T * C, solver == 1, &b)) return rc;
+    return ll_frame(m, mode, G, probes, b.dout, B, s, [&] {
+        FD_HIP(ctx, hipMemsetAsync(b.acc, 0, (size_t)B * sizeof(double), s));
+        for (const fd_ode_step_coef& c : rows) {
+            fd_fill(b.tvec, B, c.t, s);
+            if (int rc = fd_score_forward_train(m, x, b.tvec, b.score, B, 0.f, 0, 0, s)) return rc;
+            if (int rc = fd_score_input_vjp(m, b.dout, b.dx, s)) return rc;
+            hipLaunchKernelGGL(k_ll_stage, dim3(B), dim3(kBlock), 0, s, G, x, b.score, b.dx, probes, b.x0, b.v0, b.acc, b.d0, score_div,
+                               T, C, c);
+            FD_LAUNCH_CHECK(ctx);
+        }
+        return (int)FD_OK;
+    });
 }
 
 extern "C" int fd_likelihood_run_adaptive(fd_score* m, const fd_sde_params* sde, const float* G, double t0, double t1, double rtol,
                                           double atol, int max_evals, float* x, const float* probes, double* div_out, int* nfe_out,
                                           int* status_out, double* grid_out, int grid_cap, int B, int mode, void* stream) {
-    if (!m) return FD_ERR_ARG;
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_likelihood_run_adaptive")) return rc;
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, sde && G && x && probes && div_out && nfe_out && status_out, "fd_likelihood_run_adaptive: null pointer");
-    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_likelihood_run_adaptive: unknown SDE kind %d", sde->kind);
-    FD_REQUIRE(ctx, B > 0, "fd_likelihood_run_adaptive: B=%d", B);
-    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_likelihood_run_adaptive: unknown mode %d", mode);
+    FD_REQUIRE(ctx, G && x && probes && div_out && nfe_out && status_out, "fd_likelihood_run_adaptive: null pointer");
     FD_REQUIRE(ctx, std::isfinite(t0) && std::isfinite(t1) && t1 > t0, "fd_likelihood_run_adaptive: need finite t0 < t1 (%g, %g)",
                t0, t1);
     FD_REQUIRE(ctx, std::isfinite(rtol) && std::isfinite(atol) && rtol > 0 && atol > 0,
@@ -521,9 +518,6 @@ extern "C" int fd_likelihood_run_adaptive(fd_score* m, const fd_sde_params* sde,
     const int max_attempts = (max_evals - 2) / 6, gcap = 1 + max_attempts;
     FD_REQUIRE(ctx, !grid_out || grid_cap >= gcap, "fd_likelihood_run_adaptive: grid_cap=%d < 1 + (max_evals - 2) / 6 = %d",
                grid_cap, gcap);
-    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_likelihood_run_adaptive: call fd_score_prepare first");
-    const bool bf16 = mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && fd_train_bf16_supported(m);
-    TrainModeScope tm(m, bf16 ? FD_MODE_BF16 : FD_MODE_F32);
     hipStream_t s = (hipStream_t)stream;
     const int T = m->d.max_len, C = m->d.n_channels;
     const size_t n = (size_t)B * T * C;
@@ -534,37 +528,38 @@ extern "C" int fd_likelihood_run_adaptive(fd_score* m, const fd_sde_params* sde,
     for (hipEvent_t& e : ev.e) FD_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
 
     RkArgs a{G, x, b.xin, b.score, b.dx, probes, b.K, b.tvec, b.row, b.grid, n, T, C, gcap, max_evals, *sde, t1, rtol, atol, 0};
-    const unsigned ew = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)ctx->num_cu * 16);
-    hipLaunchKernelGGL(k_ll_dout, dim3(ew), dim3(kBlock), 0, s, G, probes, b.dout, n, T, C);
-    hipLaunchKernelGGL(k_ll_rk_init, dim3(B), dim3(kBlock), 0, s, a, t0);
-    FD_LAUNCH_CHECK(ctx);
-    auto eval = [&](int stage) {
-        if (int rc = fd_score_forward_train(m, b.xin, b.tvec, b.score, B, 0.f, 0, 0, s)) return rc;
-        if (int rc = fd_score_input_vjp(m, b.dout, b.dx, s)) return rc;
-        a.stage = stage;
-        hipLaunchKernelGGL(k_ll_rk_stage, dim3(B), dim3(kBlock), 0, s, a);
+    return ll_frame(m, mode, G, probes, b.dout, B, s, [&] {
+        hipLaunchKernelGGL(k_ll_rk_init, dim3(B), dim3(kBlock), 0, s, a, t0);
+        FD_LAUNCH_CHECK(ctx);
+        auto eval = [&](int stage) {
+            if (int rc = fd_score_forward_train(m, b.xin, b.tvec, b.score, B, 0.f, 0, 0, s)) return rc;
+            if (int rc = fd_score_input_vjp(m, b.dout, b.dx, s)) return rc;
+            a.stage = stage;
+            hipLaunchKernelGGL(k_ll_rk_stage, dim3(B), dim3(kBlock), 0, s, a);
+            FD_LAUNCH_CHECK(ctx);
+            return (int)FD_OK;
+        };
+        if (int rc = eval(RK_INIT0)) return rc;
+        if (int rc = eval(RK_INIT1)) return rc;
+        // Attempt k (6 evaluations) ends with the count of the rows still running, copied to host word k % 2 and marked by event
+        // k % 2.  The host reads attempt k's count once attempt k + 1 is queued: the device never waits on the host, and at most
+        // one attempt runs after the last row froze.  Every row freezes within max_attempts attempts (an attempt past max_evals is
+        // not started), so the loop needs no other bound.
+        for (int k = 0; k < max_attempts; ++k) {
+            for (int st = 1; st <= RK_FINAL; ++st)
+                if (int rc = eval(st)) return rc;
+            hipLaunchKernelGGL(k_ll_rk_count, dim3(1), dim3(kBlock), 0, s, b.row, B, b.count);
+            FD_LAUNCH_CHECK(ctx);
+            FD_HIP(ctx, hipMemcpyAsync(ctx->ll_host + (k & 1), b.count, sizeof(int), hipMemcpyDeviceToHost, s));
+            FD_HIP(ctx, hipEventRecord(ev.e[k & 1], s));
+            if (k > 0) {
+                FD_HIP(ctx, hipEventSynchronize(ev.e[(k - 1) & 1]));
+                if (ctx->ll_host[(k - 1) & 1] == 0) break;
+            }
+        }
+        hipLaunchKernelGGL(k_ll_rk_out, dim3(B), dim3(kBlock), 0, s, b.row, b.grid, gcap, div_out, nfe_out, status_out, grid_out,
+                           grid_cap);
         FD_LAUNCH_CHECK(ctx);
         return (int)FD_OK;
-    };
-    if (int rc = eval(RK_INIT0)) return rc;
-    if (int rc = eval(RK_INIT1)) return rc;
-    // Attempt k (6 evaluations) ends with the count of the rows still running, copied to host word k % 2 and marked by event
-    // k % 2.  The host reads attempt k's count once attempt k + 1 is queued: the device never waits on the host, and at most one
-    // attempt runs after the last row froze.  Every row freezes within max_attempts attempts (an attempt past max_evals is not
-    // started), so the loop needs no other bound.
-    for (int k = 0; k < max_attempts; ++k) {
-        for (int st = 1; st <= RK_FINAL; ++st)
-            if (int rc = eval(st)) return rc;
-        hipLaunchKernelGGL(k_ll_rk_count, dim3(1), dim3(kBlock), 0, s, b.row, B, b.count);
-        FD_LAUNCH_CHECK(ctx);
-        FD_HIP(ctx, hipMemcpyAsync(ctx->ll_host + (k & 1), b.count, sizeof(int), hipMemcpyDeviceToHost, s));
-        FD_HIP(ctx, hipEventRecord(ev.e[k & 1], s));
-        if (k > 0) {
-            FD_HIP(ctx, hipEventSynchronize(ev.e[(k - 1) & 1]));
-            if (ctx->ll_host[(k - 1) & 1] == 0) break;
-        }
-    }
-    hipLaunchKernelGGL(k_ll_rk_out, dim3(B), dim3(kBlock), 0, s, b.row, b.grid, gcap, div_out, nfe_out, status_out, grid_out, grid_cap);
-    FD_LAUNCH_CHECK(ctx);
-    return FD_OK;
+    });
 }

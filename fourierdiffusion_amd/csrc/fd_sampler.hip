@@ -21,9 +21,34 @@ __global__ __launch_bounds__(256) void k_fill_steps(float* __restrict__ p, const
 }
 constexpr size_t kMaxStepTable = (size_t)16 << 20;     // floats: beyond this (n_steps * B) the t vector is refilled every step
 
-// reserves `fwd + own` (+ the step table) and returns the t vector of step 0 and its stride between steps (0: refill per step)
-int step_table(fd_ctx* ctx, size_t fwd, size_t own, const float* timesteps, int n_steps, int B, hipStream_t s, float** tvec,
-               size_t* stride) {
+// The fused loop forms (fd_score_bf16.hip) of the bf16 transformer, in order: the persistent kernel, then the layer form.
+// FD_ERR_UNSUPPORTED when neither serves the model (or FDIFF_SAMPLER_STEPWISE asks for per-step launches; tests compare the two):
+// the caller then runs step by step.
+template <class Mega, class Layers>
+int run_fused(const fd_score* m, int mode, Mega mega, Layers layers) {
+    if (mode != FD_MODE_BF16 || m->backbone != FD_BACKBONE_TRANSFORMER || getenv("FDIFF_SAMPLER_STEPWISE")) return FD_ERR_UNSUPPORTED;
+    const int rc = mega();
+    return rc != FD_ERR_UNSUPPORTED ? rc : layers();
+}
+}  // namespace
+
+int fd_loop_check(fd_score* m, const fd_sde_params* sde, int B, int mode, const char* who) {
+    if (!m) return FD_ERR_ARG;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, sde, "%s: null pointer", who);
+    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "%s: unknown SDE kind %d", who, sde->kind);
+    FD_REQUIRE(ctx, B > 0, "%s: B=%d", who, B);
+    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "%s: unknown mode %d", who, mode);
+    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "%s: call fd_score_prepare first", who);
+    return FD_OK;
+}
+
+size_t fd_loop_fwd_workspace(const fd_score* m, int B) {
+    return (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
+}
+
+int fd_step_table(fd_ctx* ctx, size_t fwd, size_t own, const float* timesteps, int n_steps, int B, hipStream_t s, float** tvec,
+                  size_t* stride) {
     const size_t nt = (size_t)n_steps * B;
     const bool table = nt <= kMaxStepTable && !getenv("FDIFF_SAMPLER_FILL_PER_STEP");
     const size_t extra = table ? fd_ws::padded(nt * sizeof(float)) + fd_ws::padded((size_t)n_steps * sizeof(float))
@@ -39,7 +64,10 @@ int step_table(fd_ctx* ctx, size_t fwd, size_t own, const float* timesteps, int 
     }
     return FD_OK;
 }
-}  // namespace
+
+void fd_fill(float* p, int n, float v, hipStream_t s) {
+    hipLaunchKernelGGL(k_fill, dim3((n + 255) / 256), dim3(256), 0, s, p, n, v);
+}
 
 int fd_sampler_run_mega(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
                         float dt, float* x, const float* z_steps, uint64_t seed, uint64_t offset, int B,
@@ -50,39 +78,29 @@ int fd_sampler_run_layers(fd_score* m, const fd_sde_params* sde, const float* G,
 extern "C" int fd_sampler_run(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
                               int n_steps, float dt, float* x, const float* z_steps, uint64_t seed, uint64_t offset,
                               int B, int mode, void* stream) {
-    if (!m) return FD_ERR_ARG;
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run")) return rc;
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, sde && G && timesteps && x, "fd_sampler_run: null pointer");
-    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_sampler_run: unknown SDE kind %d", sde->kind);
-    FD_REQUIRE(ctx, n_steps > 0 && B > 0, "fd_sampler_run: n_steps=%d B=%d", n_steps, B);
+    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run: n_steps=%d", n_steps);
     FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run: step size must be > 0 (sde.py:158)");
-    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_sampler_run: call fd_score_prepare first");
     hipStream_t s = (hipStream_t)stream;
-    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_sampler_run: unknown mode %d", mode);
-    if (mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && !getenv("FDIFF_SAMPLER_STEPWISE")) {   // (switch: per-step launches; tests compare the two)
-        const int rc = fd_sampler_run_mega(m, sde, G, timesteps, n_steps, dt, x, z_steps, seed, offset, B, s);
-        if (rc != FD_ERR_UNSUPPORTED) return rc;     // ran (or failed loudly); else: step-by-step fallback below
-    }
-    if (mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && !getenv("FDIFF_SAMPLER_STEPWISE")) {
-        // same model family beyond the persistent kernel's length limit: layer launches + one fused launch per step
-        const int rc = fd_sampler_run_layers(m, sde, G, timesteps, n_steps, dt, x, z_steps, seed, offset, B, s);
-        if (rc != FD_ERR_UNSUPPORTED) return rc;
-    }
+    const int rc_fused = run_fused(
+        m, mode, [&] { return fd_sampler_run_mega(m, sde, G, timesteps, n_steps, dt, x, z_steps, seed, offset, B, s); },
+        [&] { return fd_sampler_run_layers(m, sde, G, timesteps, n_steps, dt, x, z_steps, seed, offset, B, s); });
+    if (rc_fused != FD_ERR_UNSUPPORTED) return rc_fused;
 
     const int T = m->d.max_len, C = m->d.n_channels;
     const size_t n = (size_t)B * T * C;
-    const size_t fwd = (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
-    const size_t own = fd_ws::padded(n * sizeof(float));
+    const size_t fwd = fd_loop_fwd_workspace(m, B);
     float* tvec0 = nullptr;
     size_t tstride = 0;
-    if (int rc = step_table(ctx, fwd, own, timesteps, n_steps, B, s, &tvec0, &tstride)) return rc;
+    if (int rc = fd_step_table(ctx, fwd, fd_ws::padded(n * sizeof(float)), timesteps, n_steps, B, s, &tvec0, &tstride)) return rc;
     float* score = (float*)((char*)ctx->ws + fwd);
     const uint64_t per_step = (uint64_t)((n + 3) / 4);
     for (int i = 0; i < n_steps; ++i) {
         float* tvec = tvec0 + (size_t)i * tstride;
-        if (!tstride) hipLaunchKernelGGL(k_fill, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, timesteps[i]);
-        const int rc_f = fd_score_forward_any(m, x, tvec, score, B, mode, s);
-        if (rc_f) return rc_f;
+        if (!tstride) fd_fill(tvec, B, timesteps[i], s);
+        if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
         const float* z = z_steps ? z_steps + (size_t)i * n : nullptr;
         if (int rc = fd_sde_step(ctx, sde, G, x, score, z, seed, offset + (uint64_t)i * per_step,
                                  (double)timesteps[i], dt, x, B, T, C, stream))
@@ -96,43 +114,34 @@ extern "C" int fd_sampler_run(fd_score* m, const fd_sde_params* sde, const float
 // launch per evaluation, the Heun state in two (B,T,C) workspace buffers behind the score.
 extern "C" int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
                                   int solver, float* x, int B, int mode, void* stream) {
-    if (!m) return FD_ERR_ARG;
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_ode")) return rc;
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, sde && G && timesteps && x, "fd_sampler_run_ode: null pointer");
-    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_sampler_run_ode: unknown SDE kind %d", sde->kind);
-    FD_REQUIRE(ctx, n_steps > 0 && B > 0, "fd_sampler_run_ode: n_steps=%d B=%d", n_steps, B);
+    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_ode: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_ode: n_steps=%d", n_steps);
     FD_REQUIRE(ctx, solver == 0 || solver == 1, "fd_sampler_run_ode: solver %d (0 Euler, 1 Heun)", solver);
-    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_sampler_run_ode: unknown mode %d", mode);
-    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_sampler_run_ode: call fd_score_prepare first");
     std::vector<fd_ode_step_coef> rows;
     if (int rc = fd_ode_table(ctx, sde, timesteps, n_steps, solver, &rows)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool fused = mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && !getenv("FDIFF_SAMPLER_STEPWISE");
-    if (fused) {
-        const int rc = fd_sampler_run_ode_mega(m, rows, G, x, B, s);
-        if (rc != FD_ERR_UNSUPPORTED) return rc;
-    }
-    if (fused) {
-        const int rc = fd_sampler_run_ode_layers(m, rows, G, x, B, s);
-        if (rc != FD_ERR_UNSUPPORTED) return rc;
-    }
+    const int rc_fused = run_fused(m, mode, [&] { return fd_sampler_run_ode_mega(m, rows, G, x, B, s); },
+                                   [&] { return fd_sampler_run_ode_layers(m, rows, G, x, B, s); });
+    if (rc_fused != FD_ERR_UNSUPPORTED) return rc_fused;
 
     const int T = m->d.max_len, C = m->d.n_channels;
     const int n_eval = (int)rows.size();
     const size_t n = (size_t)B * T * C;
-    const size_t fwd = (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
+    const size_t fwd = fd_loop_fwd_workspace(m, B);
     const size_t buf = fd_ws::padded(n * sizeof(float));
     std::vector<float> t_eval(n_eval);
     for (int k = 0; k < n_eval; ++k) t_eval[k] = rows[k].t;
     float* tvec0 = nullptr;
     size_t tstride = 0;
-    if (int rc = step_table(ctx, fwd, (solver ? 3 : 1) * buf, t_eval.data(), n_eval, B, s, &tvec0, &tstride)) return rc;
+    if (int rc = fd_step_table(ctx, fwd, (solver ? 3 : 1) * buf, t_eval.data(), n_eval, B, s, &tvec0, &tstride)) return rc;
     float* score = (float*)((char*)ctx->ws + fwd);
     float* x0 = solver ? (float*)((char*)ctx->ws + fwd + buf) : nullptr;
     float* v0 = solver ? (float*)((char*)ctx->ws + fwd + 2 * buf) : nullptr;
     for (int k = 0; k < n_eval; ++k) {
         float* tvec = tvec0 + (size_t)k * tstride;
-        if (!tstride) hipLaunchKernelGGL(k_fill, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, t_eval[k]);
+        if (!tstride) fd_fill(tvec, B, t_eval[k], s);
         if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
         if (int rc = fd_ode_stage(ctx, G, x, score, x0, v0, rows[k], B, T, C, s)) return rc;
     }
@@ -145,29 +154,25 @@ extern "C" int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const f
 extern "C" int fd_sampler_run_pc(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
                                  float dt, float* x, const float* z_steps, const float* zc_steps, int n_corr, float snr,
                                  uint64_t seed, uint64_t offset, int B, int mode, void* stream) {
-    if (!m) return FD_ERR_ARG;
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_pc")) return rc;
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, sde && G && timesteps && x, "fd_sampler_run_pc: null pointer");
-    FD_REQUIRE(ctx, sde->kind == 0 || sde->kind == 1, "fd_sampler_run_pc: unknown SDE kind %d", sde->kind);
-    FD_REQUIRE(ctx, n_steps > 0 && B > 0 && n_corr >= 0, "fd_sampler_run_pc: n_steps=%d B=%d n_corr=%d", n_steps, B, n_corr);
+    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_pc: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0 && n_corr >= 0, "fd_sampler_run_pc: n_steps=%d n_corr=%d", n_steps, n_corr);
     FD_REQUIRE(ctx, dt > 0.f && (n_corr == 0 || snr > 0.f), "fd_sampler_run_pc: dt=%f snr=%f", dt, snr);
-    FD_REQUIRE(ctx, mode == FD_MODE_F32 || mode == FD_MODE_BF16, "fd_sampler_run_pc: unknown mode %d", mode);
-    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_sampler_run_pc: call fd_score_prepare first");
     hipStream_t s = (hipStream_t)stream;
     const int T = m->d.max_len, C = m->d.n_channels;
     const size_t n = (size_t)B * T * C;
-    const size_t fwd = (m->backbone != FD_BACKBONE_TRANSFORMER) ? fd_bb_workspace(m, B, false) : fd_score_f32_workspace(m, B, false);
-    const size_t own = fd_ws::padded(n * sizeof(float));
+    const size_t fwd = fd_loop_fwd_workspace(m, B);
     float* tvec0 = nullptr;
     size_t tstride = 0;
-    if (int rc = step_table(ctx, fwd, own, timesteps, n_steps, B, s, &tvec0, &tstride)) return rc;
+    if (int rc = fd_step_table(ctx, fwd, fd_ws::padded(n * sizeof(float)), timesteps, n_steps, B, s, &tvec0, &tstride)) return rc;
     float* score = (float*)((char*)ctx->ws + fwd);
     const uint64_t per_step = (uint64_t)((n + 3) / 4);
     // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run); corrector noise behind them
     const uint64_t corr_base = offset + (uint64_t)n_steps * per_step;
     for (int i = 0; i < n_steps; ++i) {
         float* tvec = tvec0 + (size_t)i * tstride;
-        if (!tstride) hipLaunchKernelGGL(k_fill, dim3((B + 255) / 256), dim3(256), 0, s, tvec, B, timesteps[i]);
+        if (!tstride) fd_fill(tvec, B, timesteps[i], s);
         for (int k = 0; k < n_corr; ++k) {
             if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
             // alpha_t of Song et al.: 1 - beta(t) dt for the VP-SDE, 1 for the VE-SDE

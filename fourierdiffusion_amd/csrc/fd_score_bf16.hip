@@ -1236,6 +1236,11 @@ static LayerBufs carve_layer_bufs(const fd_score* m, int B, fd_ws& ws) {
     return lb;
 }
 static int bf16_layer_stack(fd_score* m, int B, LayerBufs& lb, hipStream_t s);
+// FDIFF_ATT_XROWS (default on): k_ffn_ln hands the layer output to the next layer's attention as bf16 rows (bf16_layer_stack)
+static bool att_xrows_on() {
+    static const bool on = !(getenv("FDIFF_ATT_XROWS") && atoi(getenv("FDIFF_ATT_XROWS")) == 0);
+    return on;
+}
 
 int fd_score_forward_bf16(fd_score* m, const float* x, const float* t, float* out, int B, hipStream_t s) {
     fd_ctx* ctx = m->ctx;
@@ -1342,8 +1347,7 @@ static int bf16_layer_stack(fd_score* m, int B, LayerBufs& lb, hipStream_t s) {
                                 (double)M * (2.0 * D * D + 4.0 * D * m->d.dim_ff));
             // the layer output also as bf16 rows for the next layer's attention staging (not behind the last layer: its reader is the
             // unembedding; FDIFF_ATT_XROWS=0 keeps the fp32 staging for A/B runs)
-            static const bool xrows_on = !(getenv("FDIFF_ATT_XROWS") && atoi(getenv("FDIFF_ATT_XROWS")) == 0);
-            const bool rows_next = xrows_on && lb.xrb && i + 1 < L && imq->mega && hd <= 7;
+            const bool rows_next = att_xrows_on() && lb.xrb && i + 1 < L && imq->mega && hd <= 7;
             if (int rc = run_ffn(m, nullptr, h1, i, M, s, att, h0, att_bf16, rows_next ? lb.xrb : nullptr)) return rc;
             lb.xrb_ok = rows_next;
             std::swap(h0, h1);
@@ -1559,258 +1563,55 @@ static void launch_step_fuse(const fd_bf16_images* im, const StepFuseArgs& a, hi
     else hipLaunchKernelGGL((k_unembed_step_embed<1, 1, ODE>), grid, block, 0, s, a);
 }
 
-// fd_sampler_run's loop for the persistent kernel's model family when the persistent kernel itself does not fit (T > 256):
-// per diffusion step the 2 L layer launches + ONE launch for unembed / reverse-SDE step / next embedding.  Returns
-// FD_ERR_UNSUPPORTED (x untouched) when this model has no such path.
-int fd_sampler_run_layers(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt,
-                          float* x, const float* z_steps, uint64_t seed, uint64_t offset, int B, hipStream_t s) {
-    fd_ctx* ctx = m->ctx;
-    const fd_bf16_images* im = m->bf16;
-    if (!im || !im->supported || !im->mega || getenv("FDIFF_SAMPLER_UNFUSED_STEP")) return FD_ERR_UNSUPPORTED;
-    const bool k35 = im->ks1 == 3 && im->dt == 5, k24 = im->ks1 == 2 && im->dt == 4, k12 = im->ks1 == 1 && im->dt == 2,
-               k11 = im->ks1 == 1 && im->dt == 1;
-    if (!(k35 || k24 || k12 || k11) || m->d.n_channels > 40 || m->d.d_model % 4 != 0) return FD_ERR_UNSUPPORTED;
-    if (int rc = fd_bf16_refresh(m, s)) return rc;
-    const int T = m->d.max_len, C = m->d.n_channels, D = m->d.d_model;
-    const int M = B * T;
-    const size_t n = (size_t)M * C;
-    const size_t fwd = fd_score_f32_workspace(m, B, false);
-    const size_t tab_bytes = fd_ws::padded(sizeof(fd_sde_step_coef) * (size_t)n_steps);
-    const size_t temb_bytes = fd_ws::padded(sizeof(float) * (size_t)n_steps * D);
-    if (int rc = fd_ws_reserve(ctx, fwd + tab_bytes + temb_bytes)) return rc;
-    fd_ws ws(ctx);
-    LayerBufs lb = carve_layer_bufs(m, B, ws);
-    fd_sde_step_coef* tabd = reinterpret_cast<fd_sde_step_coef*>((char*)ctx->ws + fwd);
-    float* temb_table = reinterpret_cast<float*>((char*)ctx->ws + fwd + tab_bytes);
+// The SDE rows of the two fused forms: fd_sde_coef at every grid point, t kept for the time-embedding table
+static std::vector<fd_sde_step_coef> sde_rows(const fd_sde_params& sde, const float* timesteps, int n_steps, float dt) {
     std::vector<fd_sde_step_coef> tab(n_steps);
     for (int i = 0; i < n_steps; ++i) {
-        const SdeCoef c = fd_sde_coef(*sde, (double)timesteps[i], dt);
+        const SdeCoef c = fd_sde_coef(sde, (double)timesteps[i], dt);
         tab[i] = fd_sde_step_coef{c.a_x, c.g, c.dt, c.sqrt_dt, timesteps[i]};
     }
-    // pageable source: the runtime stages the copy before returning
-    FD_HIP(ctx, hipMemcpyAsync(tabd, tab.data(), sizeof(fd_sde_step_coef) * (size_t)n_steps, hipMemcpyHostToDevice, s));
-    {
-        fd_mega_params MP;
-        memset(&MP, 0, sizeof MP);
-        MP.params = m->params; MP.tW = m->tW; MP.td_w = m->td_w; MP.td_b = m->td_b; MP.D = D;
-        MP.steps = tabd; MP.nsteps = n_steps;
-        fd_mega_temb_table(MP, temb_table, s);
-    }
-    StepFuseArgs A{};
-    A.x = x; A.G = G; A.pos = m->params + m->pos;
-    A.img_unemb = im->mimg + im->off_unemb; A.img_emb = im->mimg + im->off_emb;
-    A.seed = seed; A.M = M; A.T = T; A.C = C; A.D = D; A.KSE = im->kse; A.CT = im->ct;
-    const unsigned long long per_step = (unsigned long long)((n + 3) / 4);
-    auto launch = [&](const StepFuseArgs& a) { launch_step_fuse<false>(im, a, s); };
-    // first step's embedding
-    static const bool xrows_on = !(getenv("FDIFF_ATT_XROWS") && atoi(getenv("FDIFF_ATT_XROWS")) == 0);
-    const bool rows0 = xrows_on && lb.xrb && m->d.num_layers > 0 && m->d.d_model / m->d.n_head <= 7 && (im->ks1 == 3 || im->ks1 == 2) &&
-                       im->kso == 3;      // (the layer stack's fused attention + k_ffn_ln path: its first attention reads the rows)
-    A.h = nullptr; A.hn = lb.h0; A.hn_rows = rows0 ? lb.xrb : nullptr; A.temb = temb_table; A.cf = tab[0];
-    launch(A);
-    lb.xrb_ok = rows0;
-    for (int i = 0; i < n_steps; ++i) {
-        if (int rc = bf16_layer_stack(m, B, lb, s)) return rc;
-        A.h = lb.h0;
-        A.hn = (i + 1 < n_steps) ? lb.h1 : nullptr;
-        A.hn_rows = (rows0 && i + 1 < n_steps) ? lb.xrb : nullptr;
-        A.temb = temb_table + (size_t)(i + 1 < n_steps ? i + 1 : i) * D;
-        A.z = z_steps ? z_steps + (size_t)i * n : nullptr;
-        A.cf = tab[i];
-        A.ctr0 = offset + (unsigned long long)i * per_step;
-        launch(A);
-        lb.xrb_ok = rows0 && i + 1 < n_steps;
-        std::swap(lb.h0, lb.h1);
-    }
-    FD_LAUNCH_CHECK(ctx);
-    return FD_OK;
+    return tab;
 }
 
-// Whole reverse-diffusion loop in the persistent kernel.  Returns FD_ERR_UNSUPPORTED (without touching x)
-// when the shape does not fit, so that fd_sampler_run can fall back to the step-by-step loop.
-int fd_sampler_run_mega(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
-                        float dt, float* x, const float* z_steps, uint64_t seed, uint64_t offset, int B,
-                        hipStream_t s) {
-    fd_ctx* ctx = m->ctx;
-    const MegaPlan pl = plan_mega(m, B);
-    if (!pl.ok || getenv("FDIFF_NO_MEGA")) return FD_ERR_UNSUPPORTED;
-    if (int rc = fd_bf16_refresh(m, s)) return rc;
-    const size_t tab_bytes = fd_ws::padded(sizeof(fd_sde_step_coef) * (size_t)n_steps);
-    const size_t temb_bytes = fd_ws::padded(sizeof(float) * (size_t)n_steps * m->d.d_model);
-    if (int rc = fd_ws_reserve(ctx, tab_bytes + temb_bytes)) return rc;
-    std::vector<fd_sde_step_coef> tab(n_steps);
-    for (int i = 0; i < n_steps; ++i) {
-        const SdeCoef c = fd_sde_coef(*sde, (double)timesteps[i], dt);
-        tab[i] = fd_sde_step_coef{c.a_x, c.g, c.dt, c.sqrt_dt, timesteps[i]};
-    }
-    // pageable source: the runtime stages the copy before returning, so `tab` may go out of scope
-    FD_HIP(ctx, hipMemcpyAsync(ctx->ws, tab.data(), sizeof(fd_sde_step_coef) * (size_t)n_steps, hipMemcpyHostToDevice, s));
-    fd_mega_params MP;
-    if (int rc = fill_mega_params(m, pl, B, MP)) return rc;
-    MP.mode = FD_MEGA_SAMPLE;
-    MP.nsteps = n_steps;
-    MP.x = x;
-    MP.G = G;
-    MP.steps = reinterpret_cast<const fd_sde_step_coef*>(ctx->ws);
-    MP.z_steps = z_steps;
-    MP.seed = seed;
-    MP.offset = offset;
-    MP.n_elem = (unsigned long long)B * m->d.max_len * m->d.n_channels;
-    MP.ctr_per_step = (MP.n_elem + 3) / 4;
-    if (!getenv("FDIFF_MEGA_NO_TEMB_TABLE")) {     // (switch: compute the time embedding inside the kernel every step, as in forward mode)
-        float* table = reinterpret_cast<float*>((char*)ctx->ws + tab_bytes);
-        fd_mega_temb_table(MP, table, s);
-        MP.temb_table = table;
-    }
-    if (getenv("FDIFF_MEGA_PROF")) {      // profiling aid: per-phase cycle breakdown of workgroup 0 / wave 0
-        const size_t nent = 8300;
-        unsigned long long* pb = nullptr;
-        FD_HIP(ctx, hipMalloc((void**)&pb, nent * 16));
-        FD_HIP(ctx, hipMemsetAsync(pb, 0xff, nent * 16, s));
-        MP.prof = pb;
-        int rc = fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
-        FD_HIP(ctx, hipStreamSynchronize(s));
-        std::vector<unsigned long long> hb(nent * 2);
-        FD_HIP(ctx, hipMemcpy(hb.data(), pb, nent * 16, hipMemcpyDeviceToHost));
-        (void)hipFree(pb);
-        static const char* names[] = {"step begin->", "time-embed+embed", "QKV weight DMA wait", "K/V projection", "att: last epilogue + barrier",
-                                      "out-proj + LN1", "FFN loop", "FFN combine + LN2", "unembed + SDE",
-                                      " att: prev epilogue/loop", " att: Q proj + frag loads", " att: pass 1 (max)", " att: softmax stats", " att: pass 2 + PV"};
-        double acc[14] = {0};
-        unsigned long long prev = 0, first = 0, last = 0;
-        size_t n = 0;
-        for (; n < 4000 && hb[2 * n] != ~0ull; ++n) {
-            const int ph = (int)hb[2 * n];
-            const unsigned long long tm = hb[2 * n + 1];
-            if (n == 0) first = tm;
-            else if (ph >= 1 && ph <= 13) acc[ph] += (double)(tm - prev);   // (ph == 0 intervals = unprofiled steps)
-            prev = tm;
-            last = tm;
-        }
-        for (size_t i = 4000; i < 4032 && i < nent; ++i)
-            if (hb[2 * i] != ~0ull)
-                fprintf(stderr, "[fdiff prof]   unit loop, group %zu wave %zu: %llu cycles\n", (i - 4000) / 8, (i - 4000) % 8, hb[2 * i + 1]);
-        {   // residency of every workgroup: start / end (100 MHz wall clock), XCC and CU it ran on
-            unsigned long long t0 = ~0ull, t1 = 0;
-            const int ng = std::min(pl.grid, 2048);
-            for (int i = 0; i < ng; ++i) { t0 = std::min(t0, hb[2 * (4100 + i)]); t1 = std::max(t1, hb[2 * (4100 + i) + 1]); }
-            int late = 0;
-            std::map<unsigned long long, int> per_cu;
-            for (int i = 0; i < ng; ++i) {
-                const unsigned long long st = hb[2 * (4100 + i)] - t0;
-                if (st > (t1 - t0) / 10) ++late;
-                const unsigned long long id = hb[2 * (4100 + 2048 + i)];
-                const unsigned hw = (unsigned)id, xcc = (unsigned)(id >> 32) & 0xf;
-                // HW_ID: [3:0] wave, [5:4] simd, [7:6] pipe, [11:8] cu, [12] sh, [15:13] se
-                const unsigned long long key = ((unsigned long long)xcc << 16) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 15);
-                per_cu[key]++;
-            }
-            std::vector<double> dur;
-            for (int i = 0; i < ng; ++i) dur.push_back((hb[2 * (4100 + i) + 1] - hb[2 * (4100 + i)]) / 1e5);
-            std::vector<double> sd = dur;
-            std::sort(sd.begin(), sd.end());
-            fprintf(stderr, "[fdiff prof] workgroup durations (ms): wg0 %.3f min %.3f p10 %.3f median %.3f p90 %.3f max %.3f\n", dur[0],
-                    sd.front(), sd[sd.size() / 10], sd[sd.size() / 2], sd[sd.size() * 9 / 10], sd.back());
-            int hist[8] = {0};
-            for (auto& kv : per_cu) hist[std::min(7, kv.second)]++;
-            fprintf(stderr, "[fdiff prof] %d workgroups, launch span %.3f ms, %d started after 10%% of the span; distinct CUs %zu, "
-                    "workgroups per CU histogram 1:%d 2:%d 3:%d 4+:%d\n", ng, (t1 - t0) / 1e5, late, per_cu.size(), hist[1], hist[2], hist[3],
-                    hist[4] + hist[5] + hist[6] + hist[7]);
-        }
-        {   // duration of every step (workgroup 0): shows drift / clock changes after the profiled first steps
-            unsigned long long pt = 0;
-            int k = 0;
-            for (size_t i = 0; i < n; ++i)
-                if (hb[2 * i] == 0) {
-                    if (pt && (k % 8 == 0)) fprintf(stderr, "[fdiff prof]   step %d: %llu cycles\n", k, hb[2 * i + 1] - pt);
-                    pt = hb[2 * i + 1];
-                    ++k;
-                }
-        }
-        int steps_seen = 0;
-        for (size_t i = 0; i < n; ++i) steps_seen += (hb[2 * i] == 0);
-        fprintf(stderr, "[fdiff prof] nw=%d S=%d npg=%d mt=%d rot=%d lds=%zu: %d steps, %.0f cycles/step\n", pl.nw, pl.S, pl.npg, pl.mt, pl.rot,
-                pl.lds, steps_seen, (double)(last - first) / std::max(1, steps_seen));
-        const int steps_prof = std::max(1, std::min(4, steps_seen));      // phases are recorded for the first 4 steps
-        double acc_all = 0;
-        for (int ph = 1; ph <= 13; ++ph) acc_all += acc[ph];
-        for (int ph = 1; ph <= 13; ++ph)
-            fprintf(stderr, "[fdiff prof]   %-22s %10.0f cycles/step  %5.1f%%\n", names[ph], acc[ph] / steps_prof,
-                    100.0 * acc[ph] / std::max(1.0, acc_all));
-        return rc;
-    }
-    {
-        // algorithmic flops of this launch: per series per forward x B x n_steps
-        const double T = m->d.max_len, D = m->d.d_model, F = m->d.dim_ff, C = m->d.n_channels, L = m->d.num_layers;
-        const double per_fwd = T * (L * (2 * D * 3 * D + 2 * D * D + 4 * D * F + 4 * T * D) + 4 * C * D) + 2 * D * D;
-        fd_prof_scope scope(ctx, s, "k_mega (persistent score-net + reverse-SDE loop)", per_fwd * B * n_steps);
-        if (ctx->prof_on) {
-            if (!ctx->prof_clk) FD_HIP(ctx, hipMalloc((void**)&ctx->prof_clk, 4 * sizeof(unsigned long long)));
-            FD_HIP(ctx, hipMemsetAsync(ctx->prof_clk, 0, 4 * sizeof(unsigned long long), s));
-            MP.clk_out = ctx->prof_clk;
-        }
-        return fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
-    }
-}
-
-// Probability-flow ODE loops of fd_sampler_run_ode (fd_ode.hip) in the two fused forms above: the device table holds one
-// fd_ode_step_coef per score evaluation (t where the SDE rows keep it: the time-embedding table is built from it unchanged), the
-// Heun state lives in two (B,T,C) workspace buffers behind it.  FD_ERR_UNSUPPORTED (x untouched) exactly where the SDE forms return it.
-static int ode_tables(fd_ctx* ctx, const fd_score* m, const std::vector<fd_ode_step_coef>& rows, size_t base, size_t n, hipStream_t s,
-                      fd_ode_step_coef** tabd, float** temb, float** x0, float** v0) {
+// Device tables of the two fused forms, reserved at ctx->ws + base: one row per score evaluation (fd_sde_step_coef, or the
+// layout-compatible fd_ode_step_coef: t where the SDE rows keep it, so the time-embedding table is built from either unchanged),
+// the time-embedding table (temb = false: not built, its space still reserved), and for Heun the two (B,T,C) state buffers.
+struct StepTables {
+    const fd_sde_step_coef* rows;
+    float *temb, *x0, *v0;
+};
+template <class Row>
+static int step_tables(fd_ctx* ctx, const fd_score* m, const std::vector<Row>& rows, size_t base, size_t n, bool heun, bool temb,
+                       hipStream_t s, StepTables* o) {
+    static_assert(sizeof(Row) == sizeof(fd_sde_step_coef), "rows share the layout of fd_sde_step_coef");
     const size_t ne = rows.size();
-    const size_t tab_bytes = fd_ws::padded(sizeof(fd_ode_step_coef) * ne);
+    const size_t tab_bytes = fd_ws::padded(sizeof(Row) * ne);
     const size_t temb_bytes = fd_ws::padded(sizeof(float) * ne * m->d.d_model);
     const size_t buf = fd_ws::padded(n * sizeof(float));
-    const bool heun = rows[0].stage != FD_ODE_EULER;
     if (int rc = fd_ws_reserve(ctx, base + tab_bytes + temb_bytes + (heun ? 2 * buf : 0))) return rc;
     char* p = (char*)ctx->ws + base;
-    *tabd = reinterpret_cast<fd_ode_step_coef*>(p);
-    *temb = reinterpret_cast<float*>(p + tab_bytes);
-    *x0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes) : nullptr;
-    *v0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes + buf) : nullptr;
-    // pageable source: the runtime stages the copy before returning
-    FD_HIP(ctx, hipMemcpyAsync(*tabd, rows.data(), sizeof(fd_ode_step_coef) * ne, hipMemcpyHostToDevice, s));
-    fd_mega_params MP;
-    memset(&MP, 0, sizeof MP);
-    MP.params = m->params; MP.tW = m->tW; MP.td_w = m->td_w; MP.td_b = m->td_b; MP.D = m->d.d_model;
-    MP.steps = reinterpret_cast<const fd_sde_step_coef*>(*tabd); MP.nsteps = (int)ne;
-    fd_mega_temb_table(MP, *temb, s);
+    o->rows = reinterpret_cast<const fd_sde_step_coef*>(p);
+    o->temb = temb ? reinterpret_cast<float*>(p + tab_bytes) : nullptr;
+    o->x0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes) : nullptr;
+    o->v0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes + buf) : nullptr;
+    // pageable source: the runtime stages the copy before returning, so `rows` may go out of scope
+    FD_HIP(ctx, hipMemcpyAsync(p, rows.data(), sizeof(Row) * ne, hipMemcpyHostToDevice, s));
+    if (temb) {
+        fd_mega_params MP;
+        memset(&MP, 0, sizeof MP);
+        MP.params = m->params; MP.tW = m->tW; MP.td_w = m->td_w; MP.td_b = m->td_b; MP.D = m->d.d_model;
+        MP.steps = o->rows; MP.nsteps = (int)ne;
+        fd_mega_temb_table(MP, o->temb, s);
+    }
     return FD_OK;
 }
 
-int fd_sampler_run_ode_mega(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
-    fd_ctx* ctx = m->ctx;
-    const MegaPlan pl = plan_mega(m, B);
-    if (!pl.ok || getenv("FDIFF_NO_MEGA")) return FD_ERR_UNSUPPORTED;
-    if (int rc = fd_bf16_refresh(m, s)) return rc;
-    const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
-    fd_ode_step_coef* tabd;
-    float *temb, *x0, *v0;
-    if (int rc = ode_tables(ctx, m, rows, 0, n, s, &tabd, &temb, &x0, &v0)) return rc;
-    fd_mega_params MP;
-    if (int rc = fill_mega_params(m, pl, B, MP)) return rc;
-    MP.mode = FD_MEGA_ODE;
-    MP.nsteps = (int)rows.size();
-    MP.x = x;
-    MP.G = G;
-    MP.steps = reinterpret_cast<const fd_sde_step_coef*>(tabd);
-    MP.temb_table = temb;
-    MP.ode_x0 = x0;
-    MP.ode_v0 = v0;
-    MP.n_elem = n;
-    const double T = m->d.max_len, D = m->d.d_model, F = m->d.dim_ff, C = m->d.n_channels, L = m->d.num_layers;
-    const double per_fwd = T * (L * (2 * D * 3 * D + 2 * D * D + 4 * D * F + 4 * T * D) + 4 * C * D) + 2 * D * D;
-    fd_prof_scope scope(ctx, s, "k_mega (persistent score-net + probability-flow ODE loop)", per_fwd * B * (double)rows.size());
-    if (ctx->prof_on) {
-        if (!ctx->prof_clk) FD_HIP(ctx, hipMalloc((void**)&ctx->prof_clk, 4 * sizeof(unsigned long long)));
-        FD_HIP(ctx, hipMemsetAsync(ctx->prof_clk, 0, 4 * sizeof(unsigned long long), s));
-        MP.clk_out = ctx->prof_clk;
-    }
-    return fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
-}
-
-int fd_sampler_run_ode_layers(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
+// The layer form of both loops, for the persistent kernel's model family when the persistent kernel itself does not fit (T > 256):
+// per score evaluation the 2 L layer launches + ONE launch for unembed / SDE step or ODE stage / next embedding.  Returns
+// FD_ERR_UNSUPPORTED (x untouched) when this model has no such path.  ODE: rows are fd_ode_step_coef, no noise is read.
+template <bool ODE, class Row>
+static int run_layers(fd_score* m, const std::vector<Row>& rows, const float* G, float* x, const float* z_steps, uint64_t seed,
+                      uint64_t offset, int B, hipStream_t s) {
     fd_ctx* ctx = m->ctx;
     const fd_bf16_images* im = m->bf16;
     if (!im || !im->supported || !im->mega || getenv("FDIFF_SAMPLER_UNFUSED_STEP")) return FD_ERR_UNSUPPORTED;
@@ -1821,36 +1622,200 @@ int fd_sampler_run_ode_layers(fd_score* m, const std::vector<fd_ode_step_coef>& 
     const int T = m->d.max_len, C = m->d.n_channels, D = m->d.d_model;
     const int M = B * T;
     const int ne = (int)rows.size();
-    const size_t fwd = fd_score_f32_workspace(m, B, false);
-    fd_ode_step_coef* tabd;
-    float *temb, *x0, *v0;
-    if (int rc = ode_tables(ctx, m, rows, fwd, (size_t)M * C, s, &tabd, &temb, &x0, &v0)) return rc;
+    const size_t n = (size_t)M * C;
+    bool heun = false;
+    if constexpr (ODE) heun = rows[0].stage != FD_ODE_EULER;
+    StepTables tb;
+    if (int rc = step_tables(ctx, m, rows, fd_score_f32_workspace(m, B, false), n, heun, true, s, &tb)) return rc;
     fd_ws ws(ctx);
     LayerBufs lb = carve_layer_bufs(m, B, ws);
     StepFuseArgs A{};
     A.x = x; A.G = G; A.pos = m->params + m->pos;
     A.img_unemb = im->mimg + im->off_unemb; A.img_emb = im->mimg + im->off_emb;
-    A.M = M; A.T = T; A.C = C; A.D = D; A.KSE = im->kse; A.CT = im->ct;
-    A.x0 = x0; A.v0 = v0;
-    static const bool xrows_on = !(getenv("FDIFF_ATT_XROWS") && atoi(getenv("FDIFF_ATT_XROWS")) == 0);
-    const bool rows0 = xrows_on && lb.xrb && m->d.num_layers > 0 && m->d.d_model / m->d.n_head <= 7 && (im->ks1 == 3 || im->ks1 == 2) &&
-                       im->kso == 3;      // (as fd_sampler_run_layers)
-    A.h = nullptr; A.hn = lb.h0; A.hn_rows = rows0 ? lb.xrb : nullptr; A.temb = temb;
-    launch_step_fuse<true>(im, A, s);      // first evaluation's embedding
+    A.seed = seed; A.M = M; A.T = T; A.C = C; A.D = D; A.KSE = im->kse; A.CT = im->ct;
+    A.x0 = tb.x0; A.v0 = tb.v0;
+    const unsigned long long per_step = (unsigned long long)((n + 3) / 4);
+    // the layer stack's fused attention + k_ffn_ln path: its first attention reads the rows
+    const bool rows0 = att_xrows_on() && lb.xrb && m->d.num_layers > 0 && m->d.d_model / m->d.n_head <= 7 &&
+                       (im->ks1 == 3 || im->ks1 == 2) && im->kso == 3;
+    A.h = nullptr; A.hn = lb.h0; A.hn_rows = rows0 ? lb.xrb : nullptr; A.temb = tb.temb;
+    launch_step_fuse<ODE>(im, A, s);      // first evaluation's embedding
     lb.xrb_ok = rows0;
     for (int k = 0; k < ne; ++k) {
         if (int rc = bf16_layer_stack(m, B, lb, s)) return rc;
         A.h = lb.h0;
         A.hn = (k + 1 < ne) ? lb.h1 : nullptr;
         A.hn_rows = (rows0 && k + 1 < ne) ? lb.xrb : nullptr;
-        A.temb = temb + (size_t)(k + 1 < ne ? k + 1 : k) * D;
-        A.oc = rows[k];
-        launch_step_fuse<true>(im, A, s);
+        A.temb = tb.temb + (size_t)(k + 1 < ne ? k + 1 : k) * D;
+        if constexpr (ODE) {
+            A.oc = rows[k];
+        } else {
+            A.cf = rows[k];
+            A.z = z_steps ? z_steps + (size_t)k * n : nullptr;
+            A.ctr0 = offset + (unsigned long long)k * per_step;
+        }
+        launch_step_fuse<ODE>(im, A, s);
         lb.xrb_ok = rows0 && k + 1 < ne;
         std::swap(lb.h0, lb.h1);
     }
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
+}
+
+int fd_sampler_run_layers(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt,
+                          float* x, const float* z_steps, uint64_t seed, uint64_t offset, int B, hipStream_t s) {
+    return run_layers<false>(m, sde_rows(*sde, timesteps, n_steps, dt), G, x, z_steps, seed, offset, B, s);
+}
+
+int fd_sampler_run_ode_layers(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
+    return run_layers<true>(m, rows, G, x, nullptr, 0, 0, B, s);
+}
+
+// FDIFF_MEGA_PROF (profiling aid, reverse-SDE loop): the launch with the kernel's per-phase cycle record of workgroup 0 / wave 0,
+// printed to stderr
+static int mega_launch_prof(fd_score* m, const MegaPlan& pl, fd_mega_params& MP, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    const size_t nent = 8300;
+    unsigned long long* pb = nullptr;
+    FD_HIP(ctx, hipMalloc((void**)&pb, nent * 16));
+    FD_HIP(ctx, hipMemsetAsync(pb, 0xff, nent * 16, s));
+    MP.prof = pb;
+    int rc = fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    std::vector<unsigned long long> hb(nent * 2);
+    FD_HIP(ctx, hipMemcpy(hb.data(), pb, nent * 16, hipMemcpyDeviceToHost));
+    (void)hipFree(pb);
+    static const char* names[] = {"step begin->", "time-embed+embed", "QKV weight DMA wait", "K/V projection", "att: last epilogue + barrier",
+                                  "out-proj + LN1", "FFN loop", "FFN combine + LN2", "unembed + SDE",
+                                  " att: prev epilogue/loop", " att: Q proj + frag loads", " att: pass 1 (max)", " att: softmax stats", " att: pass 2 + PV"};
+    double acc[14] = {0};
+    unsigned long long prev = 0, first = 0, last = 0;
+    size_t n = 0;
+    for (; n < 4000 && hb[2 * n] != ~0ull; ++n) {
+        const int ph = (int)hb[2 * n];
+        const unsigned long long tm = hb[2 * n + 1];
+        if (n == 0) first = tm;
+        else if (ph >= 1 && ph <= 13) acc[ph] += (double)(tm - prev);   // (ph == 0 intervals = unprofiled steps)
+        prev = tm;
+        last = tm;
+    }
+    for (size_t i = 4000; i < 4032 && i < nent; ++i)
+        if (hb[2 * i] != ~0ull)
+            fprintf(stderr, "[fdiff prof]   unit loop, group %zu wave %zu: %llu cycles\n", (i - 4000) / 8, (i - 4000) % 8, hb[2 * i + 1]);
+    {   // residency of every workgroup: start / end (100 MHz wall clock), XCC and CU it ran on
+        unsigned long long t0 = ~0ull, t1 = 0;
+        const int ng = std::min(pl.grid, 2048);
+        for (int i = 0; i < ng; ++i) { t0 = std::min(t0, hb[2 * (4100 + i)]); t1 = std::max(t1, hb[2 * (4100 + i) + 1]); }
+        int late = 0;
+        std::map<unsigned long long, int> per_cu;
+        for (int i = 0; i < ng; ++i) {
+            const unsigned long long st = hb[2 * (4100 + i)] - t0;
+            if (st > (t1 - t0) / 10) ++late;
+            const unsigned long long id = hb[2 * (4100 + 2048 + i)];
+            const unsigned hw = (unsigned)id, xcc = (unsigned)(id >> 32) & 0xf;
+            // HW_ID: [3:0] wave, [5:4] simd, [7:6] pipe, [11:8] cu, [12] sh, [15:13] se
+            const unsigned long long key = ((unsigned long long)xcc << 16) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 15);
+            per_cu[key]++;
+        }
+        std::vector<double> dur;
+        for (int i = 0; i < ng; ++i) dur.push_back((hb[2 * (4100 + i) + 1] - hb[2 * (4100 + i)]) / 1e5);
+        std::vector<double> sd = dur;
+        std::sort(sd.begin(), sd.end());
+        fprintf(stderr, "[fdiff prof] workgroup durations (ms): wg0 %.3f min %.3f p10 %.3f median %.3f p90 %.3f max %.3f\n", dur[0],
+                sd.front(), sd[sd.size() / 10], sd[sd.size() / 2], sd[sd.size() * 9 / 10], sd.back());
+        int hist[8] = {0};
+        for (auto& kv : per_cu) hist[std::min(7, kv.second)]++;
+        fprintf(stderr, "[fdiff prof] %d workgroups, launch span %.3f ms, %d started after 10%% of the span; distinct CUs %zu, "
+                "workgroups per CU histogram 1:%d 2:%d 3:%d 4+:%d\n", ng, (t1 - t0) / 1e5, late, per_cu.size(), hist[1], hist[2], hist[3],
+                hist[4] + hist[5] + hist[6] + hist[7]);
+    }
+    {   // duration of every step (workgroup 0): shows drift / clock changes after the profiled first steps
+        unsigned long long pt = 0;
+        int k = 0;
+        for (size_t i = 0; i < n; ++i)
+            if (hb[2 * i] == 0) {
+                if (pt && (k % 8 == 0)) fprintf(stderr, "[fdiff prof]   step %d: %llu cycles\n", k, hb[2 * i + 1] - pt);
+                pt = hb[2 * i + 1];
+                ++k;
+            }
+    }
+    int steps_seen = 0;
+    for (size_t i = 0; i < n; ++i) steps_seen += (hb[2 * i] == 0);
+    fprintf(stderr, "[fdiff prof] nw=%d S=%d npg=%d mt=%d rot=%d lds=%zu: %d steps, %.0f cycles/step\n", pl.nw, pl.S, pl.npg, pl.mt, pl.rot,
+            pl.lds, steps_seen, (double)(last - first) / std::max(1, steps_seen));
+    const int steps_prof = std::max(1, std::min(4, steps_seen));      // phases are recorded for the first 4 steps
+    double acc_all = 0;
+    for (int ph = 1; ph <= 13; ++ph) acc_all += acc[ph];
+    for (int ph = 1; ph <= 13; ++ph)
+        fprintf(stderr, "[fdiff prof]   %-22s %10.0f cycles/step  %5.1f%%\n", names[ph], acc[ph] / steps_prof,
+                100.0 * acc[ph] / std::max(1.0, acc_all));
+    return rc;
+}
+
+// The persistent kernel's share of both loop modes: plan, weight images, device tables at the arena base, launch parameters.
+// FD_ERR_UNSUPPORTED (x untouched) when the shape does not fit, so that the caller can fall back to another loop form.
+template <class Row>
+static int mega_prepare(fd_score* m, const std::vector<Row>& rows, bool heun, bool temb, const float* G, float* x, int B,
+                        hipStream_t s, MegaPlan* pl, fd_mega_params* MP) {
+    *pl = plan_mega(m, B);
+    if (!pl->ok || getenv("FDIFF_NO_MEGA")) return FD_ERR_UNSUPPORTED;
+    if (int rc = fd_bf16_refresh(m, s)) return rc;
+    const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
+    StepTables tb;
+    if (int rc = step_tables(m->ctx, m, rows, 0, n, heun, temb, s, &tb)) return rc;
+    if (int rc = fill_mega_params(m, *pl, B, *MP)) return rc;
+    MP->nsteps = (int)rows.size();
+    MP->x = x;
+    MP->G = G;
+    MP->steps = tb.rows;
+    MP->temb_table = tb.temb;
+    MP->ode_x0 = tb.x0;
+    MP->ode_v0 = tb.v0;
+    MP->n_elem = n;
+    return FD_OK;
+}
+
+// the launch, timed by fd_prof_scope with its algorithmic flops (per series per forward x B x evaluations)
+static int mega_launch(fd_score* m, const MegaPlan& pl, fd_mega_params& MP, int B, const char* label, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    const double T = m->d.max_len, D = m->d.d_model, F = m->d.dim_ff, C = m->d.n_channels, L = m->d.num_layers;
+    const double per_fwd = T * (L * (2 * D * 3 * D + 2 * D * D + 4 * D * F + 4 * T * D) + 4 * C * D) + 2 * D * D;
+    fd_prof_scope scope(ctx, s, label, per_fwd * B * MP.nsteps);
+    if (ctx->prof_on) {
+        if (!ctx->prof_clk) FD_HIP(ctx, hipMalloc((void**)&ctx->prof_clk, 4 * sizeof(unsigned long long)));
+        FD_HIP(ctx, hipMemsetAsync(ctx->prof_clk, 0, 4 * sizeof(unsigned long long), s));
+        MP.clk_out = ctx->prof_clk;
+    }
+    return fd_mega_launch(ctx, MP, m->bf16->ks1, m->bf16->dt, m->bf16->kso, pl.mt, pl.nw, pl.grid, pl.lds, s);
+}
+
+// Whole reverse-diffusion loop in the persistent kernel; FD_ERR_UNSUPPORTED (x untouched) when the shape does not fit
+int fd_sampler_run_mega(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                        float dt, float* x, const float* z_steps, uint64_t seed, uint64_t offset, int B,
+                        hipStream_t s) {
+    MegaPlan pl;
+    fd_mega_params MP;
+    // (FDIFF_MEGA_NO_TEMB_TABLE: compute the time embedding inside the kernel every step, as in forward mode)
+    if (int rc = mega_prepare(m, sde_rows(*sde, timesteps, n_steps, dt), false, !getenv("FDIFF_MEGA_NO_TEMB_TABLE"), G, x, B, s,
+                              &pl, &MP))
+        return rc;
+    MP.mode = FD_MEGA_SAMPLE;
+    MP.z_steps = z_steps;
+    MP.seed = seed;
+    MP.offset = offset;
+    MP.ctr_per_step = (MP.n_elem + 3) / 4;
+    if (getenv("FDIFF_MEGA_PROF")) return mega_launch_prof(m, pl, MP, s);
+    return mega_launch(m, pl, MP, B, "k_mega (persistent score-net + reverse-SDE loop)", s);
+}
+
+// The probability-flow ODE loop of fd_sampler_run_ode (fd_ode.hip) in the persistent kernel: the device table holds one
+// fd_ode_step_coef per score evaluation, the Heun state lives in two (B,T,C) workspace buffers behind it
+int fd_sampler_run_ode_mega(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
+    MegaPlan pl;
+    fd_mega_params MP;
+    if (int rc = mega_prepare(m, rows, rows[0].stage != FD_ODE_EULER, true, G, x, B, s, &pl, &MP)) return rc;
+    MP.mode = FD_MEGA_ODE;
+    return mega_launch(m, pl, MP, B, "k_mega (persistent score-net + probability-flow ODE loop)", s);
 }
 
 // Which kernel path serves a batch of B series in `mode` (no launch, no device work).  The parity tests use it to assert

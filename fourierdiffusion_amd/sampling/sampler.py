@@ -78,24 +78,12 @@ class DiffusionSampler:
 
         prior_noise[b] (bs,T,C) and step_noise[b] (N,bs,T,C) inject the N(0,1) draws of batch b (parity
         tests); by default everything comes from the engine's Philox stream."""
-        model = self.score_model
-        model.eval()
-        sch = self.noise_scheduler
-        N = model.num_training_steps if num_diffusion_steps is None else num_diffusion_steps
-        sch.set_timesteps(N)
-        num_batches = max(1, num_samples // self.sample_batch_size)
-        ctx, h = model._engine()
-        dev = model.device
-        ts_host = sch.timesteps.to(torch.float32).contiguous()
-        ts_arr = (C.c_float * N)(*ts_host.tolist())
-        dt = float(sch.step_size)
-        p = sch._c_params()
-        G = sch.G_on(dev)
-        mode = _PRECISIONS[model.precision_effective]     # fp32 when the model's width has no bf16 instantiation
+        self.score_model.eval()
+        N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
+        ctx, h, p, G, mode = self._engine_args()
+        dev = self.score_model.device
         all_samples: List[torch.Tensor] = []
-        sizes = [min(num_samples - b * self.sample_batch_size, self.sample_batch_size) for b in range(num_batches)]
-        if self.merge_batches and num_batches > 1 and prior_noise is None and step_noise is None and corrector_noise is None:
-            sizes = self._launch_sizes(sum(sizes), mode)
+        sizes = self._batches(num_samples, mode, not (prior_noise is None and step_noise is None and corrector_noise is None))
         for b, bs in enumerate(sizes):
             X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
             z = None
@@ -129,11 +117,7 @@ class DiffusionSampler:
         draws of batch b.  Returns a CPU tensor (n, max_len, n_channels) in sample space."""
         model = self.score_model
         N = model.num_training_steps if num_diffusion_steps is None else int(num_diffusion_steps)
-        mode = _PRECISIONS[model.precision_effective]
-        num_batches = max(1, num_samples // self.sample_batch_size)
-        sizes = [min(num_samples - b * self.sample_batch_size, self.sample_batch_size) for b in range(num_batches)]
-        if self.merge_batches and num_batches > 1 and prior_noise is None:
-            sizes = self._launch_sizes(sum(sizes), mode)
+        sizes = self._batches(num_samples, _PRECISIONS[model.precision_effective], prior_noise is not None)
         grid = self._ode_grid(N, to_noise=False)
         out: List[torch.Tensor] = []
         for b, bs in enumerate(sizes):
@@ -162,9 +146,7 @@ class DiffusionSampler:
         return (C.c_float * (N + 1))(*ts.to(torch.float32).tolist()), N
 
     def _map_ode(self, X: torch.Tensor, grid, solver: str, name: str) -> torch.Tensor:
-        if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (self.max_len, self.n_channels):
-            raise ValueError(f"{name} must be a tensor of shape (n, {self.max_len}, {self.n_channels}), got "
-                             f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
+        self._check_series(X, name)
         dev = self.score_model.device
         out: List[torch.Tensor] = []
         for lo in range(0, X.shape[0], self.sample_batch_size):
@@ -177,15 +159,11 @@ class DiffusionSampler:
         if solver not in self._SOLVERS:
             hint = " (rk45 is available for log_likelihood only)" if solver == "rk45" else ""
             raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}{hint}")
-        model = self.score_model
-        model.eval()
-        sch = self.noise_scheduler
-        ctx, h = model._engine()
+        self.score_model.eval()
+        ctx, h, p, G, mode = self._engine_args()
         ts_arr, N = grid
-        p = sch._c_params()
-        mode = _PRECISIONS[model.precision_effective]
-        rc = _C.lib().fd_sampler_run_ode(h, C.byref(p), sch.G_on(X.device).data_ptr(), ts_arr, N, self._SOLVERS[solver], X.data_ptr(),
-                                         X.shape[0], mode, _C.stream_of(X))
+        rc = _C.lib().fd_sampler_run_ode(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], X.data_ptr(), X.shape[0], mode,
+                                         _C.stream_of(X))
         _C.check(rc, ctx)
         return X
 
@@ -206,20 +184,43 @@ class DiffusionSampler:
         max_evals score evaluations per row (Song et al. 2021 report likelihoods at rtol = atol = 1e-5).  A series any of whose
         rows stops early (max_evals, or a step under scipy's min_step) has converged False and log_prob NaN.
         Returns a ``LikelihoodResult``; ``to_data_space`` converts ``log_prob`` to the series as the user holds them."""
+        adaptive = solver == "rk45"
+        if adaptive:
+            rtol, atol, max_evals = float(rtol), float(atol), int(max_evals)
+        n, reps, N, grid, drift = self._ll_plan(X, num_diffusion_steps, solver, estimator, n_probes, probes, rtol, atol, max_evals)
+        ctx, h, p, G, mode = self._engine_args()
+        dev = self.score_model.device
         T, Cn = self.max_len, self.n_channels
-        if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (T, Cn):
-            raise ValueError(f"X must be a tensor of shape (n, {T}, {Cn}), got "
-                             f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
-        n = int(X.shape[0])
-        if n == 0:
-            raise ValueError("X is an empty batch")
+        key, off = 0, 0
+        if probes is None and estimator != "exact":
+            key, off = (int(seed), 0) if seed is not None else _rng.stream()
+        per_launch = max(1, self.sample_batch_size // reps)
+        launches = []
+        for lo in range(0, n, per_launch):
+            nb = min(per_launch, n - lo)
+            x = X[lo:lo + nb].to(device=dev, dtype=torch.float32).repeat_interleave(reps, dim=0).contiguous()
+            e, off = self._ll_probes(ctx, estimator, probes, lo, nb, reps, key, off)
+            if adaptive:
+                res = self._ll_run_adaptive(ctx, h, p, G, mode, x, e, grid, rtol, atol, max_evals)
+            else:
+                res = self._ll_run(ctx, h, p, G, mode, x, e, grid, N, solver)
+            x1 = x.view(nb, reps, T, Cn)[:, 0].contiguous()
+            lp = torch.empty(nb, device=dev, dtype=torch.float32)
+            _C.check(_C.lib().fd_prior_logp(ctx, C.byref(p), G.data_ptr(), x1.data_ptr(), lp.data_ptr(), nb, T, Cn, _C.stream_of(x1)), ctx)
+            launches.append((lp.cpu(), x1.cpu()) + tuple(r.view(nb, reps, *r.shape[1:]).cpu() for r in res))
+        return self._ll_result(launches, n, reps, N, drift, solver, estimator, rtol, atol)
+
+    def _ll_plan(self, X, num_diffusion_steps, solver, estimator, n_probes, probes, rtol, atol, max_evals):
+        """Validates the arguments of ``log_likelihood`` (before any device work); returns (n, replicas per series, N or None, the
+        grid -- ctypes float[N + 1], or t0 for rk45 --, the drift part of the divergence integral)."""
+        n = self._check_series(X, "X")
+        T, Cn = self.max_len, self.n_channels
         if solver not in self._LL_SOLVERS:
             raise ValueError(f"solver must be one of {sorted(self._LL_SOLVERS)}, got {solver!r}")
         if estimator not in ESTIMATORS:
             raise ValueError(f"estimator must be one of {ESTIMATORS}, got {estimator!r}")
         adaptive = solver == "rk45"
         if adaptive:
-            rtol, atol, max_evals = float(rtol), float(atol), int(max_evals)
             if not (math.isfinite(rtol) and rtol > 0 and math.isfinite(atol) and atol > 0):
                 raise ValueError(f"rk45 needs finite rtol > 0 and atol > 0, got rtol={rtol}, atol={atol}")
             if max_evals < 8:
@@ -254,64 +255,56 @@ class DiffusionSampler:
             # every row integrates the drift part itself (exactly: a(t) is linear); the exact estimator sums rows, so it is
             # removed from all but one (float32 parameters, as the engine reads them)
             p0f, p1f = (float(C.c_float(v).value) for v in (p0, p1))
-            drift = drift_integral(kind, p0f, p1f, t0, 1.0, T * Cn)
-        else:
-            ts = torch.linspace(sch.eps, 1.0, N + 1).to(torch.float32)
-            if not bool((ts[1:] > ts[:-1]).all()):
-                raise ValueError(f"the likelihood grid linspace({sch.eps}, 1, {N + 1}) is not strictly increasing in float32")
-            drift = drift_divergence(kind, float(p0), float(p1), ts.tolist(), solver, T * Cn)
+            return n, reps, N, t0, drift_integral(kind, p0f, p1f, t0, 1.0, T * Cn)
+        ts = torch.linspace(sch.eps, 1.0, N + 1).to(torch.float32)
+        if not bool((ts[1:] > ts[:-1]).all()):
+            raise ValueError(f"the likelihood grid linspace({sch.eps}, 1, {N + 1}) is not strictly increasing in float32")
+        drift = drift_divergence(kind, float(p0), float(p1), ts.tolist(), solver, T * Cn)
+        return n, reps, N, (C.c_float * (N + 1))(*ts.tolist()), drift
 
-        model = self.score_model
-        ctx, h = model._engine()
-        dev = model.device
-        mode = _PRECISIONS[model.precision_effective]
-        p = sch._c_params()
-        G = sch.G_on(dev)
-        if not adaptive:
-            ts_arr = (C.c_float * (N + 1))(*ts.tolist())
-        gcap = 1 + (max_evals - 2) // 6 if adaptive else 0
-        nfes, stats, grids = [], [], []
-        if probes is None and estimator != "exact":
-            key, off = (int(seed), 0) if seed is not None else _rng.stream()
-        per_launch = max(1, self.sample_batch_size // reps)
-        prior, score, lat = [], [], []
-        for lo in range(0, n, per_launch):
-            nb = min(per_launch, n - lo)
-            rows = nb * reps
-            x = X[lo:lo + nb].to(device=dev, dtype=torch.float32).repeat_interleave(reps, dim=0).contiguous()
-            if estimator == "exact":
-                e = torch.eye(T * Cn, device=dev, dtype=torch.float32).view(T * Cn, T, Cn).repeat(nb, 1, 1).contiguous()
-            elif probes is not None:
-                e = _C.dev_f32(probes[lo:lo + nb].to(device=dev, dtype=torch.float32).reshape(rows, T, Cn).contiguous(), "probes")
-            else:
-                e = torch.empty((rows, T, Cn), device=dev, dtype=torch.float32)
-                _C.check(_C.lib().fd_randn(ctx, e.data_ptr(), e.numel(), key, off, _C.stream_of(e)), ctx)
-                off += (e.numel() + 3) // 4
-                if estimator == "rademacher":
-                    e = torch.where(e >= 0, 1.0, -1.0).to(torch.float32).contiguous()
-            if adaptive:
-                sdiv = torch.empty(rows, device=dev, dtype=torch.float64)
-                nfe = torch.empty(rows, device=dev, dtype=torch.int32)
-                st = torch.empty(rows, device=dev, dtype=torch.int32)
-                grid = torch.empty((rows, gcap), device=dev, dtype=torch.float64)
-                rc = _C.lib().fd_likelihood_run_adaptive(h, C.byref(p), G.data_ptr(), t0, 1.0, rtol, atol, max_evals, x.data_ptr(),
-                                                         e.data_ptr(), sdiv.data_ptr(), nfe.data_ptr(), st.data_ptr(),
-                                                         grid.data_ptr(), gcap, rows, mode, _C.stream_of(x))
-                _C.check(rc, ctx)
-                nfes.append(nfe.view(nb, reps).cpu())
-                stats.append(st.view(nb, reps).cpu())
-                grids.append(grid.view(nb, reps, gcap).cpu())
-            else:
-                sdiv = torch.empty(rows, device=dev, dtype=torch.float32)
-                rc = _C.lib().fd_likelihood_run(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], x.data_ptr(),
-                                                e.data_ptr(), sdiv.data_ptr(), rows, mode, _C.stream_of(x))
-                _C.check(rc, ctx)
-            x1 = x.view(nb, reps, T, Cn)[:, 0].contiguous()
-            lp = torch.empty(nb, device=dev, dtype=torch.float32)
-            _C.check(_C.lib().fd_prior_logp(ctx, C.byref(p), G.data_ptr(), x1.data_ptr(), lp.data_ptr(), nb, T, Cn, _C.stream_of(x1)), ctx)
-            prior.append(lp.cpu())
-            score.append(sdiv.view(nb, reps).cpu())
-            lat.append(x1.cpu())
+    def _ll_probes(self, ctx, estimator, probes, lo, nb, reps, key, off):
+        """The probes (nb * reps, T, C) of one launch: the basis vectors (exact), the injected ones, or Philox draws at (key, off);
+        returns them and the Philox offset after them."""
+        T, Cn = self.max_len, self.n_channels
+        dev = self.score_model.device
+        if estimator == "exact":
+            return torch.eye(T * Cn, device=dev, dtype=torch.float32).view(T * Cn, T, Cn).repeat(nb, 1, 1).contiguous(), off
+        if probes is not None:
+            e = probes[lo:lo + nb].to(device=dev, dtype=torch.float32).reshape(nb * reps, T, Cn).contiguous()
+            return _C.dev_f32(e, "probes"), off
+        e = torch.empty((nb * reps, T, Cn), device=dev, dtype=torch.float32)
+        _C.check(_C.lib().fd_randn(ctx, e.data_ptr(), e.numel(), key, off, _C.stream_of(e)), ctx)
+        off += (e.numel() + 3) // 4
+        if estimator == "rademacher":
+            e = torch.where(e >= 0, 1.0, -1.0).to(torch.float32).contiguous()
+        return e, off
+
+    def _ll_run(self, ctx, h, p, G, mode, x, e, ts_arr, N, solver):
+        """fd_likelihood_run on the rows x (in place: latents on return): (score part of the divergence integral,) per row."""
+        sdiv = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+        rc = _C.lib().fd_likelihood_run(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], x.data_ptr(), e.data_ptr(),
+                                        sdiv.data_ptr(), x.shape[0], mode, _C.stream_of(x))
+        _C.check(rc, ctx)
+        return (sdiv,)
+
+    def _ll_run_adaptive(self, ctx, h, p, G, mode, x, e, t0, rtol, atol, max_evals):
+        """fd_likelihood_run_adaptive on the rows x (in place): (divergence integral, nfe, status, accepted grid) per row."""
+        rows, gcap = x.shape[0], 1 + (max_evals - 2) // 6
+        sdiv = torch.empty(rows, device=x.device, dtype=torch.float64)
+        nfe = torch.empty(rows, device=x.device, dtype=torch.int32)
+        st = torch.empty(rows, device=x.device, dtype=torch.int32)
+        grid = torch.empty((rows, gcap), device=x.device, dtype=torch.float64)
+        rc = _C.lib().fd_likelihood_run_adaptive(h, C.byref(p), G.data_ptr(), t0, 1.0, rtol, atol, max_evals, x.data_ptr(), e.data_ptr(),
+                                                 sdiv.data_ptr(), nfe.data_ptr(), st.data_ptr(), grid.data_ptr(), gcap, rows, mode,
+                                                 _C.stream_of(x))
+        _C.check(rc, ctx)
+        return sdiv, nfe, st, grid
+
+    @staticmethod
+    def _ll_result(launches, n, reps, N, drift, solver, estimator, rtol, atol) -> LikelihoodResult:
+        """LikelihoodResult from the launches' (prior log p, latents, divergence rows[, nfe, status, grid]) (CPU tensors)."""
+        adaptive = solver == "rk45"
+        prior, lat, score = ([launch[i] for launch in launches] for i in range(3))
         sd = torch.cat(score).to(torch.float64)
         if adaptive:
             sd = sd - drift      # the score part of every row (its drift part is the exact one to rounding)
@@ -324,9 +317,9 @@ class DiffusionSampler:
         delta = div + drift
         log_prob = prior_lp + delta
         if adaptive:
-            nfe_s = torch.cat(nfes).amax(dim=1).to(torch.int64)
-            converged = (torch.cat(stats) == 1).all(dim=1)
-            grid = torch.cat(grids)
+            nfe_s = torch.cat([launch[3] for launch in launches]).amax(dim=1).to(torch.int64)
+            converged = (torch.cat([launch[4] for launch in launches]) == 1).all(dim=1)
+            grid = torch.cat([launch[5] for launch in launches])
             width = int((~torch.isnan(grid)).sum(dim=2).max())
             grid = grid[:, :, :width].contiguous()
             log_prob = torch.where(converged, log_prob, torch.full_like(log_prob, float("nan")))
@@ -356,18 +349,9 @@ class DiffusionSampler:
         if self.corrector_steps > 0:
             raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
         obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
-        model = self.score_model
-        model.eval()
-        sch = self.noise_scheduler
-        N = model.num_training_steps if num_diffusion_steps is None else num_diffusion_steps
-        sch.set_timesteps(N)
-        ctx, h = model._engine()
-        dev = model.device
-        ts_arr = (C.c_float * N)(*sch.timesteps.to(torch.float32).tolist())
-        dt = float(sch.step_size)
-        p = sch._c_params()
-        G = sch.G_on(dev)
-        mode = _PRECISIONS[model.precision_effective]
+        self.score_model.eval()
+        N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
+        ctx, h, p, G, mode = self._engine_args()
         fstd = std if fourier_transform else None
         n, bs = obs.shape[0], self.sample_batch_size
         out: List[torch.Tensor] = []
@@ -425,16 +409,12 @@ class DiffusionSampler:
 
     def _conditioning(self, observed, mask, feature_mean, feature_std):
         """Validated device copies: observed (n,T,C) f32, mask as uint8 (n,T,C) or (T,C), per-series flag, mean, std."""
-        if not isinstance(observed, torch.Tensor) or not isinstance(mask, torch.Tensor):
+        if not isinstance(mask, torch.Tensor):
             raise ValueError("observed and mask must be torch tensors")
-        T, Cn = self.max_len, self.n_channels
-        if observed.dim() != 3 or tuple(observed.shape[1:]) != (T, Cn):
-            raise ValueError(f"observed must have shape (n, {T}, {Cn}), got {tuple(observed.shape)}")
+        n = self._check_series(observed, "observed")
         if not observed.is_floating_point():
             raise ValueError(f"observed must be a floating-point tensor, got {observed.dtype}")
-        n = observed.shape[0]
-        if n == 0:
-            raise ValueError("observed is an empty batch")
+        T, Cn = self.max_len, self.n_channels
         dev = self.score_model.device
         m_u8, per_series = self._mask_u8(mask, n, T, Cn, dev)
         if (feature_mean is None) != (feature_std is None):
@@ -473,6 +453,17 @@ class DiffusionSampler:
             return dft_standardize(y0, mean, std) if std is not None else dft(y0)
         return ((y0 - mean) / std).contiguous() if std is not None else y0.contiguous()
 
+    def _batches(self, num_samples: int, mode: int, injected: bool) -> List[int]:
+        """Launch sizes of ``sample`` / ``sample_ode``: the reference's batches (``max(1, num_samples // sample_batch_size)`` of
+        them, the last one possibly short), merged by ``_launch_sizes`` unless merge_batches is off, there is one batch, or noise is
+        injected (one launch per batch then)."""
+        bs = self.sample_batch_size
+        num_batches = max(1, num_samples // bs)
+        sizes = [min(num_samples - b * bs, bs) for b in range(num_batches)]
+        if self.merge_batches and num_batches > 1 and not injected:
+            sizes = self._launch_sizes(sum(sizes), mode)
+        return sizes
+
     def _launch_sizes(self, total: int, mode: int) -> List[int]:
         """`total` series cut into launches the device runs full: multiples of (series per workgroup of the persistent kernel at a
         large batch) x (CUs), at most eight rounds of workgroups per launch; the step-by-step path (T > 256, other backbones) keeps
@@ -502,6 +493,29 @@ class DiffusionSampler:
             out.append(take)
             left -= take
         return out
+
+    def _engine_args(self):
+        """(ctx, model handle, SDE parameters, G on the model's device, arithmetic mode) of one engine call."""
+        model, sch = self.score_model, self.noise_scheduler
+        ctx, h = model._engine()
+        return ctx, h, sch._c_params(), sch.G_on(model.device), _PRECISIONS[model.precision_effective]
+
+    def _sde_grid(self, num_diffusion_steps: Optional[int]):
+        """N, the reverse-SDE grid ``linspace(1, eps, N)`` of the scheduler as ctypes float[N], and its step size."""
+        sch = self.noise_scheduler
+        N = self.score_model.num_training_steps if num_diffusion_steps is None else num_diffusion_steps
+        sch.set_timesteps(N)
+        return N, (C.c_float * N)(*sch.timesteps.to(torch.float32).tolist()), float(sch.step_size)
+
+    def _check_series(self, X, name: str) -> int:
+        """Raises ValueError unless X is a non-empty tensor (n, max_len, n_channels); returns n."""
+        T, Cn = self.max_len, self.n_channels
+        if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (T, Cn):
+            raise ValueError(f"{name} must be a tensor of shape (n, {T}, {Cn}), got "
+                             f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")
+        if X.shape[0] == 0:
+            raise ValueError(f"{name} is an empty batch")
+        return int(X.shape[0])
 
     def sample_prior(self, batch_size: int, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         if isinstance(self.noise_scheduler, SDE):
