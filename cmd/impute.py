@@ -3,7 +3,9 @@
 (an extension, not in the reference): hides entries of the test split (mask.kind random / forecast), fills them in with
 DiffusionSampler.impute on the MI355X engine, maps the result back to the time domain and writes imputations.pt (the test
 split's shape) next to the checkpoint, with the MSE / MAE over the hidden entries under the key `impute` of results.yaml.
-With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+num_samples_per_series=K > 1 draws an ensemble of K samples per series instead: imputations.pt is (n, K, T, C) and results.yaml
+holds the ensemble scores of sampling/forecast.py (CRPS, quantile CRPS and CRPS-sum, median errors, 90 % interval coverage) in
+place of the MSE / MAE.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -19,6 +21,7 @@ import yaml  # noqa: E402
 from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
+from fourierdiffusion_amd.sampling.forecast import ensemble_scores  # noqa: E402
 from fourierdiffusion_amd.sampling.masks import observation_mask  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
@@ -35,6 +38,19 @@ def hidden_errors(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor) -> d
         out["mae_hidden"] = float(diff[hid].abs().mean())
     if mask.any():
         out["max_abs_err_observed"] = float(diff[mask].abs().max())
+    return out
+
+
+def ensemble_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor) -> dict:
+    """The results of an ensemble X (n, K, T, C): the shape of the split, the largest deviation on the observed entries over all
+    samples, and the aggregates of sampling.forecast.ensemble_scores over the hidden entries."""
+    out = {"num_series": int(X.shape[0]), "num_samples_per_series": int(X.shape[1]),
+           "hidden_fraction": float((~mask).double().mean())}
+    if mask.any():
+        diff = X.double() - truth.double()[:, None]
+        out["max_abs_err_observed"] = float(diff[mask[:, None].expand_as(diff)].abs().max())
+    if (~mask).any():
+        out.update(ensemble_scores(X, truth, mask).metrics)
     return out
 
 
@@ -60,6 +76,10 @@ class ImputationRunner:
         self.datamodule.prepare_data()
         self.datamodule.setup()
         self.num_diffusion_steps: int = cfg.num_diffusion_steps
+        self.num_samples: int = int(cfg.get("num_samples_per_series", 1))
+        if self.num_samples < 1:
+            raise ValueError(f"num_samples_per_series must be >= 1, got {self.num_samples}")
+        self.num_series = cfg.get("num_series", None)
         self.mask_cfg = cfg.mask
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
@@ -69,6 +89,9 @@ class ImputationRunner:
 
     def impute(self) -> None:
         truth = self.datamodule.X_test.float()
+        if self.num_series is not None:
+            truth = truth[:int(self.num_series)]
+        K = self.num_samples
         # the mask from its own generator: every rank builds the same one, and torch's global generator (the Philox keys) is untouched
         gen = torch.Generator().manual_seed(self.random_seed)
         mask = observation_mask(self.mask_cfg.kind, tuple(truth.shape), p=float(self.mask_cfg.get("p", 0.5)),
@@ -81,11 +104,14 @@ class ImputationRunner:
         X = None
         if hi > lo:
             X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
-                                    feature_mean=mean, feature_std=std)
+                                    feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K)
+            shape = X.shape
+            X = X.reshape(-1, *shape[-2:])                                          # (rows, T, C) for the maps back
             if std is not None:
                 X = destandardize_idft(X, mean, std) if self.fourier_transform else X * std.cpu() + mean.cpu()
             elif self.fourier_transform:
                 X = idft(X)
+            X = X.reshape(shape)
         if self.dist.world > 1:
             import torch.distributed as dist
             parts = [None] * self.dist.world
@@ -95,7 +121,8 @@ class ImputationRunner:
             results_path = self.save_dir / "results.yaml"
             results = yaml.safe_load(open(results_path)) if results_path.exists() else None
             results = results if isinstance(results, dict) else {}
-            results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **hidden_errors(X, truth, mask)}
+            scores = hidden_errors(X, truth, mask) if K == 1 else ensemble_results(X, truth, mask)
+            results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **scores}
             logging.info(f"Saving imputations and errors to {self.save_dir}.\n{dict_to_str(results['impute'])}")
             yaml.dump(data=results, stream=open(results_path, "w"))
             torch.save(X, self.save_dir / "imputations.pt")

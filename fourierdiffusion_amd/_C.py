@@ -101,6 +101,8 @@ _PROTOS = {
                                     C.c_uint64, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_impute": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int, _vp,
                                         C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_impute_rep": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                            _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_pf_ode_drift": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "fd_prior_logp": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
@@ -121,6 +123,7 @@ _PROTOS = {
     "fd_sort_rows_temp_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_sort_rows": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "fd_w2_sorted_rows": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_ensemble_scores": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -39,14 +39,14 @@ struct ImpArgs {
     const float* x;          // (B,T,C) state before the step (may alias out)
     const float* score;      // (B,T,C) score at t_i (STEP only)
     const float* zstep;      // (B,T,C) injected predictor noise or nullptr (Philox at off_step)
-    const float* x0;         // (B,T,C) A^-1(where(m, y, 0))
-    const uint8_t* mask;     // (B,T,C) or (T,C), 1 = observed, time domain
+    const float* x0;         // (B/obs_rep,T,C) A^-1(where(m, y, 0)): state row b reads observation row b / obs_rep
+    const uint8_t* mask;     // (B/obs_rep,T,C) or (T,C), 1 = observed, time domain
     const float* stdv;       // (T,C) feature std of the packed spectrum or nullptr (= 1)
     const float* G;          // (T)
     const float* zobs;       // (B,T,C) injected observation noise or nullptr (Philox at off_obs)
     const float* basis;      // F (Tp x Tp) then F^T (Tp x Tp)
     float* out;
-    int B, T, C, Tp, ncb, mask_per_series;
+    int B, T, C, Tp, ncb, mask_per_series, obs_rep;
     SdeCoef cf;
     float alpha, s;
     uint64_t seed, off_step, off_obs;
@@ -66,8 +66,8 @@ __global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
     const int tid = threadIdx.x;
     const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
     const int T = a.T, C = a.C, Tp = a.Tp;
-    const size_t TC = (size_t)T * C, base = (size_t)b * TC;
-    const uint8_t* mrow = a.mask + (a.mask_per_series ? base : 0);
+    const size_t TC = (size_t)T * C, base = (size_t)b * TC, obase = (size_t)(b / a.obs_rep) * TC;
+    const uint8_t* mrow = a.mask + (a.mask_per_series ? obase : 0);
 
     if (FOURIER)
         for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
             const float Gt = a.G[t];
             float xv = a.x[e];
             if (STEP) xv = fd_sde_apply(xv, a.score[e], zs[j], Gt, a.cf);
-            const float xo = a.alpha * a.x0[e] + a.s * (Gt * zo[j]);
+            const float xo = a.alpha * a.x0[obase + loc[j]] + a.s * (Gt * zo[j]);
             if (FOURIER) {
                 a.out[e] = xv;
                 const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
@@ -249,6 +249,7 @@ int prepare(fd_ctx* ctx, ImpArgs& a, const float* x0, const uint8_t* mask, int m
     a.ncb = (C + kCB - 1) / kCB;
     FD_REQUIRE(ctx, (long long)B * a.ncb < (1ll << 31), "%s: B=%d too large for one launch", who, B);
     a.x0 = x0; a.mask = mask; a.mask_per_series = mask_per_series ? 1 : 0;
+    a.obs_rep = 1;
     a.stdv = fourier ? stdv : nullptr;
     a.G = G;
     a.basis = nullptr;
@@ -294,20 +295,24 @@ extern "C" int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_ob
     return launch(ctx, a, false, fourier != 0, hs);
 }
 
-extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
-                                     float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
-                                     const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps,
-                                     uint64_t seed, uint64_t offset, int B, int mode, void* stream) {
+extern "C" int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                         int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                         int mask_per_series, const float* feat_std, int fourier, const float* z_steps,
+                                         const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
+                                         void* stream) {
     if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute")) return rc;
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_impute: null pointer");
     FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_impute: n_steps=%d", n_steps);
     FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_impute: step size must be > 0 (sde.py:158)");
+    FD_REQUIRE(ctx, obs_replicas > 0 && B % obs_replicas == 0, "fd_sampler_run_impute: B=%d is not a multiple of obs_replicas=%d", B,
+               obs_replicas);
     hipStream_t s = (hipStream_t)stream;
     const int T = m->d.max_len, C = m->d.n_channels;
     ImpArgs a{};
     if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, "fd_sampler_run_impute"))
         return rc;
+    a.obs_rep = obs_replicas;
     // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
     // at the next grid point; the last step projects hard (alpha = 1, s = 0)
     std::vector<SdeCoef> cf(n_steps);
@@ -345,4 +350,12 @@ extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, cons
         if (int rc = launch(ctx, a, true, fourier != 0, s)) return rc;
     }
     return FD_OK;
+}
+
+extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                     float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                     const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps,
+                                     uint64_t seed, uint64_t offset, int B, int mode, void* stream) {
+    return fd_sampler_run_impute_rep(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier,
+                                     z_steps, zobs_steps, seed, offset, B, 1, mode, stream);
 }

@@ -17,7 +17,8 @@ series/s against 600 with launches of 200).  Injected-noise calls (parity tests)
 Conditional sampling (an extension, not in the reference): ``impute`` fills in the unobserved entries of time-domain series
 (imputation, forecasting) by projecting the state onto the observations after every reverse step (Song et al. 2021, Sec. 5,
 App. I.2), the step and the projection fused in one engine launch (fd_sampler_run_impute); ``impute_project`` is the
-projection alone.
+projection alone.  ``impute(..., num_samples=K)`` draws an ensemble of K samples per series as K state rows that read one
+observation row in place (fd_sampler_run_impute_rep); ``sampling.forecast`` scores such ensembles.
 
 Probability-flow ODE (an extension, not in the reference): ``sample_ode`` integrates the deterministic ODE with the reverse SDE's
 marginals (Song et al. 2021, Sec. 4.3) by Euler or Heun, the whole loop one engine call (fd_sampler_run_ode); ``encode`` /
@@ -335,9 +336,12 @@ class DiffusionSampler:
     def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,
                fourier_transform: bool, feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
-               obs_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+               obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None) -> torch.Tensor:
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
-        it back with the caller's destandardise / idft), one series per row of ``observed``.
+        it back with the caller's destandardise / idft), one series per row of ``observed``.  ``num_samples`` = K >= 1: an
+        ensemble of K samples per series instead, (n, K, max_len, n_channels); a launch holds max(1, sample_batch_size // K)
+        series as K adjacent state rows each (the engine reads their observation in place: fd_sampler_run_impute_rep), and the
+        injected noise of a launch has nb * K rows, series-major.
 
         observed (n, T, C): time-domain values at data scale (entries where ``mask`` is False are ignored, NaN allowed); mask: bool,
         (n, T, C) or (T, C), True = observed.  fourier_transform / feature_mean / feature_std: the datamodule's representation
@@ -348,26 +352,35 @@ class DiffusionSampler:
         (slot N-1 of obs_noise is not read), else the engine's Philox stream, drawn in the order of ``sample``."""
         if self.corrector_steps > 0:
             raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
+        if num_samples is not None and (isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1):
+            raise ValueError(f"impute: num_samples must be None or an int >= 1, got {num_samples!r}")
         obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
         self.score_model.eval()
         N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
         ctx, h, p, G, mode = self._engine_args()
         fstd = std if fourier_transform else None
-        n, bs = obs.shape[0], self.sample_batch_size
+        reps = 1 if num_samples is None else int(num_samples)
+        n, bs = obs.shape[0], max(1, self.sample_batch_size // reps)
         out: List[torch.Tensor] = []
         for b, lo in enumerate(range(0, n, bs)):
             nb = min(bs, n - lo)
-            X = self.sample_prior(nb, noise=None if prior_noise is None else prior_noise[b])
-            z = None if step_noise is None else self._noise(step_noise[b], (N, nb), "step_noise")
-            zo = None if obs_noise is None else self._noise(obs_noise[b], (N, nb), "obs_noise")
+            rows = nb * reps
+            X = self.sample_prior(rows, noise=None if prior_noise is None else prior_noise[b])
+            z = None if step_noise is None else self._noise(step_noise[b], (N, rows), "step_noise")
+            zo = None if obs_noise is None else self._noise(obs_noise[b], (N, rows), "obs_noise")
             key, off = (0, 0) if (z is not None and zo is not None) else _rng.stream()
             m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
             x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
-            rc = _C.lib().fd_sampler_run_impute(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
-                                                m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
-                                                _C.ptr(z), _C.ptr(zo), key, off, nb, mode, _C.stream_of(X))
+            if num_samples is None:
+                rc = _C.lib().fd_sampler_run_impute(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                    m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
+                                                    _C.ptr(z), _C.ptr(zo), key, off, nb, mode, _C.stream_of(X))
+            else:
+                rc = _C.lib().fd_sampler_run_impute_rep(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                        m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
+                                                        _C.ptr(z), _C.ptr(zo), key, off, rows, reps, mode, _C.stream_of(X))
             _C.check(rc, ctx)
-            out.append(X)
+            out.append(X if num_samples is None else X.view(nb, reps, *X.shape[1:]))
         return torch.cat([x.cpu() for x in out], dim=0)
 
     def impute_project(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: Optional[float] = None, *,

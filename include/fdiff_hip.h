@@ -319,7 +319,13 @@ int fd_sampler_run_pc(fd_score* m, const fd_sde_params* sde, const float* G, con
  *                          Philox (seed): predictor noise of step i at offset + i*ceil(BTC/4) + e/4 (as fd_sampler_run),
  *                          observation noise at offset + (n_steps + i)*ceil(BTC/4) + e/4.  z_steps, zobs_steps: injected
  *                          (n_steps,B,T,C) noise or NULL (slot n_steps-1 of zobs_steps is not read).  No host synchronisation
- *                          in the loop (the first call for a T builds the transform basis and waits for it). */
+ *                          in the loop (the first call for a T builds the transform basis and waits for it).
+ *   fd_sampler_run_impute_rep: the same loop over B = n * obs_replicas state rows conditioned on n observations: state row r
+ *                          reads observation row r / obs_replicas of x0_obs (n,T,C), and of mask_u8 when mask_per_series, so the
+ *                          replicas of an observation are never materialised (an ensemble of obs_replicas samples per series in
+ *                          one launch).  The Philox layout counts state rows (ceil(BTC/4) per step with B = n * obs_replicas), so
+ *                          every replica draws its own noise; z_steps / zobs_steps are (n_steps,B,T,C).  B must be a multiple of
+ *                          obs_replicas.  fd_sampler_run_impute is the obs_replicas = 1 case. */
 int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                       const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z, uint64_t seed,
                       uint64_t offset, float* out, int B, int T, int C, void* stream);
@@ -327,6 +333,10 @@ int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G,
                           float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
                           int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B,
                           int mode, void* stream);
+int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                              float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                              const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
+                              uint64_t offset, int B, int obs_replicas, int mode, void* stream);
 
 /* Probability-flow ODE extension (NOT in the reference, whose only sampler is Euler-Maruyama over the reverse SDE; Song et al. 2021,
  * Sec. 4.3): the deterministic ODE with the reverse SDE's marginals.  With a = a_x(t), g = g(t) of the SDE (VP: a = beta/2,
@@ -422,6 +432,19 @@ int fd_transpose_rows(fd_ctx* ctx, const float* x, float* out, int n, int d, voi
 int fd_sort_rows_temp_bytes(fd_ctx* ctx, int K, int n, size_t* bytes);
 int fd_sort_rows(fd_ctx* ctx, const float* in, float* out, int K, int n, void* temp, size_t temp_bytes, void* stream);
 int fd_w2_sorted_rows(fd_ctx* ctx, const float* a, const float* b, float* out, int K, int n, int m, void* stream);
+
+/* Ensemble scores of probabilistic imputation / forecasting (NOT in the reference; CSDI, TimeGrad, TSDiff report them): samples
+ * (n, K, T, C) fp32 in data scale and the time domain, truth (n, T, C).  For every entry e = (series, t, c), x_1 .. x_K its
+ * ensemble and y its truth:
+ *   out_crps[e]         (1/K) sum_k |x_k - y| - (1/(2K^2)) sum_{j,k} |x_j - x_k|   (properscoring.crps_ensemble, fair = False)
+ *   out_quantiles[q, e] sample quantile at levels[q] in [0, 1], linear between order statistics at position levels[q] (K - 1)
+ *                       (numpy.quantile / torch.quantile "linear"); (n_levels, n, T, C)
+ *   out_mean[e]         (1/K) sum_k x_k
+ * 1 <= K <= 1024.  levels: device double[n_levels]; any output may be NULL (out_quantiles only when n_levels == 0).  A NaN sample
+ * or truth makes that entry's outputs NaN and no other.  One workgroup sorts a tile of entries in LDS (bitonic), sums in double;
+ * deterministic. */
+int fd_ensemble_scores(fd_ctx* ctx, const float* samples, const float* truth, int n, int K, int T, int C, const double* levels,
+                       int n_levels, float* out_crps, float* out_quantiles, float* out_mean, void* stream);
 
 #ifdef __cplusplus
 }
