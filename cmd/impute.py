@@ -5,7 +5,8 @@ DiffusionSampler.impute on the MI355X engine, maps the result back to the time d
 split's shape) next to the checkpoint, with the MSE / MAE over the hidden entries under the key `impute` of results.yaml.
 num_samples_per_series=K > 1 draws an ensemble of K samples per series instead: imputations.pt is (n, K, T, C) and results.yaml
 holds the ensemble scores of sampling/forecast.py (CRPS, quantile CRPS and CRPS-sum, median errors, 90 % interval coverage) in
-place of the MSE / MAE.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+place of the MSE / MAE.  conditioning=dps (guidance.scale, guidance.jacobian) replaces the projection by gradient guidance; the three
+keys are then recorded in the `impute` block.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -81,6 +82,10 @@ class ImputationRunner:
             raise ValueError(f"num_samples_per_series must be >= 1, got {self.num_samples}")
         self.num_series = cfg.get("num_series", None)
         self.mask_cfg = cfg.mask
+        self.conditioning: str = str(cfg.get("conditioning", "replace"))
+        guidance = cfg.get("guidance", None) or {}
+        self.guidance_scale = float(guidance.get("scale", 1.0))
+        self.guidance_jacobian = bool(guidance.get("jacobian", True))
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
         self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path)
@@ -104,7 +109,9 @@ class ImputationRunner:
         X = None
         if hi > lo:
             X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
-                                    feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K)
+                                    feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K,
+                                    conditioning=self.conditioning, guidance_scale=self.guidance_scale,
+                                    guidance_jacobian=self.guidance_jacobian)
             shape = X.shape
             X = X.reshape(-1, *shape[-2:])                                          # (rows, T, C) for the maps back
             if std is not None:
@@ -123,6 +130,9 @@ class ImputationRunner:
             results = results if isinstance(results, dict) else {}
             scores = hidden_errors(X, truth, mask) if K == 1 else ensemble_results(X, truth, mask)
             results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **scores}
+            if self.conditioning != "replace":
+                results["impute"].update(conditioning=self.conditioning, guidance_scale=self.guidance_scale,
+                                         guidance_jacobian=self.guidance_jacobian)
             logging.info(f"Saving imputations and errors to {self.save_dir}.\n{dict_to_str(results['impute'])}")
             yaml.dump(data=results, stream=open(results_path, "w"))
             torch.save(X, self.save_dir / "imputations.pt")

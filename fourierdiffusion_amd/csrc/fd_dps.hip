@@ -1,0 +1,386 @@
+// fd_dps.hip -- gradient-guided conditional sampling: diffusion posterior sampling (DPS; Chung et al., ICLR 2023) and TSDiff's
+// observation self-guidance (Kollovieh et al., NeurIPS 2023), NOT in the reference.  The state is never overwritten (the hard
+// projection of fd_impute.hip is not used); every reverse step is nudged along -grad_x ||y - A(x0_hat(x))||^2 instead, x0_hat being
+// Tweedie's denoised estimate.  Per state row b and step t_i -> t_{i+1}, with (alpha, s) the perturbation kernel at t_i (the std of
+// frequency k is s G_k), A(x) = idft(sigma x + mu) and idft = F^T diag(1/rho) (F, rho of fd_impute.hip):
+//
+//   x0_hat = (x + s^2 G^2 . score) / alpha
+//   r      = m . idft(sigma . (x0_obs - x0_hat))            = m . (y - A(x0_hat))   (fourier = 0: m . sigma . (x0_obs - x0_hat))
+//   u      = sigma . idft^T(r) = sigma . diag(1/rho) F r                            (fourier = 0: sigma . r)
+//   dx     = J^T (s^2 G^2 . u)                              (fd_score_input_vjp of the training forward; 0 without the Jacobian)
+//   g      = (2 / alpha) (u + dx)                           = -grad_x ||r||^2
+//   x'     = fd_sde_apply(x, score, z) + (zeta / ||r||) g   (0 where ||r|| = 0)
+//
+// The guidance is multiplied by sigma where the projection divides by it, so near-empty spectral bins receive almost nothing.
+//
+// k_dps_residual<FOURIER>: one workgroup per (row, block of 16 channels), on fd_impute.hip's basis and LDS layout.  Phase 1:
+// sigma (x0_obs - x0_hat) / rho into the k-quad LDS image U; phase 2: V = F^T U (v_mfma_f32_16x16x4_f32), masked into W = r, and
+// the block's sum r^2 in double; phase 3: Y = F W, u = sigma Y / rho, dout = s^2 G^2 u.  The block's sum goes to part[b][block]
+// (no atomics).  k_dps_step: elementwise over k_sde_step's Philox groups; a row's ||r||^2 is the sum of its blocks in order, so
+// runs are bit-identical.  Every stage buffer lives in ctx->ll_buf, outside the arena that holds the training forward's saved
+// activations.
+#include <algorithm>
+#include <cmath>
+
+#include "fd_common.h"
+#include "fd_engine.h"
+#include "fd_philox.h"
+#include "fd_score.h"
+#include "fd_sde.h"
+
+namespace {
+
+constexpr int kThreads = 512;    // residual: 8 waves, the row tiles of a product dealt round-robin
+constexpr int kCB = 16;          // channels per workgroup = N of the MFMA tile
+constexpr int kStepBlock = 256;
+
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+struct ResArgs {
+    const float* x;          // (B,T,C) state x_i
+    const float* score;      // (B,T,C) s_theta(x_i, t_i)
+    const float* x0;         // (B/obs_rep,T,C) A^-1(where(m, y, 0))
+    const uint8_t* mask;     // (B/obs_rep,T,C) or (T,C), 1 = observed, time domain
+    const float* stdv;       // (T,C) feature std or nullptr (= 1)
+    const float* G;          // (T)
+    const float* basis;      // F (Tp x Tp) then F^T (Tp x Tp); FOURIER only
+    float* u;                // (B,T,C)
+    float* dout;             // (B,T,C) s^2 G^2 u, or nullptr (no Jacobian)
+    double* part;            // (B, ncb) sum r^2 of each channel block
+    int T, C, Tp, ncb, mask_per_series, obs_rep;
+    float alpha, s2;
+};
+
+__device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k == T)) ? 1.0f : 2.0f; }
+__device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB + c) * 4 + (k & 3); }
+
+template <bool FOURIER>
+__global__ __launch_bounds__(kThreads) void k_dps_residual(ResArgs a) {
+    extern __shared__ float lds[];
+    __shared__ double red[kThreads];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
+    const int T = a.T, C = a.C, Tp = a.Tp;
+    const size_t TC = (size_t)T * C, base = (size_t)b * TC, obase = (size_t)(b / a.obs_rep) * TC;
+    const uint8_t* mrow = a.mask + (a.mask_per_series ? obase : 0);
+    double rr = 0.0;
+
+    if (!FOURIER) {
+        for (int i = tid; i < T * kCB; i += kThreads) {
+            const int t = i / kCB, c = c0 + i % kCB;
+            if (c >= C) continue;
+            const size_t tc = (size_t)t * C + c, e = base + tc;
+            const float Gt = a.G[t], sg2 = a.s2 * (Gt * Gt);
+            const float sd = a.stdv ? a.stdv[tc] : 1.0f;
+            const float x0h = (a.x[e] + sg2 * a.score[e]) / a.alpha;
+            const float r = mrow[tc] ? sd * (a.x0[obase + tc] - x0h) : 0.f;
+            rr += (double)r * (double)r;
+            const float uv = sd * r;
+            a.u[e] = uv;
+            if (a.dout) a.dout[e] = sg2 * uv;
+        }
+    } else {
+        float* U = lds;                            // sigma (x0_obs - x0_hat) / rho, frequency rows
+        float* W = lds + (size_t)Tp * kCB;         // r, time rows
+        for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
+        __syncthreads();
+        // ---- phase 1
+        for (int i = tid; i < T * kCB; i += kThreads) {
+            const int k = i / kCB, cl = i % kCB, c = c0 + cl;
+            if (c >= C) continue;
+            const size_t kc = (size_t)k * C + c, e = base + kc;
+            const float Gk = a.G[k];
+            const float sd = a.stdv ? a.stdv[kc] : 1.0f;
+            const float x0h = (a.x[e] + a.s2 * (Gk * Gk) * a.score[e]) / a.alpha;
+            U[quad_idx(k, cl)] = sd * (a.x0[obase + kc] - x0h) * inv_r(k, T);
+        }
+        __syncthreads();
+        const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
+        const int li = lane & 15, kq = lane >> 4;
+        const int ntile = Tp / 16;
+        const float* Fm = a.basis;
+        const float* Ft = a.basis + (size_t)Tp * Tp;
+        // ---- phase 2: V = F^T U (row i of the tile = time t0 + i); W = r = m ? V : 0
+        for (int tile = wave; tile < ntile; tile += nw) {
+            const int t0 = tile * 16;
+            const float* arow = Ft + (size_t)(t0 + li) * Tp + 4 * kq;
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            for (int k0 = 0; k0 < Tp; k0 += 16) {
+                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(U + ((k0 / 4 + kq) * kCB + li) * 4);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+            }
+            const int c = c0 + li;
+            f32x4 w;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int t = t0 + 4 * kq + v;
+                const bool keep = t < T && c < C && mrow[(size_t)t * C + c];
+                w[v] = keep ? acc0[v] + acc1[v] : 0.f;
+                rr += (double)w[v] * (double)w[v];
+            }
+            *reinterpret_cast<f32x4*>(W + ((t0 / 4 + kq) * kCB + li) * 4) = w;
+        }
+        __syncthreads();
+        // ---- phase 3: Y = F W (row i of the tile = packed row r0 + i); u = sigma Y / rho, dout = s^2 G^2 u
+        for (int tile = wave; tile < ntile; tile += nw) {
+            const int r0 = tile * 16;
+            const float* arow = Fm + (size_t)(r0 + li) * Tp + 4 * kq;
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+            for (int k0 = 0; k0 < Tp; k0 += 16) {
+                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(W + ((k0 / 4 + kq) * kCB + li) * 4);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+            }
+            const int c = c0 + li;
+            if (c >= C) continue;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int k = r0 + 4 * kq + v;
+                if (k >= T) continue;
+                const size_t kc = (size_t)k * C + c, e = base + kc;
+                const float sd = a.stdv ? a.stdv[kc] : 1.0f;
+                const float uv = sd * inv_r(k, T) * (acc0[v] + acc1[v]);
+                a.u[e] = uv;
+                if (a.dout) {
+                    const float Gk = a.G[k];
+                    a.dout[e] = a.s2 * (Gk * Gk) * uv;
+                }
+            }
+        }
+    }
+    // the block's sum r^2: fixed-order LDS tree
+    red[tid] = rr;
+    __syncthreads();
+#pragma unroll
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) a.part[blockIdx.x] = red[0];
+}
+
+struct StepArgs {
+    const float* G;
+    float* x;                // (B,T,C) state, updated in place (STEP)
+    const float* score;
+    const float* zin;        // injected predictor noise or nullptr (Philox at offset)
+    const float* u;
+    const float* dx;         // J^T dout or nullptr
+    const double* part;      // (B, ncb)
+    float* gout;             // GRAD: g (B,T,C)
+    double* rn2_out;         // GRAD: ||r||^2 per row
+    size_t n, TC;
+    int T, C, ncb;
+    SdeCoef cf;
+    float alpha;
+    double zeta;
+    uint64_t seed, offset;
+};
+
+// STEP: x' = fd_sde_apply(x, score, z) + (zeta / ||r||) g over the Philox groups of k_sde_step (group q = elements 4q .. 4q+3 of the
+// whole (B,T,C) tensor, drawn at offset + q).  GRAD: g and ||r||^2 alone.
+template <bool GRAD>
+__global__ __launch_bounds__(kStepBlock) void k_dps_step(StepArgs a) {
+    const size_t ngroups = (a.n + 3) / 4;
+    for (size_t q = blockIdx.x * (size_t)kStepBlock + threadIdx.x; q < ngroups; q += (size_t)gridDim.x * kStepBlock) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!GRAD) {
+            if (a.zin) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (q * 4 + j < a.n) z[j] = a.zin[q * 4 + j];
+            } else {
+                fd_randn4(a.offset + q, a.seed, z);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t e = q * 4 + j;
+            if (e >= a.n) break;
+            const size_t b = e / a.TC, loc = e - b * a.TC;
+            double rn2 = 0.0;
+            for (int k = 0; k < a.ncb; ++k) rn2 += a.part[b * a.ncb + k];
+            const float gv = (2.0f / a.alpha) * (a.u[e] + (a.dx ? a.dx[e] : 0.f));
+            if (GRAD) {
+                a.gout[e] = gv;
+                if (loc == 0) a.rn2_out[b] = rn2;
+            } else {
+                const int t = (int)(loc / a.C);
+                float xv = fd_sde_apply(a.x[e], a.score[e], z[j], a.G[t], a.cf);
+                const float coef = rn2 > 0.0 ? (float)(a.zeta / sqrt(rn2)) : 0.f;
+                if (coef != 0.f) xv += coef * gv;
+                a.x[e] = xv;
+            }
+        }
+    }
+}
+
+// the stage buffers of one run (fd_ll_carve: outside the arena)
+struct DpsBufs {
+    float *tvec, *score, *u, *dout, *dx;
+    double* part;
+};
+int dps_buffers(fd_ctx* ctx, int B, size_t n, int ncb, bool jac, DpsBufs* o) {
+    return fd_ll_carve(ctx, [&](auto take) {
+        o->tvec = (float*)take(B * sizeof(float));
+        o->score = (float*)take(n * sizeof(float));
+        o->u = (float*)take(n * sizeof(float));
+        o->dout = jac ? (float*)take(n * sizeof(float)) : nullptr;
+        o->dx = jac ? (float*)take(n * sizeof(float)) : nullptr;
+        o->part = (double*)take((size_t)B * ncb * sizeof(double));
+    });
+}
+
+// checks and fills the conditioning / geometry fields shared by both entries
+int dps_prepare(fd_score* m, ResArgs& r, const float* G, const float* x, const float* x0, const uint8_t* mask, int mask_per_series,
+                const float* stdv, int fourier, int B, int obs_replicas, hipStream_t s, const char* who) {
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, G && x && x0 && mask, "%s: null pointer", who);
+    FD_REQUIRE(ctx, obs_replicas > 0 && B % obs_replicas == 0, "%s: B=%d is not a multiple of obs_replicas=%d", who, B, obs_replicas);
+    const int T = m->d.max_len, C = m->d.n_channels;
+    FD_REQUIRE(ctx, !fourier || T <= 1024, "%s: max_len %d > 1024 (the LDS images of one series)", who, T);
+    r.T = T; r.C = C;
+    r.Tp = (T + 15) / 16 * 16;
+    r.ncb = (C + kCB - 1) / kCB;
+    FD_REQUIRE(ctx, (long long)B * r.ncb < (1ll << 31), "%s: B=%d too large for one launch", who, B);
+    r.x0 = x0; r.mask = mask; r.mask_per_series = mask_per_series ? 1 : 0;
+    r.obs_rep = obs_replicas;
+    r.stdv = stdv;
+    r.G = G;
+    r.basis = nullptr;
+    if (fourier) {
+        r.basis = fd_impute_basis(ctx, T, r.Tp, s);
+        if (!r.basis) return fd_fail(ctx, FD_ERR_HIP, "%s: could not build the transform basis of T=%d", who, T);
+    }
+    return FD_OK;
+}
+
+template <bool FOURIER>
+int launch_residual(fd_ctx* ctx, const ResArgs& r, int B, hipStream_t s) {
+    static unsigned long long attr_set = 0;
+    const size_t lds = FOURIER ? (size_t)2 * r.Tp * kCB * sizeof(float) : 0;
+    if (FOURIER && fd_first_on_device(attr_set, ctx->device))
+        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_dps_residual<FOURIER>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    hipLaunchKernelGGL((k_dps_residual<FOURIER>), dim3((unsigned)(B * r.ncb)), dim3(kThreads), lds, s, r);
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
+}
+
+template <bool GRAD>
+int launch_step(fd_ctx* ctx, const StepArgs& a, hipStream_t s) {
+    const size_t ngroups = (a.n + 3) / 4;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((ngroups + kStepBlock - 1) / kStepBlock,
+                                                                         (size_t)ctx->num_cu * 16));
+    hipLaunchKernelGGL((k_dps_step<GRAD>), dim3(grid), dim3(kStepBlock), 0, s, a);
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
+}
+
+// One guidance evaluation at (x, tvec): the score (training forward with the Jacobian, else the sampler's forward), the residual,
+// and the VJP; leaves score, u, dx and the block sums in the buffers
+int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, bool jac, bool fourier, int mode, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    if (jac) {
+        if (int rc = fd_score_forward_train(m, x, bf.tvec, bf.score, B, 0.f, 0, 0, s)) return rc;
+    } else {
+        if (int rc = fd_score_forward_any(m, x, bf.tvec, bf.score, B, mode, s)) return rc;
+    }
+    r.x = x;
+    r.score = bf.score;
+    if (int rc = fourier ? launch_residual<true>(ctx, r, B, s) : launch_residual<false>(ctx, r, B, s)) return rc;
+    if (jac)
+        if (int rc = fd_score_input_vjp(m, bf.dout, bf.dx, s)) return rc;
+    return FD_OK;
+}
+
+}  // namespace
+
+extern "C" int fd_impute_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                                  const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian,
+                                  float* g_out, double* rnorm2_out, int B, int obs_replicas, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance")) return rc;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, g_out && rnorm2_out, "fd_impute_guidance: null pointer");
+    FD_REQUIRE(ctx, std::isfinite(t) && t > 0.f, "fd_impute_guidance: t=%g must be finite and > 0", (double)t);
+    hipStream_t s = (hipStream_t)stream;
+    ResArgs r{};
+    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, "fd_impute_guidance"))
+        return rc;
+    const bool jac = jacobian != 0;
+    const size_t n = (size_t)B * r.T * r.C;
+    DpsBufs bf;
+    if (int rc = dps_buffers(ctx, B, n, r.ncb, jac, &bf)) return rc;
+    double al = 1.0, sd = 0.0;
+    fd_marginal_coef(*sde, (double)t, &al, &sd);
+    r.alpha = (float)al;
+    r.s2 = (float)(sd * sd);
+    r.u = bf.u; r.dout = bf.dout; r.part = bf.part;
+    fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
+    fd_fill(bf.tvec, B, t, s);
+    if (int rc = dps_eval(m, r, bf, x, B, jac, fourier != 0, mode, s)) return rc;
+    StepArgs a{};
+    a.G = G; a.u = bf.u; a.dx = bf.dx; a.part = bf.part; a.gout = g_out; a.rn2_out = rnorm2_out;
+    a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
+    a.alpha = r.alpha;
+    return launch_step<true>(ctx, a, s);
+}
+
+extern "C" int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                         float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                         const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
+                                         uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_dps")) return rc;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, timesteps, "fd_sampler_run_impute_dps: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_impute_dps: n_steps=%d", n_steps);
+    FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_impute_dps: step size must be > 0 (sde.py:158)");
+    FD_REQUIRE(ctx, std::isfinite(guidance_scale) && guidance_scale >= 0.f,
+               "fd_sampler_run_impute_dps: guidance_scale=%g must be finite and >= 0", (double)guidance_scale);
+    hipStream_t s = (hipStream_t)stream;
+    ResArgs r{};
+    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s,
+                             "fd_sampler_run_impute_dps"))
+        return rc;
+    const bool jac = jacobian != 0;
+    const size_t n = (size_t)B * r.T * r.C;
+    DpsBufs bf;
+    if (int rc = dps_buffers(ctx, B, n, r.ncb, jac, &bf)) return rc;
+    r.u = bf.u; r.dout = bf.dout; r.part = bf.part;
+    // per-step coefficients on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and Tweedie's (alpha, s) at t_i
+    std::vector<SdeCoef> cf(n_steps);
+    std::vector<float> al(n_steps), s2(n_steps);
+    for (int i = 0; i < n_steps; ++i) {
+        cf[i] = fd_sde_coef(*sde, (double)timesteps[i], dt);
+        double aa = 1.0, ss = 0.0;
+        fd_marginal_coef(*sde, (double)timesteps[i], &aa, &ss);
+        al[i] = (float)aa;
+        s2[i] = (float)(ss * ss);
+    }
+    fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
+    StepArgs a{};
+    a.G = G; a.x = x; a.score = bf.score; a.u = bf.u; a.dx = bf.dx; a.part = bf.part;
+    a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
+    a.zeta = (double)guidance_scale;
+    a.seed = seed;
+    // Philox: predictor noise of step i at offset + i*ceil(BTC/4) (as fd_sampler_run)
+    const uint64_t per_step = (uint64_t)((n + 3) / 4);
+    for (int i = 0; i < n_steps; ++i) {
+        fd_fill(bf.tvec, B, timesteps[i], s);
+        r.alpha = al[i];
+        r.s2 = s2[i];
+        if (int rc = dps_eval(m, r, bf, x, B, jac, fourier != 0, mode, s)) return rc;
+        a.zin = z_steps ? z_steps + (size_t)i * n : nullptr;
+        a.cf = cf[i];
+        a.alpha = al[i];
+        a.offset = offset + (uint64_t)i * per_step;
+        if (int rc = launch_step<false>(ctx, a, s)) return rc;
+    }
+    return FD_OK;
+}

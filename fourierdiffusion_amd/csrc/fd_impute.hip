@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "fd_common.h"
+#include "fd_engine.h"
 #include "fd_philox.h"
 #include "fd_score.h"
 #include "fd_sde.h"
@@ -208,26 +209,6 @@ __global__ __launch_bounds__(256) void k_impute_basis(float* __restrict__ Fm, fl
     }
 }
 
-constexpr int kBasisKey = 2 << 20;     // ctx->fft_tw key -T - kBasisKey (fd_fourier.hip uses T, -T and -T - 2^20)
-
-const float* impute_basis(fd_ctx* ctx, int T, int Tp, hipStream_t s) {
-    const int key = -T - kBasisKey;
-    for (auto& e : ctx->fft_tw)
-        if (e.first == key) return reinterpret_cast<const float*>(e.second);
-    void* d = nullptr;
-    if (hipMalloc(&d, sizeof(float) * 2 * (size_t)Tp * Tp) != hipSuccess) return nullptr;
-    float* Fm = reinterpret_cast<float*>(d);
-    hipLaunchKernelGGL(k_impute_basis, dim3((unsigned)std::min<size_t>(((size_t)Tp * Tp + 255) / 256, 4096)), dim3(256), 0, s, Fm,
-                       Fm + (size_t)Tp * Tp, T, Tp);
-    // once per (context, T): later callers may use another stream
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipFree(d);
-        return nullptr;
-    }
-    ctx->fft_tw.emplace_back(key, d);
-    return Fm;
-}
-
 template <bool STEP, bool FOURIER>
 int launch_variant(fd_ctx* ctx, const ImpArgs& a, size_t lds, hipStream_t s) {
     static unsigned long long attr_set = 0;
@@ -254,7 +235,7 @@ int prepare(fd_ctx* ctx, ImpArgs& a, const float* x0, const uint8_t* mask, int m
     a.G = G;
     a.basis = nullptr;
     if (fourier) {
-        a.basis = impute_basis(ctx, T, a.Tp, s);
+        a.basis = fd_impute_basis(ctx, T, a.Tp, s);
         if (!a.basis) return fd_fail(ctx, FD_ERR_HIP, "%s: could not build the transform basis of T=%d", who, T);
     }
     return FD_OK;
@@ -266,8 +247,30 @@ int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s
     return fourier ? launch_variant<false, true>(ctx, a, lds, s) : launch_variant<false, false>(ctx, a, lds, s);
 }
 
+}  // namespace
+
+constexpr int kBasisKey = 2 << 20;     // ctx->fft_tw key -T - kBasisKey (fd_fourier.hip uses T, -T and -T - 2^20)
+
+const float* fd_impute_basis(fd_ctx* ctx, int T, int Tp, hipStream_t s) {
+    const int key = -T - kBasisKey;
+    for (auto& e : ctx->fft_tw)
+        if (e.first == key) return reinterpret_cast<const float*>(e.second);
+    void* d = nullptr;
+    if (hipMalloc(&d, sizeof(float) * 2 * (size_t)Tp * Tp) != hipSuccess) return nullptr;
+    float* Fm = reinterpret_cast<float*>(d);
+    hipLaunchKernelGGL(k_impute_basis, dim3((unsigned)std::min<size_t>(((size_t)Tp * Tp + 255) / 256, 4096)), dim3(256), 0, s, Fm,
+                       Fm + (size_t)Tp * Tp, T, Tp);
+    // once per (context, T): later callers may use another stream
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipFree(d);
+        return nullptr;
+    }
+    ctx->fft_tw.emplace_back(key, d);
+    return Fm;
+}
+
 // marginal mean coefficient and std of the perturbation kernel at t (sde.py:108-123, 187-210), in double
-void marginal_coef(const fd_sde_params& p, double t, double* alpha, double* sdev) {
+void fd_marginal_coef(const fd_sde_params& p, double t, double* alpha, double* sdev) {
     if (p.kind == 0) {
         const double lmc = -0.25 * t * t * ((double)p.p1 - (double)p.p0) - 0.5 * t * (double)p.p0;
         *alpha = std::exp(lmc);
@@ -277,8 +280,6 @@ void marginal_coef(const fd_sde_params& p, double t, double* alpha, double* sdev
         *sdev = (double)p.p0 * std::pow((double)p.p1 / (double)p.p0, t);
     }
 }
-
-}  // namespace
 
 extern "C" int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                                  const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
@@ -320,7 +321,7 @@ extern "C" int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, 
     for (int i = 0; i < n_steps; ++i) {
         cf[i] = fd_sde_coef(*sde, (double)timesteps[i], dt);
         double aa = 1.0, ss = 0.0;
-        if (i + 1 < n_steps) marginal_coef(*sde, (double)timesteps[i + 1], &aa, &ss);
+        if (i + 1 < n_steps) fd_marginal_coef(*sde, (double)timesteps[i + 1], &aa, &ss);
         al[i] = (float)aa;
         sd[i] = (float)ss;
     }

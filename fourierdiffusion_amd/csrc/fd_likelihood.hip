@@ -10,6 +10,7 @@
 // fd_likelihood_run_adaptive runs the same evaluation under per-row Dormand-Prince 5(4) step control (scipy's RK45), below.
 #include <cmath>
 
+#include "fd_engine.h"
 #include "fd_ode.h"
 #include "fd_score.h"
 #include "fd_sde.h"
@@ -89,31 +90,12 @@ __global__ __launch_bounds__(kBlock) void k_ll_prior(const float* __restrict__ G
     if (threadIdx.x == 0) out[blockIdx.x] = (float)(s - 0.5 * (double)n_row * log(2.0 * M_PI));
 }
 
-// The state of one run, outside the arena (the training forward and its VJP own the arena between them): grow-only, freed with the
-// context.  layout(take) points the run's buffers at consecutive shares of ctx->ll_buf, take(bytes) returning the next one; it runs
-// twice, first to size the buffer.
-template <class Layout>
-int ll_carve(fd_ctx* ctx, Layout layout) {
-    size_t need = 0;
-    layout([&](size_t bytes) -> char* { need += fd_ws::padded(bytes); return nullptr; });
-    if (ctx->ll_bytes < need) {
-        if (ctx->ll_buf) (void)hipFree(ctx->ll_buf);      // (synchronising: an earlier run on any stream has finished with it)
-        ctx->ll_buf = nullptr;
-        ctx->ll_bytes = 0;
-        FD_HIP(ctx, hipMalloc(&ctx->ll_buf, need));
-        ctx->ll_bytes = need;
-    }
-    char* p = (char*)ctx->ll_buf;
-    layout([&](size_t bytes) { char* q = p; p += fd_ws::padded(bytes); return q; });
-    return FD_OK;
-}
-
 struct LlBufs {
     float *tvec, *dout, *score, *dx, *x0, *v0;
     double *acc, *d0;
 };
 int ll_buffers(fd_ctx* ctx, int B, size_t n, bool heun, LlBufs* o) {
-    return ll_carve(ctx, [&](auto take) {
+    return fd_ll_carve(ctx, [&](auto take) {
         o->tvec = (float*)take(B * sizeof(float));
         o->dout = (float*)take(n * sizeof(float));
         o->score = (float*)take(n * sizeof(float));
@@ -125,20 +107,11 @@ int ll_buffers(fd_ctx* ctx, int B, size_t n, bool heun, LlBufs* o) {
     });
 }
 
-// restores the model's training arithmetic when the run returns
-struct TrainModeScope {
-    fd_score* m;
-    int saved;
-    TrainModeScope(fd_score* mm, int mode) : m(mm), saved(mm->train_mode) { m->train_mode = mode; }
-    ~TrainModeScope() { m->train_mode = saved; }
-};
-
 // The frame of both runs around body(): the evaluations run in the training arithmetic (bf16: the bf16 training kernels where the
 // model has them, else -- other backbones, widths -- the exact-f32 ones), and dout = G^2 e is built first
 template <class Body>
 int ll_frame(fd_score* m, int mode, const float* G, const float* probes, float* dout, int B, hipStream_t s, Body body) {
-    const bool bf16 = mode == FD_MODE_BF16 && m->backbone == FD_BACKBONE_TRANSFORMER && fd_train_bf16_supported(m);
-    TrainModeScope tm(m, bf16 ? FD_MODE_BF16 : FD_MODE_F32);
+    fd_train_mode_scope tm(m, fd_diff_train_mode(m, mode));
     const int T = m->d.max_len, C = m->d.n_channels;
     const size_t n = (size_t)B * T * C;
     const unsigned ew = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)m->ctx->num_cu * 16);
@@ -440,7 +413,7 @@ struct RkBufs {
     int* count;
 };
 int rk_buffers(fd_ctx* ctx, int B, size_t n, int gcap, RkBufs* o) {
-    return ll_carve(ctx, [&](auto take) {
+    return fd_ll_carve(ctx, [&](auto take) {
         o->tvec = (float*)take(B * sizeof(float));
         o->dout = (float*)take(n * sizeof(float));
         o->score = (float*)take(n * sizeof(float));

@@ -336,7 +336,8 @@ class DiffusionSampler:
     def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,
                fourier_transform: bool, feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
-               obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None) -> torch.Tensor:
+               obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None,
+               conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True) -> torch.Tensor:
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
         it back with the caller's destandardise / idft), one series per row of ``observed``.  ``num_samples`` = K >= 1: an
         ensemble of K samples per series instead, (n, K, max_len, n_channels); a launch holds max(1, sample_batch_size // K)
@@ -349,16 +350,33 @@ class DiffusionSampler:
         ``sample`` is followed by the projection onto the observations noised to the next time level; the last one is exact, so
         the observed entries of the result reproduce ``observed`` up to f32 transform rounding.  Launches of at most
         ``sample_batch_size`` series; launch b's noise: prior_noise[b] (nb,T,C), step_noise[b] / obs_noise[b] (N,nb,T,C)
-        (slot N-1 of obs_noise is not read), else the engine's Philox stream, drawn in the order of ``sample``."""
+        (slot N-1 of obs_noise is not read), else the engine's Philox stream, drawn in the order of ``sample``.
+
+        conditioning="dps": gradient guidance instead of the projection (diffusion posterior sampling; fd_sampler_run_impute_dps).
+        The state is never overwritten: every reverse step adds (guidance_scale / ||r||) (-grad ||r||^2), r = m . (y - A(x0_hat)) the
+        residual of Tweedie's estimate x0_hat at the observations, and the observed entries of the result are NOT reproduced
+        exactly.  guidance_jacobian=False drops the network's Jacobian from the gradient (d x0_hat / d x ~ I / alpha): about the
+        cost of the projection, against a training forward and an input VJP per step.  guidance_scale: finite, >= 0.  obs_noise is
+        an error under "dps" (no observation is noised)."""
         if self.corrector_steps > 0:
             raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
         if num_samples is not None and (isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1):
             raise ValueError(f"impute: num_samples must be None or an int >= 1, got {num_samples!r}")
+        if conditioning not in ("replace", "dps"):
+            raise ValueError(f"impute: conditioning must be 'replace' or 'dps', got {conditioning!r}")
+        if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)) or not math.isfinite(guidance_scale) \
+                or guidance_scale < 0:
+            raise ValueError(f"impute: guidance_scale must be a finite number >= 0, got {guidance_scale!r}")
+        if not isinstance(guidance_jacobian, bool):
+            raise ValueError(f"impute: guidance_jacobian must be a bool, got {guidance_jacobian!r}")
+        dps = conditioning == "dps"
+        if dps and obs_noise is not None:
+            raise ValueError("impute: obs_noise is not used by conditioning='dps' (no observation is noised)")
         obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
         self.score_model.eval()
         N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
         ctx, h, p, G, mode = self._engine_args()
-        fstd = std if fourier_transform else None
+        fstd = std if (fourier_transform or dps) else None      # (the guidance weighs the residual by sigma in both domains)
         reps = 1 if num_samples is None else int(num_samples)
         n, bs = obs.shape[0], max(1, self.sample_batch_size // reps)
         out: List[torch.Tensor] = []
@@ -368,10 +386,15 @@ class DiffusionSampler:
             X = self.sample_prior(rows, noise=None if prior_noise is None else prior_noise[b])
             z = None if step_noise is None else self._noise(step_noise[b], (N, rows), "step_noise")
             zo = None if obs_noise is None else self._noise(obs_noise[b], (N, rows), "obs_noise")
-            key, off = (0, 0) if (z is not None and zo is not None) else _rng.stream()
+            key, off = (0, 0) if (z is not None and (zo is not None or dps)) else _rng.stream()
             m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
             x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
-            if num_samples is None:
+            if dps:
+                rc = _C.lib().fd_sampler_run_impute_dps(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                        m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
+                                                        float(guidance_scale), int(guidance_jacobian), _C.ptr(z), key, off, rows,
+                                                        reps, mode, _C.stream_of(X))
+            elif num_samples is None:
                 rc = _C.lib().fd_sampler_run_impute(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
                                                     m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
                                                     _C.ptr(z), _C.ptr(zo), key, off, nb, mode, _C.stream_of(X))
@@ -412,6 +435,35 @@ class DiffusionSampler:
                                         _C.ptr(z), key, off, out.data_ptr(), B, T, Cn, _C.stream_of(xd))
         _C.check(rc, h)
         return out
+
+    def impute_guidance(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: float, *,
+                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None, jacobian: bool = True) -> tuple:
+        """One guidance evaluation of ``impute(conditioning="dps")`` alone (fd_impute_guidance): X (B,T,C) in sample space at
+        ``timestep`` -> (g, rnorm2), g = -grad_X ||r||^2 (B,T,C) float32 and rnorm2 = ||r||^2 per row (B,) float64, both on the
+        device.  x0_obs from ``observed_to_sample_space``; feature_std: the datamodule's std when it standardises (used in both
+        domains), else None.  jacobian=False: the Jacobian-free gradient (the score from the sampler's forward)."""
+        T, Cn = self.max_len, self.n_channels
+        if not (isinstance(X, torch.Tensor) and isinstance(x0_obs, torch.Tensor)) or x0_obs.shape != X.shape or X.dim() != 3 \
+                or tuple(X.shape[1:]) != (T, Cn) or X.shape[0] == 0:
+            raise ValueError(f"impute_guidance: X and x0_obs must be tensors of the same non-empty (B,{T},{Cn}) shape")
+        if isinstance(timestep, bool) or not isinstance(timestep, (int, float)) or not math.isfinite(timestep) or timestep <= 0:
+            raise ValueError(f"impute_guidance: timestep must be a finite number > 0, got {timestep!r}")
+        if feature_std is not None and tuple(feature_std.shape) != (T, Cn):
+            raise ValueError(f"impute_guidance: feature_std must have shape {(T, Cn)}, got {tuple(feature_std.shape)}")
+        B = X.shape[0]
+        m_u8, per_series = self._mask_u8(mask, B, T, Cn, self.score_model.device)
+        xd = _C.dev_f32(X.to(self.score_model.device), "X")
+        x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
+        std = None if feature_std is None else _C.dev_f32(feature_std.to(xd.device), "feature_std")
+        self.score_model.eval()
+        ctx, h, p, G, mode = self._engine_args()
+        g = torch.empty_like(xd)
+        rn2 = torch.empty(B, dtype=torch.float64, device=xd.device)
+        rc = _C.lib().fd_impute_guidance(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(),
+                                         int(per_series), _C.ptr(std), int(bool(fourier_transform)), int(bool(jacobian)),
+                                         g.data_ptr(), rn2.data_ptr(), B, 1, mode, _C.stream_of(xd))
+        _C.check(rc, ctx)
+        return g, rn2
 
     def observed_to_sample_space(self, observed: torch.Tensor, mask: torch.Tensor, *, fourier_transform: bool,
                                  feature_mean: Optional[torch.Tensor] = None,

@@ -338,6 +338,34 @@ int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, const float
                               const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
                               uint64_t offset, int B, int obs_replicas, int mode, void* stream);
 
+/* Gradient-guided conditional sampling extension (NOT in the reference; diffusion posterior sampling, Chung et al. 2023, and
+ * TSDiff's observation self-guidance, Kollovieh et al. 2023).  The state is never overwritten; every reverse step is nudged along
+ * -grad ||r||^2 of the observation residual of Tweedie's estimate.  Per state row b and step i (t_i -> t_{i+1}), with (alpha, s)
+ * the perturbation kernel at t_i, A and x0_obs as above, idft = F^T diag(1/rho) (F the packed DFT as a matrix, rho = 1 at DC and
+ * Nyquist, 1/2 elsewhere) and sigma = feat_std (NULL = 1; read in both domains here):
+ *   x0_hat = (x + s^2 G^2 . score) / alpha
+ *   r      = m . idft(sigma . (x0_obs - x0_hat))       (fourier == 0: m . sigma . (x0_obs - x0_hat))
+ *   u      = sigma . diag(1/rho) F r                    (fourier == 0: sigma . r)
+ *   dx     = J^T (s^2 G^2 . u)                          (fd_score_input_vjp of the training forward, dropout 0; 0 when jacobian == 0)
+ *   g      = (2 / alpha) (u + dx)                       = -grad_x ||r||^2
+ *   x'     = fd_sde_apply(x, score, z) + (guidance_scale / ||r||) g      (0 where ||r|| = 0)
+ * jacobian != 0: the score is the training forward's (mode FD_MODE_BF16: the bf16 training kernels where the model has them, else
+ * exact f32); jacobian == 0: the sampler's forward (bf16: the persistent kernel in single-step mode) and no VJP.  Stage buffers live
+ * in the context buffer of fd_likelihood_run (outside the workspace; grown on first use: synchronising).  Per-row sums in double,
+ * fixed order: bit-reproducible.  T <= 1024 when fourier != 0.
+ *   fd_impute_guidance       : one evaluation at (x, t): g_out (B,T,C) and rnorm2_out[b] = ||r_b||^2 (device double[B]).
+ *   fd_sampler_run_impute_dps: the whole loop in place on x (B = n * obs_replicas rows; row b reads observation b / obs_replicas as
+ *                              fd_sampler_run_impute_rep).  Philox (seed): predictor noise of step i at offset + i*ceil(BTC/4) + e/4
+ *                              (as fd_sampler_run); z_steps: injected (n_steps,B,T,C) or NULL.  guidance_scale finite, >= 0.  No
+ *                              host synchronisation in the loop. */
+int fd_impute_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                       const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian, float* g_out,
+                       double* rnorm2_out, int B, int obs_replicas, int mode, void* stream);
+int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt,
+                              float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
+                              int fourier, float guidance_scale, int jacobian, const float* z_steps, uint64_t seed, uint64_t offset,
+                              int B, int obs_replicas, int mode, void* stream);
+
 /* Probability-flow ODE extension (NOT in the reference, whose only sampler is Euler-Maruyama over the reverse SDE; Song et al. 2021,
  * Sec. 4.3): the deterministic ODE with the reverse SDE's marginals.  With a = a_x(t), g = g(t) of the SDE (VP: a = beta/2,
  * g = sqrt(beta); VE: a = 0, g = sigma_min sqrt(2 ln(sigma_max/sigma_min)) (sigma_max/sigma_min)^t) and s the score:

@@ -5,8 +5,12 @@ The model and data are those of scripts/ode_quality.py: a default-width transfor
 scaling) trained on SyntheticDatamodule (sines, generated from the seed; frequency domain, standardised).  The first `--series`
 held-out series are masked (a forecast mask of horizon `--horizon`, a random mask hiding each entry with probability `--p`, each
 from a generator of its own), imputed with K = `--num-samples` samples per series at every step count of `--steps`, mapped back to
-the time domain and scored over the hidden entries.  One run, one seed.  One JSON line per (mask, steps); `--out FILE` writes the
-table as JSON."""
+the time domain and scored over the hidden entries.  One run, one seed.  One JSON line per (mask, steps, conditioning); `--out FILE`
+writes the table as JSON.
+
+`--conditioning replace dps` adds rows of gradient guidance (impute(conditioning="dps")) for every `--guidance-scale` and every
+`--jacobian` setting (on: with the network's Jacobian, off: Jacobian-free).  `--time-domain` trains the model on the time-domain
+representation instead (standardised all the same).  The defaults reproduce the table of the projection alone."""
 from __future__ import annotations
 
 import argparse
@@ -34,6 +38,10 @@ def main() -> None:
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--C", type=int, default=4)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--conditioning", nargs="+", choices=["replace", "dps"], default=["replace"])
+    ap.add_argument("--guidance-scale", type=float, nargs="+", default=[1.0])
+    ap.add_argument("--jacobian", nargs="+", choices=["on", "off"], default=["on"])
+    ap.add_argument("--time-domain", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from fourierdiffusion_amd.dataloaders.datamodules import SyntheticDatamodule
@@ -45,9 +53,11 @@ def main() -> None:
     from fourierdiffusion_amd.trainer import Trainer
     from fourierdiffusion_amd.utils.fourier import destandardize_idft
 
+    fourier = not args.time_domain
+
     torch.manual_seed(args.seed)
     data_dir = tempfile.mkdtemp(prefix="impute_quality_")
-    dm = SyntheticDatamodule(data_dir=data_dir, random_seed=args.seed, batch_size=64, fourier_transform=True, standardize=True,
+    dm = SyntheticDatamodule(data_dir=data_dir, random_seed=args.seed, batch_size=64, fourier_transform=fourier, standardize=True,
                              max_len=args.T, num_samples=args.train_samples, n_channels=args.C)
     dm.prepare_data()
     dm.setup()
@@ -62,7 +72,7 @@ def main() -> None:
     head = {"train": {"epochs": args.epochs, "steps": trainer.global_step, "seconds": round(time.perf_counter() - t0, 1),
                       "final_loss": trainer.history[-1] if trainer.history else None},
             "T": args.T, "C": args.C, "series": args.series, "K": args.num_samples, "seed": args.seed,
-            "precision": model.precision_effective}
+            "precision": model.precision_effective, "fourier_transform": fourier}
     print(json.dumps(head), flush=True)
     truth = dm.X_test[: args.series].float()
     mean, std = dm.feature_mean_and_std
@@ -71,23 +81,37 @@ def main() -> None:
     masks = {f"forecast_h{args.horizon}": observation_mask("forecast", tuple(truth.shape), horizon=args.horizon),
              f"random_p{args.p}": observation_mask("random", tuple(truth.shape), p=args.p,
                                                    generator=torch.Generator().manual_seed(args.seed))}
+    variants = []      # (conditioning keyword arguments, the row's extra fields)
+    for cond in args.conditioning:
+        if cond == "replace":
+            variants.append(({}, {}))
+            continue
+        for jac in args.jacobian:
+            for zeta in args.guidance_scale:
+                variants.append((dict(conditioning="dps", guidance_scale=zeta, guidance_jacobian=jac == "on"),
+                                 {"conditioning": "dps", "guidance_scale": zeta, "guidance_jacobian": jac == "on"}))
     rows = []
     for name, mask in masks.items():
         observed = truth.masked_fill(~mask, float("nan"))
         for N in args.steps:
-            torch.manual_seed(args.seed + N)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            X = sampler.impute(observed, mask, N, fourier_transform=True, feature_mean=mean, feature_std=std, num_samples=K)
-            torch.cuda.synchronize()
-            sec = time.perf_counter() - t0
-            Xt = destandardize_idft(X.reshape(-1, args.T, args.C), mean, std).reshape(X.shape).cpu()
-            t1 = time.perf_counter()
-            sc = ensemble_scores(Xt, truth, mask)
-            rec = {"mask": name, "steps": N, "K": K, "impute_s": round(sec, 2), "score_s": round(time.perf_counter() - t1, 2),
-                   **sc.metrics, "finite": bool(torch.isfinite(Xt).all())}
-            print(json.dumps(rec), flush=True)
-            rows.append(rec)
+            for kw, extra in variants:
+                torch.manual_seed(args.seed + N)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                X = sampler.impute(observed, mask, N, fourier_transform=fourier, feature_mean=mean, feature_std=std, num_samples=K,
+                                   **kw)
+                torch.cuda.synchronize()
+                sec = time.perf_counter() - t0
+                if fourier:
+                    Xt = destandardize_idft(X.reshape(-1, args.T, args.C), mean, std).reshape(X.shape).cpu()
+                else:
+                    Xt = (X * std.cpu() + mean.cpu()).cpu()
+                t1 = time.perf_counter()
+                sc = ensemble_scores(Xt, truth, mask)
+                rec = {"mask": name, "steps": N, "K": K, **extra, "impute_s": round(sec, 2),
+                       "score_s": round(time.perf_counter() - t1, 2), **sc.metrics, "finite": bool(torch.isfinite(Xt).all())}
+                print(json.dumps(rec), flush=True)
+                rows.append(rec)
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"setup": head, "rows": rows}, f, indent=1)
