@@ -110,6 +110,9 @@ _PROTOS = {
                                             _vp]),
     "fd_pf_ode_drift": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_dpm": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "fd_dpm_stage": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.c_int,
+                               C.c_int, C.c_int, _vp]),
     "fd_prior_logp": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run_adaptive": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,

@@ -1637,7 +1637,19 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             // state (ode_x0 / ode_v0 at the same indices) needs no synchronisation between the two stages
                             const fd_ode_step_coef oc = reinterpret_cast<const fd_ode_step_coef*>(P.steps)[step];
                             const float gk = oc.g * P.G[t];
-                            if ((C & 3) == 0) {
+                            if (oc.stage >= FD_ODE_DDIM) {
+                                // data-prediction stage (DDIM / DPM-Solver++ 2M): D_prev at the lane's own indices of ode_x0
+                                const fd_dpm_coef dc = P.dpm[step];
+                                if ((C & 3) == 0) {
+                                    const float4 xv = *reinterpret_cast<const float4*>(P.x + e0);
+                                    *reinterpret_cast<float4*>(P.x + e0) =
+                                        fd_dpm_stage4(xv, sc[0], sc[1], sc[2], sc[3], gk, oc, dc, P.ode_x0 + e0);
+                                } else {
+#pragma unroll
+                                    for (int r = 0; r < 4; ++r)
+                                        if (c0 + r < C) P.x[e0 + r] = fd_dpm_stage1(P.x[e0 + r], sc[r], gk, oc, dc, P.ode_x0 + e0 + r);
+                                }
+                            } else if ((C & 3) == 0) {
                                 const float4 xv = *reinterpret_cast<const float4*>(P.x + e0);
                                 *reinterpret_cast<float4*>(P.x + e0) =
                                     fd_ode_stage4(xv, sc[0], sc[1], sc[2], sc[3], gk, oc, P.ode_x0 + e0, P.ode_v0 + e0);

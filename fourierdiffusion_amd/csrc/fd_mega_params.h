@@ -62,6 +62,42 @@ __device__ __forceinline__ float4 fd_ode_stage4(float4 x, float s0, float s1, fl
     return float4{x.x + c.h * v.x, x.y + c.h * v.y, x.z + c.h * v.z, x.w + c.h * v.w};
 }
 
+// Data-prediction exponential integrator (DPM-Solver++, Lu et al. 2022; its first order is deterministic DDIM) on the same rows, one
+// score evaluation per step.  With (alpha, s) the perturbation kernel and lambda = log(alpha / s), h = lambda' - lambda > 0:
+//   D  = (x + (s G_k)^2 score) / alpha                       Tweedie's estimate of x_0
+//   x' = (s'/s) x + cD ((1 + w) D - w D_prev),   cD = -alpha' expm1(-h),  w = h / (2 h_prev)  (0: first order / first step)
+// The row's fields are reused: a_x = 1 / alpha, g = s (so that gk = s G_k), h = s'/s.  The two weights of D and D_prev do not fit
+// the row (its size is pinned to fd_sde_step_coef) and travel in a parallel array, fd_dpm_coef per evaluation.  D_prev is one
+// (B,T,C) buffer (the Heun x0 buffer), the same element owned by the same lane in every evaluation.
+//   FD_ODE_DDIM      x' = h x + c1 D                         (no state)
+//   FD_ODE_DPM_FIRST the same, D stored
+//   FD_ODE_DPM_2M    x' = h x + c1 D + c0 D_prev, D stored
+#define FD_ODE_DDIM 3
+#define FD_ODE_DPM_FIRST 4
+#define FD_ODE_DPM_2M 5
+struct fd_dpm_coef {
+    float c1, c0;   // cD (1 + w), -cD w
+};
+__device__ __forceinline__ float fd_dpm_stage1(float x, float s, float gk, const fd_ode_step_coef& c, const fd_dpm_coef& w, float* dprev) {
+    const float d = (x + (gk * gk) * s) * c.a_x;
+    float o = c.h * x + w.c1 * d;
+    if (c.stage == FD_ODE_DPM_2M) o += w.c0 * *dprev;
+    if (c.stage != FD_ODE_DDIM) *dprev = d;
+    return o;
+}
+__device__ __forceinline__ float4 fd_dpm_stage4(float4 x, float s0, float s1, float s2, float s3, float gk, const fd_ode_step_coef& c,
+                                                const fd_dpm_coef& w, float* dprev) {
+    const float g2 = gk * gk;
+    const float4 d = {(x.x + g2 * s0) * c.a_x, (x.y + g2 * s1) * c.a_x, (x.z + g2 * s2) * c.a_x, (x.w + g2 * s3) * c.a_x};
+    float4 o = {c.h * x.x + w.c1 * d.x, c.h * x.y + w.c1 * d.y, c.h * x.z + w.c1 * d.z, c.h * x.w + w.c1 * d.w};
+    if (c.stage == FD_ODE_DPM_2M) {
+        const float4 p = *reinterpret_cast<const float4*>(dprev);
+        o.x += w.c0 * p.x; o.y += w.c0 * p.y; o.z += w.c0 * p.z; o.w += w.c0 * p.w;
+    }
+    if (c.stage != FD_ODE_DDIM) *reinterpret_cast<float4*>(dprev) = d;
+    return o;
+}
+
 struct fd_mega_params {
     // shapes
     int B, T, KT /* ceil(T/16) */, C, D, H, hd, L, F;
@@ -105,4 +141,6 @@ struct fd_mega_params {
     // probability-flow ODE (FD_MEGA_ODE): `steps` then holds fd_ode_step_coef rows; Heun state (B,T,C), null for Euler
     float* ode_x0;
     float* ode_v0;
+    // data-prediction stages (FD_ODE_DDIM and above): their second coefficient pair, device array [nsteps]; D_prev lives in ode_x0
+    const fd_dpm_coef* dpm;
 };

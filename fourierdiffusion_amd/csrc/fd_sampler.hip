@@ -109,21 +109,14 @@ extern "C" int fd_sampler_run(fd_score* m, const fd_sde_params* sde, const float
     return FD_OK;
 }
 
-// Probability-flow ODE loop (fd_ode.hip; not in the reference): Euler (n_steps evaluations) or Heun (2 n_steps) over the grid
-// timesteps[0 .. n_steps], in place on x, in the dispatch order of fd_sampler_run.  Step by step: one score launch and one stage
-// launch per evaluation, the Heun state in two (B,T,C) workspace buffers behind the score.
-extern "C" int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
-                                  int solver, float* x, int B, int mode, void* stream) {
-    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_ode")) return rc;
+// Probability-flow ODE loop (fd_ode.hip; not in the reference) over the rows of one solver, in place on x, in the dispatch order of
+// fd_sampler_run.  Step by step: one score launch and one stage launch per evaluation, the solver's state (nstate (B,T,C) workspace
+// buffers: Heun 2, DPM-Solver++ 2M 1) behind the score.  dpm: the data-prediction solvers' second coefficient pairs, or null.
+static int run_ode_rows(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const std::vector<fd_dpm_coef>* dpm, int nstate,
+                        const float* G, float* x, int B, int mode, hipStream_t s) {
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_ode: null pointer");
-    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_ode: n_steps=%d", n_steps);
-    FD_REQUIRE(ctx, solver == 0 || solver == 1, "fd_sampler_run_ode: solver %d (0 Euler, 1 Heun)", solver);
-    std::vector<fd_ode_step_coef> rows;
-    if (int rc = fd_ode_table(ctx, sde, timesteps, n_steps, solver, &rows)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int rc_fused = run_fused(m, mode, [&] { return fd_sampler_run_ode_mega(m, rows, G, x, B, s); },
-                                   [&] { return fd_sampler_run_ode_layers(m, rows, G, x, B, s); });
+    const int rc_fused = run_fused(m, mode, [&] { return fd_sampler_run_ode_mega(m, rows, G, x, B, s, dpm); },
+                                   [&] { return fd_sampler_run_ode_layers(m, rows, G, x, B, s, dpm); });
     if (rc_fused != FD_ERR_UNSUPPORTED) return rc_fused;
 
     const int T = m->d.max_len, C = m->d.n_channels;
@@ -135,17 +128,45 @@ extern "C" int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const f
     for (int k = 0; k < n_eval; ++k) t_eval[k] = rows[k].t;
     float* tvec0 = nullptr;
     size_t tstride = 0;
-    if (int rc = fd_step_table(ctx, fwd, (solver ? 3 : 1) * buf, t_eval.data(), n_eval, B, s, &tvec0, &tstride)) return rc;
+    if (int rc = fd_step_table(ctx, fwd, (1 + nstate) * buf, t_eval.data(), n_eval, B, s, &tvec0, &tstride)) return rc;
     float* score = (float*)((char*)ctx->ws + fwd);
-    float* x0 = solver ? (float*)((char*)ctx->ws + fwd + buf) : nullptr;
-    float* v0 = solver ? (float*)((char*)ctx->ws + fwd + 2 * buf) : nullptr;
+    float* x0 = nstate > 0 ? (float*)((char*)ctx->ws + fwd + buf) : nullptr;
+    float* v0 = nstate > 1 ? (float*)((char*)ctx->ws + fwd + 2 * buf) : nullptr;
     for (int k = 0; k < n_eval; ++k) {
         float* tvec = tvec0 + (size_t)k * tstride;
         if (!tstride) fd_fill(tvec, B, t_eval[k], s);
         if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
-        if (int rc = fd_ode_stage(ctx, G, x, score, x0, v0, rows[k], B, T, C, s)) return rc;
+        if (int rc = fd_ode_stage(ctx, G, x, score, x0, v0, rows[k], B, T, C, s, dpm ? &(*dpm)[k] : nullptr)) return rc;
     }
     return FD_OK;
+}
+
+// Euler (n_steps evaluations) or Heun (2 n_steps) over the grid timesteps[0 .. n_steps]
+extern "C" int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                  int solver, float* x, int B, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_ode")) return rc;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_ode: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_ode: n_steps=%d", n_steps);
+    FD_REQUIRE(ctx, solver == 0 || solver == 1, "fd_sampler_run_ode: solver %d (0 Euler, 1 Heun)", solver);
+    std::vector<fd_ode_step_coef> rows;
+    if (int rc = fd_ode_table(ctx, sde, timesteps, n_steps, solver, &rows)) return rc;
+    return run_ode_rows(m, rows, nullptr, solver ? 2 : 0, G, x, B, mode, (hipStream_t)stream);
+}
+
+// The data-prediction solvers over a sampling grid (t decreasing): solver 2 = deterministic DDIM, 3 = DPM-Solver++ 2M; n_steps
+// evaluations either way
+extern "C" int fd_sampler_run_dpm(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                  int solver, float* x, int B, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_dpm")) return rc;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_dpm: null pointer");
+    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_dpm: n_steps=%d", n_steps);
+    FD_REQUIRE(ctx, solver == 2 || solver == 3, "fd_sampler_run_dpm: solver %d (2 DDIM, 3 DPM-Solver++ 2M)", solver);
+    std::vector<fd_ode_step_coef> rows;
+    std::vector<fd_dpm_coef> dpm;
+    if (int rc = fd_dpm_table(ctx, sde, timesteps, n_steps, solver, &rows, &dpm)) return rc;
+    return run_ode_rows(m, rows, &dpm, solver == 3 ? 1 : 0, G, x, B, mode, (hipStream_t)stream);
 }
 
 // Predictor-corrector variant (not in the reference; BASELINE.json configs[3] says "PC sampler"): n_corr Langevin corrector

@@ -1397,6 +1397,7 @@ struct StepFuseArgs {
     fd_ode_step_coef oc;
     float* x0;
     float* v0;
+    fd_dpm_coef dc;        // second coefficient pair of a data-prediction stage (FD_ODE_DDIM and above; D_prev in x0)
 };
 // ODE: the epilogue runs the probability-flow ODE stage of fd_ode.hip instead of the Euler-Maruyama step (no noise)
 template <int KS1, int DT, bool ODE = false>
@@ -1445,7 +1446,23 @@ __global__ __launch_bounds__(256) void k_unembed_step_embed(const StepFuseArgs A
                 float o[4] = {0.f, 0.f, 0.f, 0.f};
                 if constexpr (ODE) {
                     // (only valid rows: a padding lane shares row M-1 with a valid one and must not touch its Heun state)
-                    if (valid && (C & 3) == 0) {
+                    if (valid && A.oc.stage >= FD_ODE_DDIM) {
+                        // data-prediction stage (DDIM / DPM-Solver++ 2M): D_prev in x0
+                        if ((C & 3) == 0) {
+                            const float4 xv = *reinterpret_cast<const float4*>(A.x + e0);
+                            const float4 r = fd_dpm_stage4(xv, sc[0], sc[1], sc[2], sc[3], gk, A.oc, A.dc, A.x0 + e0);
+                            *reinterpret_cast<float4*>(A.x + e0) = r;
+                            o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                if (c0 + r < C) {
+                                    o[r] = fd_dpm_stage1(A.x[e0 + r], sc[r], gk, A.oc, A.dc, A.x0 + e0 + r);
+                                    A.x[e0 + r] = o[r];
+                                }
+                            }
+                        }
+                    } else if (valid && (C & 3) == 0) {
                         const float4 xv = *reinterpret_cast<const float4*>(A.x + e0);
                         const float4 r = fd_ode_stage4(xv, sc[0], sc[1], sc[2], sc[3], gk, A.oc, A.x0 + e0, A.v0 + e0);
                         *reinterpret_cast<float4*>(A.x + e0) = r;
@@ -1575,27 +1592,35 @@ static std::vector<fd_sde_step_coef> sde_rows(const fd_sde_params& sde, const fl
 
 // Device tables of the two fused forms, reserved at ctx->ws + base: one row per score evaluation (fd_sde_step_coef, or the
 // layout-compatible fd_ode_step_coef: t where the SDE rows keep it, so the time-embedding table is built from either unchanged),
-// the time-embedding table (temb = false: not built, its space still reserved), and for Heun the two (B,T,C) state buffers.
+// the time-embedding table (temb = false: not built, its space still reserved), the (B,T,C) state buffers of the ODE solver
+// (nstate: 2 for Heun, 1 for DPM-Solver++ 2M, else 0) and, behind them, the data-prediction solvers' second coefficient array.
 struct StepTables {
     const fd_sde_step_coef* rows;
     float *temb, *x0, *v0;
+    const fd_dpm_coef* dpm;
 };
+static int ode_state_bufs(int first_stage) {
+    return first_stage == FD_ODE_HEUN_PREDICT ? 2 : first_stage == FD_ODE_DPM_FIRST ? 1 : 0;
+}
 template <class Row>
-static int step_tables(fd_ctx* ctx, const fd_score* m, const std::vector<Row>& rows, size_t base, size_t n, bool heun, bool temb,
-                       hipStream_t s, StepTables* o) {
+static int step_tables(fd_ctx* ctx, const fd_score* m, const std::vector<Row>& rows, size_t base, size_t n, int nstate, bool temb,
+                       hipStream_t s, StepTables* o, const std::vector<fd_dpm_coef>* dpm = nullptr) {
     static_assert(sizeof(Row) == sizeof(fd_sde_step_coef), "rows share the layout of fd_sde_step_coef");
     const size_t ne = rows.size();
     const size_t tab_bytes = fd_ws::padded(sizeof(Row) * ne);
     const size_t temb_bytes = fd_ws::padded(sizeof(float) * ne * m->d.d_model);
     const size_t buf = fd_ws::padded(n * sizeof(float));
-    if (int rc = fd_ws_reserve(ctx, base + tab_bytes + temb_bytes + (heun ? 2 * buf : 0))) return rc;
+    const size_t dpm_bytes = dpm ? fd_ws::padded(sizeof(fd_dpm_coef) * ne) : 0;
+    if (int rc = fd_ws_reserve(ctx, base + tab_bytes + temb_bytes + nstate * buf + dpm_bytes)) return rc;
     char* p = (char*)ctx->ws + base;
     o->rows = reinterpret_cast<const fd_sde_step_coef*>(p);
     o->temb = temb ? reinterpret_cast<float*>(p + tab_bytes) : nullptr;
-    o->x0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes) : nullptr;
-    o->v0 = heun ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes + buf) : nullptr;
+    o->x0 = nstate > 0 ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes) : nullptr;
+    o->v0 = nstate > 1 ? reinterpret_cast<float*>(p + tab_bytes + temb_bytes + buf) : nullptr;
+    o->dpm = dpm ? reinterpret_cast<const fd_dpm_coef*>(p + tab_bytes + temb_bytes + nstate * buf) : nullptr;
     // pageable source: the runtime stages the copy before returning, so `rows` may go out of scope
     FD_HIP(ctx, hipMemcpyAsync(p, rows.data(), sizeof(Row) * ne, hipMemcpyHostToDevice, s));
+    if (dpm) FD_HIP(ctx, hipMemcpyAsync((void*)o->dpm, dpm->data(), sizeof(fd_dpm_coef) * ne, hipMemcpyHostToDevice, s));
     if (temb) {
         fd_mega_params MP;
         memset(&MP, 0, sizeof MP);
@@ -1611,7 +1636,7 @@ static int step_tables(fd_ctx* ctx, const fd_score* m, const std::vector<Row>& r
 // FD_ERR_UNSUPPORTED (x untouched) when this model has no such path.  ODE: rows are fd_ode_step_coef, no noise is read.
 template <bool ODE, class Row>
 static int run_layers(fd_score* m, const std::vector<Row>& rows, const float* G, float* x, const float* z_steps, uint64_t seed,
-                      uint64_t offset, int B, hipStream_t s) {
+                      uint64_t offset, int B, hipStream_t s, const std::vector<fd_dpm_coef>* dpm = nullptr) {
     fd_ctx* ctx = m->ctx;
     const fd_bf16_images* im = m->bf16;
     if (!im || !im->supported || !im->mega || getenv("FDIFF_SAMPLER_UNFUSED_STEP")) return FD_ERR_UNSUPPORTED;
@@ -1623,10 +1648,10 @@ static int run_layers(fd_score* m, const std::vector<Row>& rows, const float* G,
     const int M = B * T;
     const int ne = (int)rows.size();
     const size_t n = (size_t)M * C;
-    bool heun = false;
-    if constexpr (ODE) heun = rows[0].stage != FD_ODE_EULER;
+    int nstate = 0;
+    if constexpr (ODE) nstate = ode_state_bufs(rows[0].stage);
     StepTables tb;
-    if (int rc = step_tables(ctx, m, rows, fd_score_f32_workspace(m, B, false), n, heun, true, s, &tb)) return rc;
+    if (int rc = step_tables(ctx, m, rows, fd_score_f32_workspace(m, B, false), n, nstate, true, s, &tb)) return rc;
     fd_ws ws(ctx);
     LayerBufs lb = carve_layer_bufs(m, B, ws);
     StepFuseArgs A{};
@@ -1649,6 +1674,7 @@ static int run_layers(fd_score* m, const std::vector<Row>& rows, const float* G,
         A.temb = tb.temb + (size_t)(k + 1 < ne ? k + 1 : k) * D;
         if constexpr (ODE) {
             A.oc = rows[k];
+            if (dpm) A.dc = (*dpm)[k];
         } else {
             A.cf = rows[k];
             A.z = z_steps ? z_steps + (size_t)k * n : nullptr;
@@ -1667,8 +1693,9 @@ int fd_sampler_run_layers(fd_score* m, const fd_sde_params* sde, const float* G,
     return run_layers<false>(m, sde_rows(*sde, timesteps, n_steps, dt), G, x, z_steps, seed, offset, B, s);
 }
 
-int fd_sampler_run_ode_layers(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
-    return run_layers<true>(m, rows, G, x, nullptr, 0, 0, B, s);
+int fd_sampler_run_ode_layers(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s,
+                              const std::vector<fd_dpm_coef>* dpm) {
+    return run_layers<true>(m, rows, G, x, nullptr, 0, 0, B, s, dpm);
 }
 
 // FDIFF_MEGA_PROF (profiling aid, reverse-SDE loop): the launch with the kernel's per-phase cycle record of workgroup 0 / wave 0,
@@ -1755,14 +1782,14 @@ static int mega_launch_prof(fd_score* m, const MegaPlan& pl, fd_mega_params& MP,
 // The persistent kernel's share of both loop modes: plan, weight images, device tables at the arena base, launch parameters.
 // FD_ERR_UNSUPPORTED (x untouched) when the shape does not fit, so that the caller can fall back to another loop form.
 template <class Row>
-static int mega_prepare(fd_score* m, const std::vector<Row>& rows, bool heun, bool temb, const float* G, float* x, int B,
-                        hipStream_t s, MegaPlan* pl, fd_mega_params* MP) {
+static int mega_prepare(fd_score* m, const std::vector<Row>& rows, int nstate, bool temb, const float* G, float* x, int B,
+                        hipStream_t s, MegaPlan* pl, fd_mega_params* MP, const std::vector<fd_dpm_coef>* dpm = nullptr) {
     *pl = plan_mega(m, B);
     if (!pl->ok || getenv("FDIFF_NO_MEGA")) return FD_ERR_UNSUPPORTED;
     if (int rc = fd_bf16_refresh(m, s)) return rc;
     const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
     StepTables tb;
-    if (int rc = step_tables(m->ctx, m, rows, 0, n, heun, temb, s, &tb)) return rc;
+    if (int rc = step_tables(m->ctx, m, rows, 0, n, nstate, temb, s, &tb, dpm)) return rc;
     if (int rc = fill_mega_params(m, *pl, B, *MP)) return rc;
     MP->nsteps = (int)rows.size();
     MP->x = x;
@@ -1771,6 +1798,7 @@ static int mega_prepare(fd_score* m, const std::vector<Row>& rows, bool heun, bo
     MP->temb_table = tb.temb;
     MP->ode_x0 = tb.x0;
     MP->ode_v0 = tb.v0;
+    MP->dpm = tb.dpm;
     MP->n_elem = n;
     return FD_OK;
 }
@@ -1796,7 +1824,7 @@ int fd_sampler_run_mega(fd_score* m, const fd_sde_params* sde, const float* G, c
     MegaPlan pl;
     fd_mega_params MP;
     // (FDIFF_MEGA_NO_TEMB_TABLE: compute the time embedding inside the kernel every step, as in forward mode)
-    if (int rc = mega_prepare(m, sde_rows(*sde, timesteps, n_steps, dt), false, !getenv("FDIFF_MEGA_NO_TEMB_TABLE"), G, x, B, s,
+    if (int rc = mega_prepare(m, sde_rows(*sde, timesteps, n_steps, dt), 0, !getenv("FDIFF_MEGA_NO_TEMB_TABLE"), G, x, B, s,
                               &pl, &MP))
         return rc;
     MP.mode = FD_MEGA_SAMPLE;
@@ -1809,11 +1837,13 @@ int fd_sampler_run_mega(fd_score* m, const fd_sde_params* sde, const float* G, c
 }
 
 // The probability-flow ODE loop of fd_sampler_run_ode (fd_ode.hip) in the persistent kernel: the device table holds one
-// fd_ode_step_coef per score evaluation, the Heun state lives in two (B,T,C) workspace buffers behind it
-int fd_sampler_run_ode_mega(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s) {
+// fd_ode_step_coef per score evaluation, the solver's state (Heun: two (B,T,C) workspace buffers, DPM-Solver++ 2M: one) behind it,
+// then the data-prediction solvers' fd_dpm_coef array (dpm: one per row, or null for Euler / Heun)
+int fd_sampler_run_ode_mega(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s,
+                            const std::vector<fd_dpm_coef>* dpm) {
     MegaPlan pl;
     fd_mega_params MP;
-    if (int rc = mega_prepare(m, rows, rows[0].stage != FD_ODE_EULER, true, G, x, B, s, &pl, &MP)) return rc;
+    if (int rc = mega_prepare(m, rows, ode_state_bufs(rows[0].stage), true, G, x, B, s, &pl, &MP, dpm)) return rc;
     MP.mode = FD_MEGA_ODE;
     return mega_launch(m, pl, MP, B, "k_mega (persistent score-net + probability-flow ODE loop)", s);
 }

@@ -23,7 +23,9 @@ observation row in place (fd_sampler_run_impute_rep); ``sampling.forecast`` scor
 Probability-flow ODE (an extension, not in the reference): ``sample_ode`` integrates the deterministic ODE with the reverse SDE's
 marginals (Song et al. 2021, Sec. 4.3) by Euler or Heun, the whole loop one engine call (fd_sampler_run_ode); ``encode`` /
 ``decode`` run it data -> latents and back.  ``ODESampler`` is a DiffusionSampler whose ``sample`` is ``sample_ode``
-(hydra: ``sampler=ode``).
+(hydra: ``sampler=ode``).  ``solver="ddim"`` / ``"dpmpp2m"`` sample the same ODE with the data-prediction exponential integrator
+(DPM-Solver++, Lu et al. 2022: one evaluation per step, first order or second-order multistep; fd_sampler_run_dpm), and
+``schedule="logsnr"`` puts any solver on a grid uniform in the log signal-to-noise ratio (hydra: ``sampler=dpm``).
 
 Likelihood (an extension, not in the reference): ``log_likelihood`` evaluates log p(x) under the probability-flow ODE
 (Song et al. 2021, Sec. 4.3, App. D.2): the ODE runs data -> latents with the divergence integral along it, one engine call
@@ -110,41 +112,78 @@ class DiffusionSampler:
 
     # ------------------------------------------------------------ probability-flow ODE (extension, not in the reference)
     _SOLVERS = {"euler": 0, "heun": 1}
+    _DPM_SOLVERS = {"ddim": 2, "dpmpp2m": 3}      # data-prediction exponential integrators: sampling direction only
+    _SCHEDULES = ("time", "logsnr")
 
     def sample_ode(self, num_samples: int, num_diffusion_steps: Optional[int] = None, solver: str = "heun",
-                   prior_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
-        """Samples by the probability-flow ODE from t = 1 to t = eps on ``linspace(1, eps, N + 1)`` (N steps: N score evaluations
-        for Euler, 2N for Heun).  Batching, launch merging and the prior as ``sample``; prior_noise[b] (bs,T,C) injects the prior
-        draws of batch b.  Returns a CPU tensor (n, max_len, n_channels) in sample space."""
+                   prior_noise: Optional[Sequence[torch.Tensor]] = None, schedule: str = "time") -> torch.Tensor:
+        """Samples by the probability-flow ODE from t = 1 to t = eps in N steps: N score evaluations for Euler, 2N for Heun, N for
+        "ddim" (the first-order exponential integrator in data-prediction form) and "dpmpp2m" (DPM-Solver++ 2M, its second-order
+        multistep form).  schedule: "time", the grid ``linspace(1, eps, N + 1)``, or "logsnr", N + 1 points uniform in
+        ``noise_scheduler.log_snr`` between t = 1 and t = eps.  Batching, launch merging and the prior as ``sample``;
+        prior_noise[b] (bs,T,C) injects the prior draws of batch b.  Returns a CPU tensor (n, max_len, n_channels) in sample
+        space."""
         model = self.score_model
+        self._check_solver(solver, dpm=True)
         N = model.num_training_steps if num_diffusion_steps is None else int(num_diffusion_steps)
+        grid = self._ode_grid(N, to_noise=False, schedule=schedule)
         sizes = self._batches(num_samples, _PRECISIONS[model.precision_effective], prior_noise is not None)
-        grid = self._ode_grid(N, to_noise=False)
         out: List[torch.Tensor] = []
         for b, bs in enumerate(sizes):
             X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
             out.append(self._run_ode(X, grid, solver))
         return torch.cat([x.cpu() for x in out], dim=0)
 
-    def encode(self, X: torch.Tensor, num_diffusion_steps: int, solver: str = "heun") -> torch.Tensor:
-        """Latents of X (n, max_len, n_channels) in sample space: the probability-flow ODE from t = eps to t = 1.  Deterministic;
-        ``decode`` inverts it up to the discretisation error.  Launches of at most ``sample_batch_size`` series; returns a CPU
-        tensor."""
-        return self._map_ode(X, self._ode_grid(int(num_diffusion_steps), to_noise=True), solver, "X")
+    def encode(self, X: torch.Tensor, num_diffusion_steps: int, solver: str = "heun", schedule: str = "time") -> torch.Tensor:
+        """Latents of X (n, max_len, n_channels) in sample space: the probability-flow ODE from t = eps to t = 1 by Euler or Heun
+        (the data-prediction solvers sample only: ValueError).  Deterministic; ``decode`` inverts it up to the discretisation
+        error.  Launches of at most ``sample_batch_size`` series; returns a CPU tensor."""
+        self._check_solver(solver, dpm=False)
+        return self._map_ode(X, self._ode_grid(int(num_diffusion_steps), to_noise=True, schedule=schedule), solver, "X")
 
-    def decode(self, latents: torch.Tensor, num_diffusion_steps: int, solver: str = "heun") -> torch.Tensor:
+    def decode(self, latents: torch.Tensor, num_diffusion_steps: int, solver: str = "heun", schedule: str = "time") -> torch.Tensor:
         """Series in sample space from latents at t = 1: the probability-flow ODE from t = 1 to t = eps (``sample_ode`` from given
-        latents).  Returns a CPU tensor."""
-        return self._map_ode(latents, self._ode_grid(int(num_diffusion_steps), to_noise=False), solver, "latents")
+        latents, any of its solvers and schedules).  Returns a CPU tensor."""
+        self._check_solver(solver, dpm=True)
+        return self._map_ode(latents, self._ode_grid(int(num_diffusion_steps), to_noise=False, schedule=schedule), solver, "latents")
 
-    def _ode_grid(self, N: int, to_noise: bool):
+    def _check_solver(self, solver: str, dpm: bool) -> None:
+        """ValueError unless ``solver`` names an ODE solver (dpm: the data-prediction ones are allowed too)."""
+        if solver in self._SOLVERS or (dpm and solver in self._DPM_SOLVERS):
+            return
+        if solver in self._DPM_SOLVERS:
+            raise ValueError(f"solver {solver!r} integrates from noise to data only (sample_ode, decode); encode takes "
+                             f"{sorted(self._SOLVERS)}")
+        hint = " (rk45 is available for log_likelihood only)" if solver == "rk45" else ""
+        allowed = sorted(self._SOLVERS) + (sorted(self._DPM_SOLVERS) if dpm else [])
+        raise ValueError(f"solver must be one of {allowed}, got {solver!r}{hint}")
+
+    def _ode_grid(self, N: int, to_noise: bool, schedule: str = "time"):
+        if schedule not in self._SCHEDULES:
+            raise ValueError(f"schedule must be one of {list(self._SCHEDULES)}, got {schedule!r}")
         if N < 1:
             raise ValueError(f"num_diffusion_steps must be >= 1, got {N}")
         sch = self.noise_scheduler
         if sch.G is None:
             raise RuntimeError("the noise scheduler has no noise scaling yet (set_noise_scaling)")
-        ts = torch.linspace(sch.eps, 1.0, N + 1) if to_noise else torch.linspace(1.0, sch.eps, N + 1)
+        if schedule == "logsnr":
+            ts = self.logsnr_grid(sch, N)
+            if to_noise:
+                ts = ts.flip(0)
+        else:
+            ts = torch.linspace(sch.eps, 1.0, N + 1) if to_noise else torch.linspace(1.0, sch.eps, N + 1)
         return (C.c_float * (N + 1))(*ts.to(torch.float32).tolist()), N
+
+    @staticmethod
+    def logsnr_grid(sch: SDE, N: int) -> torch.Tensor:
+        """N + 1 float32 times from 1 down to ``sch.eps`` whose log-SNR (``sch.log_snr``) is uniformly spaced: computed in double,
+        the end points exactly 1 and eps.  ValueError when the float32 grid is not strictly decreasing."""
+        l1, l0 = sch.log_snr(1.0), sch.log_snr(sch.eps)
+        ts = [1.0] + [sch.t_of_log_snr(l1 + (l0 - l1) * (i / N)) for i in range(1, N)] + [float(sch.eps)]
+        out = torch.tensor(ts, dtype=torch.float64).to(torch.float32)
+        if not bool((out[1:] < out[:-1]).all()):
+            raise ValueError(f"the log-SNR grid of {N} steps between t = 1 and t = {sch.eps} is not strictly decreasing in float32")
+        return out
 
     def _map_ode(self, X: torch.Tensor, grid, solver: str, name: str) -> torch.Tensor:
         self._check_series(X, name)
@@ -157,14 +196,15 @@ class DiffusionSampler:
 
     def _run_ode(self, X: torch.Tensor, grid, solver: str) -> torch.Tensor:
         """X (bs,T,C) device float32, integrated in place over ``grid`` (ctypes float[N+1], N)."""
-        if solver not in self._SOLVERS:
-            hint = " (rk45 is available for log_likelihood only)" if solver == "rk45" else ""
-            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}{hint}")
+        self._check_solver(solver, dpm=True)
         self.score_model.eval()
         ctx, h, p, G, mode = self._engine_args()
         ts_arr, N = grid
-        rc = _C.lib().fd_sampler_run_ode(h, C.byref(p), G.data_ptr(), ts_arr, N, self._SOLVERS[solver], X.data_ptr(), X.shape[0], mode,
-                                         _C.stream_of(X))
+        if solver in self._DPM_SOLVERS:
+            run, sid = _C.lib().fd_sampler_run_dpm, self._DPM_SOLVERS[solver]
+        else:
+            run, sid = _C.lib().fd_sampler_run_ode, self._SOLVERS[solver]
+        rc = run(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), X.shape[0], mode, _C.stream_of(X))
         _C.check(rc, ctx)
         return X
 
@@ -591,14 +631,18 @@ class DiffusionSampler:
 
 class ODESampler(DiffusionSampler):
     """A DiffusionSampler whose ``sample`` integrates the probability-flow ODE (``sample_ode``) with the constructor's ``solver``
-    ("heun" or "euler"): ``python cmd/sample.py sampler=ode num_diffusion_steps=50``."""
+    ("heun", "euler", "ddim" or "dpmpp2m") and ``schedule`` ("time" or "logsnr"):
+    ``python cmd/sample.py sampler=ode num_diffusion_steps=50``, ``python cmd/sample.py sampler=dpm num_diffusion_steps=20``."""
 
-    def __init__(self, score_model: ScoreModule, sample_batch_size: int, solver: str = "heun", merge_batches: bool = True) -> None:
+    def __init__(self, score_model: ScoreModule, sample_batch_size: int, solver: str = "heun", merge_batches: bool = True,
+                 schedule: str = "time") -> None:
         super().__init__(score_model=score_model, sample_batch_size=sample_batch_size, merge_batches=merge_batches)
-        if solver not in self._SOLVERS:
-            raise ValueError(f"solver must be one of {sorted(self._SOLVERS)}, got {solver!r}")
+        self._check_solver(solver, dpm=True)
+        if schedule not in self._SCHEDULES:
+            raise ValueError(f"schedule must be one of {list(self._SCHEDULES)}, got {schedule!r}")
         self.solver = solver
+        self.schedule = schedule
 
     def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
-        return self.sample_ode(num_samples, num_diffusion_steps, solver=self.solver, prior_noise=prior_noise)
+        return self.sample_ode(num_samples, num_diffusion_steps, solver=self.solver, prior_noise=prior_noise, schedule=self.schedule)

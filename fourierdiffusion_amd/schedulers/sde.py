@@ -114,6 +114,29 @@ class SDE(abc.ABC):
             return math.exp(lmc), math.sqrt(1.0 - math.exp(2.0 * lmc))
         return 1.0, p0 * (p1 / p0) ** t
 
+    def log_snr(self, t: float) -> float:
+        """lambda(t) = log(alpha(t) / s(t)), the half log signal-to-noise ratio of the perturbation kernel (per coordinate it is
+        shifted by -log G_k, a constant in t), in double.  Strictly decreasing in t.  VP: s^2 = 1 - alpha^2 comes from expm1 (at
+        t = eps the difference cancels to half the mantissa)."""
+        p0, p1 = self._params()
+        t = float(t)
+        if self.kind == 0:
+            lmc = -0.25 * t * t * (p1 - p0) - 0.5 * t * p0
+            return lmc - 0.5 * math.log(-math.expm1(2.0 * lmc))
+        return -(math.log(p0) + t * math.log(p1 / p0))
+
+    def t_of_log_snr(self, lam: float) -> float:
+        """The inverse of ``log_snr`` in closed form.  VE: t is affine in lambda.  VP: log alpha = -0.5 log(1 + exp(-2 lambda)), and
+        t is the positive root of 0.25 (beta_1 - beta_0) t^2 + 0.5 beta_0 t + log alpha = 0 (in the form without cancellation)."""
+        p0, p1 = self._params()
+        lam = float(lam)
+        if self.kind == 0:
+            # -0.5 log1p(exp(-2 lam)), without overflow for lam << 0
+            lmc = -0.5 * math.log1p(math.exp(-2.0 * lam)) if lam > 0 else lam - 0.5 * math.log1p(math.exp(2.0 * lam))
+            a, b = 0.25 * (p1 - p0), 0.5 * p0
+            return -2.0 * lmc / (b + math.sqrt(b * b - 4.0 * a * lmc))
+        return (-lam - math.log(p0)) / math.log(p1 / p0)
+
     def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
         """mean(x0, t) + noise -- the noise is already scaled by the caller (sde.py:66-77)."""
         mean, _ = self.marginal_prob(original_samples, timesteps)
@@ -199,6 +222,34 @@ class SDE(abc.ABC):
                                       out.data_ptr(), B, T, Cn, _C.stream_of(xd))
         _C.check(rc, h)
         return out
+
+    def dpm_step(self, model_output: torch.Tensor, timestep: float, next_timestep: float, sample: torch.Tensor,
+                 prev_data: Optional[torch.Tensor] = None, prev_timestep: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One step t -> t_next (t_next < t) of the data-prediction exponential integrator (fd_dpm_stage): returns (x_next, D) with
+        D = (x + (s G)^2 score) / alpha Tweedie's estimate of x_0 at t.  prev_data None: first order (deterministic DDIM, and the
+        first step of DPM-Solver++ 2M); else the D returned by the step before, taken at ``prev_timestep`` > t: the 2M update.  The
+        step-wise twin of ``DiffusionSampler.sample_ode(solver="ddim" / "dpmpp2m")``; returns new device tensors."""
+        assert self.G is not None
+        if (prev_data is None) != (prev_timestep is None):
+            raise ValueError("dpm_step: prev_data and prev_timestep go together (both or neither)")
+        xd = _C.dev_f32(sample, "sample")
+        sd = _C.dev_f32(model_output.to(xd.device), "model_output")
+        if sd.shape != xd.shape or xd.dim() != 3:
+            raise ValueError(f"dpm_step: sample {tuple(xd.shape)} and model_output {tuple(sd.shape)} must be the same (B,T,C) shape")
+        dp = None
+        if prev_data is not None:
+            dp = _C.dev_f32(prev_data.to(xd.device), "prev_data")
+            if dp.shape != xd.shape:
+                raise ValueError(f"dpm_step: prev_data {tuple(dp.shape)} must have the shape of sample {tuple(xd.shape)}")
+        B, T, Cn = xd.shape
+        out, d_out = torch.empty_like(xd), torch.empty_like(xd)
+        h = _C.ctx(xd.device)
+        p = self._c_params()
+        rc = _C.lib().fd_dpm_stage(h, C.byref(p), self.G_on(xd.device).data_ptr(), xd.data_ptr(), sd.data_ptr(), _C.ptr(dp),
+                                   float("nan") if prev_timestep is None else float(prev_timestep), float(timestep),
+                                   float(next_timestep), out.data_ptr(), d_out.data_ptr(), B, T, Cn, _C.stream_of(xd))
+        _C.check(rc, h)
+        return out, d_out
 
 
 class VEScheduler(SDE):

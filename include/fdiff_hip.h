@@ -385,6 +385,24 @@ int fd_pf_ode_drift(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const
 int fd_sampler_run_ode(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
                        float* x, int B, int mode, void* stream);
 
+/* Data-prediction exponential integrators for the same ODE (NOT in the reference; DPM-Solver++, Lu et al. 2022, in its multistep
+ * second-order form "2M", and its first order, deterministic DDIM, Song et al. 2021a).  With (alpha, s) the perturbation kernel
+ * x_t = alpha x_0 + s G z, lambda = log(alpha / s) and h_i = lambda(t_{i+1}) - lambda(t_i) > 0 on a grid t_0 > ... > t_N:
+ *   D_i     = (x_i + (s_i G_k)^2 score(x_i, t_i)) / alpha_i                                  Tweedie's estimate of x_0
+ *   Dbar    = D_i  (solver 2: DDIM; solver 3: i = 0)   or   (1 + h_i / (2 h_{i-1})) D_i - h_i / (2 h_{i-1}) D_{i-1}  (solver 3: 2M)
+ *   x_{i+1} = (s_{i+1} / s_i) x_i - alpha_{i+1} expm1(-h_i) Dbar
+ * One score evaluation per step; the coefficients are computed on the host in double.  G_k cancels from every ratio.
+ *   fd_sampler_run_dpm: the whole loop in place on x (B,T,C), arguments and dispatch as fd_sampler_run_ode.  timesteps: HOST
+ *                       float[n_steps + 1], finite, strictly DECREASING, with lambda strictly increasing (FD_ERR_ARG otherwise).
+ *                       solver: 2 or 3 (FD_ERR_ARG otherwise; fd_sampler_run_ode keeps 0 and 1).
+ *   fd_dpm_stage      : one step t -> t_next on given x and score: x_out = x_{i+1}, d_out = D_i.  d_prev == NULL: first order;
+ *                       else D_{i-1}, evaluated at t_prev > t (2M).  x_out may alias x, d_out may alias d_prev; no other aliasing.
+ *                       The step-wise building block (the times are rounded to float first, as the loop's grid is). */
+int fd_sampler_run_dpm(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
+                       float* x, int B, int mode, void* stream);
+int fd_dpm_stage(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const float* x, const float* score, const float* d_prev,
+                 double t_prev, double t, double t_next, float* x_out, float* d_out, int B, int T, int C, void* stream);
+
 /* Likelihood extension (NOT in the reference; Song et al. 2021, Sec. 4.3 and App. D.2): the exact log-density of the
  * probability-flow ODE above,
  *   log p_0(x_0) = log p_1(x_1) + int_eps^1 div v(x(t), t) dt,   div v = -a T C - 0.5 g^2 tr(diag(G_k^2) ds/dx)

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""ms per score evaluation of DiffusionSampler.sample() (reverse SDE, Euler-Maruyama) against sample_ode (probability-flow ODE, Euler
-and Heun) on the bf16 path, default-width model (D = 72, L = 10, H = 12), random weights: at the benched ecg shape (T = 100, C = 12,
+"""ms per score evaluation of DiffusionSampler.sample() (reverse SDE, Euler-Maruyama) against sample_ode (probability-flow ODE: Euler,
+Heun, and the data-prediction solvers DDIM and DPM-Solver++ 2M on the log-SNR grid) on the bf16 path, default-width model (D = 72, L = 10, H = 12), random weights: at the benched ecg shape (T = 100, C = 12,
 B = 2 x CUs: the persistent kernel) and at BASELINE configs[4] (T = 1024, C = 16, B = 64: layer launches + the fused
 unembed / step / embed launch).  The same number of evaluations per run for every sampler (`--evals`, below the run-time
-specialisation threshold, so all three run the same ahead-of-time kernel), runs alternated over `--reps` rounds, the median kept.
+specialisation threshold, so all of them run the same ahead-of-time kernel), runs alternated over `--reps` rounds, the median kept.
 One JSON line per shape; `--out FILE` also writes them as a JSON list."""
 from __future__ import annotations
 
@@ -47,7 +47,9 @@ def main() -> None:
         m, _, _ = make_model(cfg, precision="bf16")
         s = DiffusionSampler(score_model=m, sample_batch_size=B)
         runs = {"sde": lambda: s.sample(B, E), "ode_euler": lambda: s.sample_ode(B, E, solver="euler"),
-                "ode_heun": lambda: s.sample_ode(B, E // 2, solver="heun")}
+                "ode_heun": lambda: s.sample_ode(B, E // 2, solver="heun"),
+                "ode_ddim": lambda: s.sample_ode(B, E, solver="ddim", schedule="logsnr"),
+                "ode_dpmpp2m": lambda: s.sample_ode(B, E, solver="dpmpp2m", schedule="logsnr")}
         for fn in runs.values():         # warm-up: images, workspace, first launches
             fn()
         times = {k: [] for k in runs}
@@ -58,6 +60,7 @@ def main() -> None:
                "plan": m.plan(B, "bf16")[0].split(" S=")[0]}
         for k, v in times.items():
             rec[f"{k}_ms_per_eval"] = 1e3 * statistics.median(v) / E
+            rec[f"{k}_ms_per_eval_rounds"] = [round(1e3 * t / E, 5) for t in v]
         rec["heun_over_sde"] = rec["ode_heun_ms_per_eval"] / rec["sde_ms_per_eval"]
         rec["euler_over_sde"] = rec["ode_euler_ms_per_eval"] / rec["sde_ms_per_eval"]
         print(json.dumps(rec), flush=True)

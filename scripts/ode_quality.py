@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Sample quality against the number of score evaluations: reverse-SDE sampling (Euler-Maruyama, the reference's sampler) against the
-probability-flow ODE (Heun, Euler) on one trained model.
+probability-flow ODE (Heun, Euler, deterministic DDIM, DPM-Solver++ 2M; on the time-uniform grid and on the log-SNR grid) on one
+trained model.
 
 A default-width transformer (D = 72, L = 10, H = 12, VP-SDE, Fourier noise scaling) is trained on SyntheticDatamodule (sines, generated
 locally from the seed; frequency domain, standardised), then every sampler draws `--num-samples` series; the series are mapped back to
@@ -22,6 +23,11 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 ROWS = [("sde", 1000), ("sde", 100), ("sde", 50), ("heun", 10), ("heun", 25), ("heun", 50), ("heun", 100), ("euler", 100)]
+# (sampler, steps, schedule) rows behind them: the data-prediction solvers at 10-50 evaluations on both grids, Euler / Heun on the
+# log-SNR grid at the evaluation counts of their time-grid rows
+ROWS = [(k, n, "time") for k, n in ROWS] + \
+       [(k, n, sc) for k in ("ddim", "dpmpp2m") for sc in ("time", "logsnr") for n in (10, 15, 20, 30, 50)] + \
+       [("heun", 10, "logsnr"), ("heun", 25, "logsnr"), ("heun", 50, "logsnr"), ("euler", 50, "logsnr"), ("euler", 100, "logsnr")]
 
 
 def main() -> None:
@@ -70,9 +76,10 @@ def main() -> None:
     print(json.dumps({"baselines": base}), flush=True)
     sampler = DiffusionSampler(score_model=model, sample_batch_size=args.num_samples)
     rows = []
-    for kind, N in ROWS:
+    for kind, N, schedule in ROWS:
         torch.manual_seed(args.seed + N)
-        run = (lambda: sampler.sample(args.num_samples, N)) if kind == "sde" else (lambda: sampler.sample_ode(args.num_samples, N, solver=kind))
+        run = (lambda: sampler.sample(args.num_samples, N)) if kind == "sde" else \
+            (lambda: sampler.sample_ode(args.num_samples, N, solver=kind, schedule=schedule))
         run() if N <= 100 else None       # (warm-up of short runs: the first launch of a shape builds images / workspace)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -80,7 +87,8 @@ def main() -> None:
         torch.cuda.synchronize()
         sec = time.perf_counter() - t0
         Xt = destandardize_idft(X, mean, std)
-        rec = {"sampler": kind, "steps": N, "evals": N * (2 if kind == "heun" else 1), "ms_per_series": 1e3 * sec / X.shape[0],
+        rec = {"sampler": kind, "schedule": schedule, "steps": N, "evals": N * (2 if kind == "heun" else 1),
+               "ms_per_series": 1e3 * sec / X.shape[0],
                **sw(Xt), **mw(Xt), "finite": bool(torch.isfinite(Xt).all())}
         print(json.dumps(rec), flush=True)
         rows.append(rec)
