@@ -50,7 +50,10 @@ class SamplingRunner:
         self.num_diffusion_steps: int = cfg.num_diffusion_steps
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
-        self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path)
+        self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path,
+                                                             weights=cfg.get("weights", "auto"))
+        logging.info(f"Running on the {'averaged (EMA)' if self.score_model.weights_loaded == 'ema' else 'raw'} weights of "
+                     f"{best_checkpoint_path}.")
         self.score_model.to(device=torch.device("cuda", self.dev_index))
         self.sampler = instantiate(cfg.sampler)(score_model=self.score_model)
         # metrics against the training set, on the main rank only (reference cmd/sample.py:62-65)

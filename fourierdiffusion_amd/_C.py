@@ -81,6 +81,7 @@ _PROTOS = {
     "fd_score_create_ex": (C.c_int, [_vp, C.POINTER(ModelDims), C.c_int, C.c_int, C.POINTER(_vp)]),
     "fd_score_destroy": (C.c_int, [_vp]),
     "fd_score_prepare": (C.c_int, [_vp, _vp, _vp]),
+    "fd_score_rebind": (C.c_int, [_vp, _vp]),
     "fd_score_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "fd_score_plan": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
     "fd_score_set_train_mode": (C.c_int, [_vp, C.c_int]),
@@ -121,6 +122,9 @@ _PROTOS = {
     "fd_adamw_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_float, C.c_int64,
                                 C.c_int64, _vp]),
+    "fd_adamw_ema_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_int64, C.c_int, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, C.c_float, _vp, C.c_float, C.c_float, C.c_int64,
+                                    C.c_int64, _vp]),
     "fd_comm_unique_id": (C.c_int, [_vp]),
     "fd_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "fd_comm_destroy": (C.c_int, [_vp]),

@@ -41,6 +41,11 @@ def keys_drawn() -> int:
     return _state["keys_drawn"]
 
 
+def set_keys_drawn(n: int) -> None:
+    """Put the counter back next to a restored torch generator state (the Trainer's second validation pass)."""
+    _state["keys_drawn"] = int(n)
+
+
 def discard_keys(n: int) -> None:
     for _ in range(int(n)):
         next_key()

@@ -782,6 +782,20 @@ extern "C" int fd_score_prepare(fd_score* m, const float* params, void* stream) 
     return FD_OK;
 }
 
+// fd_score_prepare without the in-place renormalisation: for a buffer that HAS been prepared since it last changed (the model's
+// swap between its raw and its averaged weights, ScoreModule.use_ema).  Renormalising rows that already sit at the bound moves
+// their last bits, so a second fd_score_prepare would not give the weights back bit for bit.
+extern "C" int fd_score_rebind(fd_score* m, const float* params) {
+    if (!m) return FD_ERR_ARG;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, params != nullptr, "fd_score_rebind: null params");
+    if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_score_rebind: call fd_score_prepare first");
+    m->params = const_cast<float*>(params);
+    m->prep_event_bound = false;      // (no kernel of this call to wait for: the training forward records its own event)
+    m->bf16_stale = true;
+    return FD_OK;
+}
+
 extern "C" int fd_score_forward(fd_score* m, const float* x, const float* t, float* out, int B, int mode,
                                 void* stream) {
     if (!m) return FD_ERR_ARG;

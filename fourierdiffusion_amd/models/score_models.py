@@ -9,9 +9,13 @@ fused pass and the data-parallel gradient exchange is one flat RCCL all-reduce.
 
 No autograd graph is built: ``forward`` in training mode keeps activations inside the engine and
 ``backward(dscore)`` accumulates into ``self.grads`` (same flat layout).
+
+Extension (not in the reference): an exponential moving average of the weights lives next to them in a second flat buffer
+(``ema_parameters``, filled by ``FusedAdamW(ema_decay=...)``); ``use_ema()`` runs every engine call on it.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -82,6 +86,11 @@ class ScoreModule:
                                    self.dim_feedforward)
         self._layout, self._nparams = _C.score_layout(self._dims, self._backbone, self._d_mlp)
         self._flat = torch.zeros(self._nparams, dtype=torch.float32)
+        self._ema: Optional[torch.Tensor] = None              # averaged weights, same layout (enable_ema)
+        self._ema_scope: Optional[torch.Tensor] = None        # inside use_ema(): the raw buffer that `_flat` stopped naming
+        self._ema_meta: Optional[Dict[str, Any]] = None       # {"decay", "warmup", "num_updates"}, kept current by the optimizer
+        self._other_dirty = True                              # `_dirty` of the buffer `_flat` does not name at the moment
+        self._rebind = False                                  # the engine handle still points at the other buffer
         self._grads: Optional[torch.Tensor] = None
         self._zero_pending = False
         self._views: "OrderedDict[str, torch.Tensor]" = OrderedDict()
@@ -97,6 +106,10 @@ class ScoreModule:
         for name, off, numel, shape, trainable in self._layout:
             self._views[name] = self._flat[off:off + numel].view(*shape)
             self._trainable[name] = trainable
+
+    def _named_copies(self, flat: torch.Tensor) -> "OrderedDict[str, torch.Tensor]":
+        return OrderedDict((name, flat[off:off + numel].view(*shape).detach().clone())
+                           for name, off, numel, shape, _ in self._layout)
 
     def _init_parameters(self) -> None:
         """Same initialisers, drawn from torch's global generator in the same order as the reference's
@@ -173,6 +186,76 @@ class ScoreModule:
         """Call after writing into ``flat_parameters`` / the views (e.g. an optimizer step)."""
         self._dirty = True
 
+    # ------------------------------------------------------------------ averaged weights (EMA; not in the reference)
+    @property
+    def ema_parameters(self) -> Optional[torch.Tensor]:
+        """The averaged weights: a flat fp32 buffer with the layout and device of ``flat_parameters``; None until ``enable_ema()``."""
+        return self._ema
+
+    def enable_ema(self) -> torch.Tensor:
+        """Allocate the averaged weights as a copy of the current ones (idempotent); returns the buffer."""
+        if self._ema is None:
+            if self._ema_scope is not None:
+                raise _C.FdError("enable_ema() inside use_ema()")
+            self._ema = self._flat.detach().clone()
+            self._other_dirty = True
+        return self._ema
+
+    def ema_state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        """The averaged weights under the names and shapes of ``state_dict()``."""
+        if self._ema is None:
+            raise _C.FdError("this model has no averaged weights: train with FusedAdamW(ema_decay=...) / Trainer(ema_decay=...), "
+                             "call enable_ema(), or load a checkpoint that has an 'ema_state_dict'")
+        return self._named_copies(self._ema)
+
+    def load_ema_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True) -> None:
+        missing = [k for k in self._views if k not in state_dict]
+        unexpected = [k for k in state_dict if k not in self._views]
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"Error(s) in loading ema state_dict: missing {missing}, unexpected {unexpected}")
+        ema = self.enable_ema()
+        for name, off, numel, shape, _ in self._layout:
+            if name in state_dict:
+                src = state_dict[name]
+                if tuple(src.shape) != tuple(shape):
+                    raise RuntimeError(f"size mismatch for {name}: {tuple(src.shape)} vs {tuple(shape)}")
+                ema[off:off + numel].view(*shape).copy_(src.to(device=ema.device, dtype=torch.float32))
+        self.mark_ema_changed()
+
+    def mark_ema_changed(self) -> None:
+        """Call after writing into ``ema_parameters`` (the optimizer step does)."""
+        if self._ema_scope is not None:
+            self._dirty = True
+        else:
+            self._other_dirty = True
+
+    @contextlib.contextmanager
+    def use_ema(self):
+        """Inside the scope every engine call (forward, the samplers, likelihood, impute) and ``state_dict()`` see the averaged
+        weights; on exit -- also by exception -- the raw weights are back bit for bit.  No copy: ``flat_parameters`` names the
+        other buffer and the views are rebound; the engine handle caches only the parameter pointer and the images derived from
+        it, both of which the next engine call renews: through fd_score_prepare when the buffer changed since it was last
+        prepared (which, as on the raw weights, renormalises the rows of the positional table above max_norm in place), else
+        through fd_score_rebind, which leaves the buffer alone -- a second renormalisation would move the last bits of rows at
+        the bound.  Not re-entrant; an optimizer step inside the scope raises."""
+        if self._ema_scope is not None:
+            raise _C.FdError("use_ema() is already active (the scope does not nest)")
+        if self._ema is None:
+            raise _C.FdError("use_ema(): this model has no averaged weights -- train with FusedAdamW(ema_decay=...) / "
+                             "Trainer(ema_decay=...), or load a checkpoint that has an 'ema_state_dict'")
+        self._ema_scope, self._flat = self._flat, self._ema
+        self._swapped()
+        try:
+            yield self
+        finally:
+            self._flat, self._ema_scope = self._ema_scope, None
+            self._swapped()
+
+    def _swapped(self) -> None:
+        self._bind_views()
+        self._dirty, self._other_dirty = self._other_dirty, self._dirty
+        self._rebind = not self._rebind        # (in and out again without an engine call in between: the handle never noticed)
+
     # ------------------------------------------------------------------ device / mode
     @property
     def device(self) -> torch.device:
@@ -183,8 +266,13 @@ class ScoreModule:
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if device != self._flat.device:
+            if self._ema_scope is not None:
+                raise _C.FdError("ScoreModule.to() inside use_ema()")
             self._release()
             self._flat = self._flat.to(device)
+            if self._ema is not None:
+                self._ema = self._ema.to(device)
+                self._other_dirty = True
             self.grads = None
             self._bind_views()
             self._dirty = True
@@ -226,12 +314,15 @@ class ScoreModule:
             rc = _C.lib().fd_score_create_ex(ctx, C.byref(self._dims), self._backbone, self._d_mlp, C.byref(h))
             _C.check(rc, ctx)
             self._handle = h
-            self._dirty = True
+            self._dirty = self._other_dirty = True
             self._train_mode_set = None
         if self._dirty:
             rc = _C.lib().fd_score_prepare(self._handle, self._flat.data_ptr(), _C.stream_of(self._flat))
             _C.check(rc, ctx)
-            self._dirty = False
+            self._dirty = self._rebind = False
+        elif self._rebind:
+            _C.check(_C.lib().fd_score_rebind(self._handle, self._flat.data_ptr()), ctx)
+            self._rebind = False
         if self._train_mode_set != self.train_precision:
             rc = _C.lib().fd_score_set_train_mode(self._handle, _PRECISIONS[self.train_precision])
             if rc == -5 and self.train_precision == "bf16":       # FD_ERR_UNSUPPORTED: dims without bf16 training kernels
@@ -429,19 +520,44 @@ class ScoreModule:
     def save_checkpoint(self, path, **extra) -> None:
         # Lightning's layout (state_dict keys of the reference model, ctor hyper-parameters incl. the scheduler object) plus
         # the bookkeeping keys its load_from_checkpoint expects, so the reference can load checkpoints written here
+        # ("state_dict" is always the RAW weights, also when written inside use_ema(); the averaged ones, when there are any, go
+        #  under two extra keys the reference's loader ignores: tensors and plain numbers only, nothing it could not unpickle)
+        raw = self._ema_scope if self._ema_scope is not None else self._flat
         ckpt = {"epoch": 0, "global_step": 0, "pytorch-lightning_version": "2.1.0",
-                "state_dict": OrderedDict((k, t.cpu()) for k, t in self.state_dict().items()),
+                "state_dict": OrderedDict((k, t.cpu()) for k, t in self._named_copies(raw).items()),
                 "hparams_name": "kwargs", "hyper_parameters": dict(self.hparams), "engine": "fourierdiffusion_amd"}
+        if self._ema is not None:
+            meta = self._ema_meta or {}
+            ckpt["ema_state_dict"] = OrderedDict((k, t.cpu()) for k, t in self._named_copies(self._ema).items())
+            ckpt["ema"] = {"decay": float(meta.get("decay", 0.0)), "warmup": bool(meta.get("warmup", False)),
+                           "num_updates": int(meta.get("num_updates", 0))}
         ckpt.update(extra)
         torch.save(ckpt, path)
 
     @classmethod
-    def load_from_checkpoint(cls, checkpoint_path, map_location=None, **overrides) -> "ScoreModule":
+    def load_from_checkpoint(cls, checkpoint_path, map_location=None, weights: str = "raw", **overrides) -> "ScoreModule":
+        """weights: "raw" -- the trained weights, with the averaged ones attached (``ema_parameters``) when the file has them;
+        "ema" -- the averaged weights AS the model's weights (a plain inference model; raises when the file has none);
+        "auto" -- "ema" when the file has them, else "raw".  ``weights_loaded`` says which of the two the model runs."""
+        if weights not in ("raw", "ema", "auto"):
+            raise ValueError(f"load_from_checkpoint: weights must be 'raw', 'ema' or 'auto', got {weights!r}")
         ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
+        has_ema = "ema_state_dict" in ckpt
+        if weights == "ema" and not has_ema:
+            raise _C.FdError(f"{checkpoint_path} has no averaged weights ('ema_state_dict'): it was trained without ema_decay; "
+                             "load it with weights='raw' or 'auto'")
         hp = dict(ckpt["hyper_parameters"])
         hp.update(overrides)
         model = cls(**hp)
-        model.load_state_dict(ckpt["state_dict"])
+        if weights != "raw" and has_ema:
+            model.load_state_dict(ckpt["ema_state_dict"])
+            model.weights_loaded = "ema"
+        else:
+            model.load_state_dict(ckpt["state_dict"])
+            model.weights_loaded = "raw"
+            if has_ema:
+                model.load_ema_state_dict(ckpt["ema_state_dict"])
+                model._ema_meta = dict(ckpt.get("ema") or {})
         if map_location is not None:
             model.to(map_location)
         return model

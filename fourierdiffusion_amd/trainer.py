@@ -1,9 +1,12 @@
 """Training loop standing in for `pl.Trainer` (absent from the image) -- the subset the reference configures
 (cmd/conf/trainer/default.yaml: max_epochs, gradient_clip_val, callbacks; Lightning defaults otherwise):
 per batch  zero_grad -> training_step (engine forward + backward) -> [RCCL all-reduce] -> fused clip+AdamW -> LR step;
-per epoch  validation loss with the training statistics, callbacks (checkpoint on val/loss, LR monitor, sampling)."""
+per epoch  validation loss with the training statistics, callbacks (checkpoint on val/loss, LR monitor, sampling).
+Extension (not in the reference): `ema_decay` averages the weights inside the optimizer pass, and with `ema_eval` the validation
+loss, the checkpoint choice and the sampling callback describe the averaged model (the raw one is logged as val/loss_raw)."""
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 import os
@@ -57,11 +60,23 @@ class ModelCheckpoint(Callback):
         self.best_score, self.best_model_path = score, str(path)
 
 
+def _rng_snapshot(device: torch.device):
+    return torch.get_rng_state(), (torch.cuda.get_rng_state(device) if device.type == "cuda" else None), _rng.keys_drawn()
+
+
+def _rng_restore(device: torch.device, snap) -> None:
+    torch.set_rng_state(snap[0])
+    if snap[1] is not None:
+        torch.cuda.set_rng_state(snap[1], device)
+    _rng.set_keys_drawn(snap[2])
+
+
 class Trainer:
     def __init__(self, accelerator: str = "auto", max_epochs: int = 200, gradient_clip_val: Optional[float] = None,
                  enable_progress_bar: bool = True, logger: Any = None, callbacks: Optional[List[Callback]] = None,
                  accumulate_grad_batches: int = 1, default_root_dir: Optional[str] = None,
                  grad_exchange: str = "rccl", log_every_n_steps: int = 50, limit_train_batches: Optional[int] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_eval: bool = True,
                  **unused: Any) -> None:
         self.max_epochs = max_epochs
         self.gradient_clip_val = gradient_clip_val
@@ -73,6 +88,9 @@ class Trainer:
         self.log_every_n_steps = log_every_n_steps
         self.limit_train_batches = limit_train_batches
         self.enable_progress_bar = enable_progress_bar
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_eval = bool(ema_eval)
         self.current_epoch = 0
         self.global_step = 0
         self.logged: Dict[str, float] = {}
@@ -92,6 +110,11 @@ class Trainer:
         opt_cfg = model.configure_optimizers()
         self.optimizer = opt_cfg["optimizer"]
         self.optimizer.max_grad_norm = self.gradient_clip_val
+        if self.ema_decay is not None:
+            self.optimizer.enable_ema(self.ema_decay, self.ema_warmup)
+        # the scope the evaluation half of an epoch runs in: the averaged weights when there are any and ema_eval asks for them
+        ema_eval = self.ema_decay is not None and self.ema_eval
+        eval_scope = model.use_ema if ema_eval else contextlib.nullcontext
         lr_lambda = opt_cfg["lr_scheduler"]["scheduler"]
         for cb in self.callbacks:
             cb.on_train_start(self, model)
@@ -142,19 +165,33 @@ class Trainer:
                 optimizer_step()                                   # the accumulation window is not full
             train_loss = float(torch.stack(losses).mean().item()) if losses else float("nan")
             self.logged["train/loss"] = exchange.all_reduce_scalar_mean(train_loss)
-            for cb in self.callbacks:
-                cb.on_train_epoch_end(self, model)
-            # ---- validate (every rank evaluates the full validation set: no exchange needed)
-            vals, weights = [], []
-            for bi, batch in enumerate(datamodule.val_dataloader()):
-                vals.append(model.validation_step(batch, bi))
-                weights.append(len(batch))
-            if vals:
-                w = torch.tensor(weights, dtype=torch.float64)
-                v = torch.stack([x.double().cpu() for x in vals])
-                self.logged["val/loss"] = float((v * w).sum() / w.sum())
-            for cb in self.callbacks:
-                cb.on_validation_end(self, model)
+
+            def validate(key: str) -> None:
+                # (every rank evaluates the full validation set: no exchange needed)
+                vals, weights = [], []
+                for bi, batch in enumerate(datamodule.val_dataloader()):
+                    vals.append(model.validation_step(batch, bi))
+                    weights.append(len(batch))
+                if vals:
+                    w = torch.tensor(weights, dtype=torch.float64)
+                    v = torch.stack([x.double().cpu() for x in vals])
+                    self.logged[key] = float((v * w).sum() / w.sum())
+
+            with eval_scope():
+                for cb in self.callbacks:
+                    cb.on_train_epoch_end(self, model)
+            # ---- validate
+            if ema_eval:
+                # The raw weights first, then the generators go back to where this pass found them: the averaged weights are
+                # evaluated on the SAME timesteps and noise, and the run draws exactly what a run without the average draws -- its
+                # raw trajectory is that run's bit for bit.
+                snap = _rng_snapshot(model.device)
+                validate("val/loss_raw")
+                _rng_restore(model.device, snap)
+            with eval_scope():
+                validate("val/loss")
+                for cb in self.callbacks:
+                    cb.on_validation_end(self, model)
             self.history.append(dict(self.logged, epoch=epoch))
             if self.dist.is_main and self.enable_progress_bar:
                 logging.info("epoch %d  train/loss %.5f  val/loss %.5f  lr %.2e", epoch, self.logged["train/loss"],

@@ -223,6 +223,11 @@ int fd_score_destroy(fd_score* m);
  * Must be called after every change of params (load, optimizer step) before forward.
  * The engine keeps the pointer `params` (no copy of the fp32 masters). */
 int fd_score_prepare(fd_score* m, const float* params, void* stream);
+/* Point a prepared model at another flat parameter buffer that has itself been through fd_score_prepare since it last changed
+ * (not in the reference: the swap between the raw and the averaged weights, fd_adamw_ema_step): the pointer is replaced and the
+ * derived images are marked stale, but the positional table is NOT renormalised again -- a second renormalisation moves the last
+ * bits of rows that sit at the bound, and the swap must give the weights back bit for bit.  No device work. */
+int fd_score_rebind(fd_score* m, const float* params);
 
 #define FD_MODE_F32 0    /* fp32 parity path (exact-f32 arithmetic) */
 #define FD_MODE_BF16 1   /* bf16 MFMA operands, fp32 accumulate / residual / LN / softmax */
@@ -450,6 +455,17 @@ int fd_adamw_step(fd_ctx* ctx, float* params, const float* grads, float* exp_avg
                   float* exp_avg_sq, int64_t n, int step, float lr, float beta1, float beta2,
                   float eps, float weight_decay, const float* sqnorm, float max_norm,
                   float grad_scale, int64_t frozen_begin, int64_t frozen_end, void* stream);
+/* fd_adamw_ema_step: fd_adamw_step of the a11 row plus an exponential moving average of the weights in the same pass (an extension,
+ *                 NOT in the reference: the ExponentialMovingAverage score-SDE code bases train with).  params, exp_avg and
+ *                 exp_avg_sq come out bit-identical to fd_adamw_step on the same inputs; with p' the updated parameter,
+ *                 ema[i] = fmaf(ema_decay, ema[i], (1 - ema_decay) * p'[i]), 0 <= ema_decay <= 1 (0: ema == p' bit for bit,
+ *                 1: ema untouched).  ema: device float[n], same layout as params.  The frozen range and the on-device skip
+ *                 leave ema untouched together with params and the moments.  36 B/param of traffic instead of 28. */
+int fd_adamw_ema_step(fd_ctx* ctx, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                      float* ema, float ema_decay,
+                      int64_t n, int step, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      const float* sqnorm, float max_norm, float grad_scale,
+                      int64_t frozen_begin, int64_t frozen_end, void* stream);
 
 /* ----------------------------------------------------- (e) multi-GPU exchange
  * Data-parallel gradient all-reduce over RCCL/xGMI on ONE flat fp32 buffer.
