@@ -89,6 +89,7 @@ _PROTOS = {
     "fd_score_backward": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "fd_score_input_vjp": (C.c_int, [_vp, _vp, _vp, _vp]),
     "fd_score_train_plan": (C.c_int, [_vp, C.c_int, C.c_char_p, C.POINTER(C.c_int)]),
+    "fd_score_train_cluster_xcds": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _vp]),
     "fd_score_train_dsm_supported": (C.c_int, [_vp, C.c_int]),
     "fd_score_train_dsm": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_uint64,
                                      _vp, _vp, C.c_int, _vp]),

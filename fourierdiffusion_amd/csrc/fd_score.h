@@ -42,6 +42,10 @@ struct fd_score {
     uint64_t saved_seed = 0, saved_offset = 0;
     const float* saved_x = nullptr;
     const float* saved_t = nullptr;
+    // this model's last training forward that ran every layer as ONE persistent launch: the context's count of training forwards then, the
+    // batch, the tiles per series and the value every tile flag carries behind it (epoch * 64 + layers published); 0 = none yet
+    unsigned long long trp_serial = 0, trp_value = 0;
+    int trp_B = 0, trp_KT = 0;
     int saved_mask_set = 0;         // which of the two sets of dropout-decision buffers the saved forward used (fd_train_bf16.hip)
     bool saved_bf16 = false;        // the training forward ran the bf16 MFMA kernels (fd_train_bf16.hip)
     int train_mode = 0;             // FD_MODE_F32 (exact-f32 kernels) or FD_MODE_BF16 for fd_score_forward_train
@@ -106,6 +110,7 @@ bool fd_train_bf16_supported(const fd_score* m);
 bool fd_score_train_dsm_bf16_supported(const fd_score* m, int B);
 int fd_train_bf16_token_splits(const fd_score* m, int B, int* nblk);
 void fd_train_bf16_forward_plan(const fd_score* m, int B, char* out, size_t n);   // "k_tr_fwd_layers NT=.. x .." or "2 kernels per layer"
+int fd_train_bf16_cluster_xcds(fd_score* m, int B, int* xcd, hipStream_t s);      // host copy of the tile flags' publisher XCDs
 int fd_score_forward_train_bf16(fd_score* m, const float* x, const float* t, float* out, int B, float p, uint64_t seed,
                                 uint64_t offset, hipStream_t s);
 int fd_score_backward_bf16(fd_score* m, const float* dout, float* grads, int accumulate, hipStream_t s);

@@ -826,6 +826,7 @@ extern "C" int fd_score_forward_train(fd_score* m, const float* x, const float* 
         return fd_fail(ctx, FD_ERR_UNSUPPORTED, "fd_score_forward_train: bf16 training kernels are not instantiated for this "
                        "model (needs bf16 weight images -- fd_score_plan says which widths have them --, dim_ff %% 1024 == 0, dim_ff <= 2048, "
                        "max_len <= 1024); select FD_MODE_F32");
+    ++ctx->tr_fwd_serial;               // (whatever the flags of an earlier persistent forward said is history: fd_score_train_cluster_xcds)
     int rc = (m->backbone != FD_BACKBONE_TRANSFORMER)
                  ? fd_bb_forward(m, x, t, out, B, (hipStream_t)stream, true, dropout_p, seed, offset)
                  : (bf16 ? fd_score_forward_train_bf16(m, x, t, out, B, dropout_p, seed, offset, (hipStream_t)stream)
@@ -891,6 +892,16 @@ extern "C" int fd_score_train_plan(fd_score* m, int B, char* out, int* token_spl
     snprintf(out, 192, "bf16 training: forward %s; backward 3 kernels per layer, k_tr_wgrad token splits TS=%d over %d 32-token blocks, fused loss head %s",
              fwd, ts, nblk, (m->prepared && fd_score_train_dsm_bf16_supported(m, B) && !getenv("FDIFF_TRAIN_DSM_UNFUSED")) ? "yes" : "no");
     return FD_OK;
+}
+
+// Where the clusters of the last persistent training forward ran (include/fdiff_hip.h): the publisher XCD of every (series, token
+// tile), read back from the tile flags the kernel leaves behind.
+extern "C" int fd_score_train_cluster_xcds(fd_score* m, int B, int* xcd, void* stream) {
+    if (!m) return FD_ERR_ARG;
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, xcd, "fd_score_train_cluster_xcds: null pointer");
+    FD_REQUIRE(ctx, B > 0, "fd_score_train_cluster_xcds: B=%d", B);
+    return fd_train_bf16_cluster_xcds(m, B, xcd, (hipStream_t)stream);
 }
 
 // Arithmetic of fd_score_forward_train / fd_score_backward: FD_MODE_F32 = exact-f32 kernels (parity anchor, any model),

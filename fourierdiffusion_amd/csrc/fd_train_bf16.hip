@@ -2492,8 +2492,7 @@ TrDims make_dims(const fd_score* m, int B, float p, uint64_t seed) {
     if (p > 0.f && d.thr16 == 0) d.thr16 = 1;
     d.keep_scale = (p > 0.f) ? (float)(65536.0 / (65536.0 - (double)d.thr16)) : 1.0f;
     d.seed = seed;
-    static const int xcd_env = getenv("FDIFF_TR_XCD") ? atoi(getenv("FDIFF_TR_XCD")) : 1;      // (0: hardware order, A/B runs)
-    d.xcd = xcd_env;
+    { const char* e = getenv("FDIFF_TR_XCD"); d.xcd = e ? atoi(e) : 1; }      // (0: hardware order; read per call: a test switches it)
     d.fsplit = tr_fsplit_rule(m, d.M, d.F, false);      // (the forward launch applies its own rule, see there)
     { const char* e = getenv("FDIFF_TR_ROT"); d.norot = (e && atoi(e) == 0) ? 1 : 0; }      // (read per call: a test switches it)
     return d;
@@ -2807,6 +2806,10 @@ int tr_forward_t(fd_score* m, const float* x, const float* t, float* out, int B,
                 // the launch is the forward's last reader of the decision buffers: their "readers done" event is its stop event
                 if ((lean & 2) && p > 0.f) readers_done = ctx->tr_readers_event[mask_set];
                 if (int rc = fd_trp_forward(m, d, ta, trp_nt, trp_nq, trp_spl, s, readers_done)) return rc;
+                if (L > 1) {        // (what fd_score_train_cluster_xcds reads back: every tile flag now carries the last published layer)
+                    m->trp_serial = ctx->tr_fwd_serial; m->trp_B = B; m->trp_KT = d.KT;
+                    m->trp_value = ta.epoch * 64ull + (unsigned long long)(L - 1);
+                }
             }
         }
     }
@@ -3203,6 +3206,7 @@ int fd_score_forward_train_bf16(fd_score* m, const float* x, const float* t, flo
     fd_ctx* ctx = m->ctx;
     if (int rc = fd_train_async_check(ctx)) return rc;
     if (!fd_train_bf16_supported(m)) return fd_fail(ctx, FD_ERR_UNSUPPORTED, "bf16 training path unsupported for this model");
+    ++ctx->tr_fwd_serial;               // (tr_forward_t stamps the model with it when the layers run as one persistent launch)
     // The optimizer step made the bf16 weight images stale.  Rebuilding them (~50 us of small kernels) needs nothing but the
     // parameters, and the step's prologue on `s` (time embedding, embedding, first layer's operand preparation) does not need
     // the images: the rebuild runs beside it on the second side stream and joins `s` in front of the first attention kernel.
@@ -3293,6 +3297,28 @@ void fd_train_bf16_forward_plan(const fd_score* m, int B, char* out, size_t n) {
     const int nt = (mode != 0 && m->d.num_layers > 0 && !m->ctx->trp_disabled) ? fd_trp_tiles(m, B, &nq, &spl) : 0;
     if (nt) snprintf(out, n, "k_tr_fwd_layers NT=%d, %d x %d workgroups%s", nt, nq, std::min(B, spl), mode == 2 ? " per layer" : "");
     else snprintf(out, n, "2 kernels per layer%s", m->ctx->trp_disabled ? " (persistent form disabled after a timeout)" : "");
+}
+// The XCD every (series, token tile) of the last persistent training forward was published from: the low four bits of the tile flags
+// (fd_train_persist.hip), copied behind everything queued on `s`.  Host only: the kernel writes nothing for this.
+int fd_train_bf16_cluster_xcds(fd_score* m, int B, int* xcd, hipStream_t s) {
+    fd_ctx* ctx = m->ctx;
+    if (m->trp_serial == 0 || m->trp_serial != ctx->tr_fwd_serial)
+        return fd_fail(ctx, FD_ERR_STATE, "fd_score_train_cluster_xcds: the last training forward of this context was not a persistent "
+                       "launch of this model over more than one layer (FDIFF_TR_PERSIST=1)");
+    FD_REQUIRE(ctx, B == m->trp_B, "fd_score_train_cluster_xcds: B=%d, the last persistent training forward ran B=%d", B, m->trp_B);
+    const size_t n = (size_t)B * m->trp_KT;
+    if (!ctx->trp_flags || n > ctx->trp_flag_count) return fd_fail(ctx, FD_ERR_STATE, "fd_score_train_cluster_xcds: no tile flags");
+    std::vector<unsigned long long> h(n);
+    FD_HIP(ctx, hipMemcpyAsync(h.data(), ctx->trp_flags, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) {
+        if ((h[i] >> 4) != m->trp_value)
+            return fd_fail(ctx, FD_ERR_STATE, "fd_score_train_cluster_xcds: the flag of series %d, tile %d carries %llu, not the last launch's %llu "
+                           "(a cluster wait gave up, or the publisher never ran)", (int)(i / m->trp_KT), (int)(i % m->trp_KT),
+                           h[i] >> 4, m->trp_value);
+        xcd[i] = (int)(h[i] & 15ull);
+    }
+    return FD_OK;
 }
 bool fd_score_train_dsm_bf16_supported(const fd_score* m, int B) {
     int TS, kmax;

@@ -370,6 +370,16 @@ class ScoreModule:
         _C.check(_C.lib().fd_score_train_plan(h, int(batch_size), buf, C.byref(ts)), ctx)
         return buf.value.decode(), ts.value
 
+    def train_cluster_xcds(self, batch_size: int) -> torch.Tensor:
+        """(batch_size, ceil(max_len / 16)) int32 CPU tensor: the XCD that published each 16-token tile of each series in the last
+        training forward, which must have been the persistent bf16 form at this batch size -- fd_score_train_cluster_xcds.  A row
+        with one value is a cluster that exchanged its rows through that XCD's L2."""
+        ctx, h = self._engine()
+        B, KT = int(batch_size), (self.max_len + 15) // 16
+        buf = (C.c_int * (max(B, 1) * KT))()
+        _C.check(_C.lib().fd_score_train_cluster_xcds(h, B, buf, _C.stream_of(self._flat)), ctx)
+        return torch.tensor(list(buf), dtype=torch.int32).view(B, KT)
+
     # ------------------------------------------------------------------ forward / backward
     def forward(self, batch: DiffusableBatch) -> torch.Tensor:
         X = batch.X

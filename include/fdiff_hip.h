@@ -260,6 +260,14 @@ int fd_score_set_train_mode(fd_score* m, int mode);
 /* The training launch plan of a batch of B series, nothing launched: out (>= 192 bytes) names the arithmetic and, on the bf16
  * path, the token splits of the weight-gradient kernel (also in *token_splits, nullable; 0 on the exact-f32 path). */
 int fd_score_train_plan(fd_score* m, int B, char* out, int* token_splits);
+/* Where the last training forward's clusters ran, for the parity tests (no reference counterpart): when the last training forward
+ * on the model's context was the persistent bf16 form of THIS model at batch B (every encoder layer in one launch, a cluster of
+ * workgroups per series), waits for `stream` and writes the XCD that published each 16-token tile of each series into the HOST
+ * array xcd[B * ceil(max_len / 16)], laid out [series][tile].  A series whose tiles all carry one XCD exchanged its rows through
+ * that XCD's L2, any other one through the memory-side path.  FD_ERR_ARG for a null pointer or a B other than that forward's;
+ * FD_ERR_STATE when the last training forward was not that form (per-layer kernels, exact-f32 path, one layer, another model,
+ * none yet) or a tile flag does not carry that launch's value. */
+int fd_score_train_cluster_xcds(fd_score* m, int B, int* xcd, void* stream);
 
 /* Training forward: keeps activations in the ctx workspace for fd_score_backward.
  * dropout_p > 0 applies the four dropout sites of nn.TransformerEncoderLayer with masks
