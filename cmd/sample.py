@@ -20,6 +20,7 @@ import yaml  # noqa: E402
 
 from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
+from fourierdiffusion_amd.sampling.sampler import parse_labels  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, env, init_process_group, shard_range  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
@@ -66,7 +67,14 @@ class SamplingRunner:
         num_batches = max(1, self.num_samples // bs)
         lo, hi = shard_range(num_batches, self.dist.rank, self.dist.world)       # independent units: no exchange
         n_local = (hi - lo) * min(bs, self.num_samples)
-        X = self.sampler.sample(num_samples=n_local, num_diffusion_steps=self.num_diffusion_steps) if n_local else None
+        X = labels = None
+        if n_local:
+            guide = {}
+            if self.score_model.n_classes > 0 or self.sampler.labels is not None or self.sampler.cfg_scale != 1.0:
+                # sampler.labels: a class, `balanced` or null; the chosen labels are written next to the samples
+                labels = parse_labels(self.sampler.labels, n_local, self.score_model.n_classes)
+                guide = {"y": labels, "cfg_scale": self.sampler.cfg_scale}
+            X = self.sampler.sample(num_samples=n_local, num_diffusion_steps=self.num_diffusion_steps, **guide)
         if X is not None:
             if self.datamodule.standardize:
                 feature_mean, feature_std = self.datamodule.feature_mean_and_std
@@ -79,8 +87,10 @@ class SamplingRunner:
         if self.dist.world > 1:
             import torch.distributed as dist
             parts = [None] * self.dist.world
-            dist.all_gather_object(parts, X)                                        # host-side gather of the results
-            X = torch.cat([p for p in parts if p is not None], dim=0)
+            dist.all_gather_object(parts, (X, labels))                              # host-side gather of the results
+            X = torch.cat([p[0] for p in parts if p[0] is not None], dim=0)
+            lab = [p[1] for p in parts if p[0] is not None]
+            labels = torch.cat(lab, dim=0) if lab and all(v is not None for v in lab) else None
         if self.dist.is_main:
             results = {"num_samples": int(X.shape[0]), "sample_mean": float(X.mean()), "sample_std": float(X.std())}
             if self.metrics is not None:
@@ -88,6 +98,8 @@ class SamplingRunner:
             logging.info(f"Saving samples ands metrics to {self.save_dir}.\n{dict_to_str(results)}")
             yaml.dump(data=results, stream=open(self.save_dir / "results.yaml", "w"))
             torch.save(X, self.save_dir / "samples.pt")
+            if labels is not None:
+                torch.save(labels, self.save_dir / "labels.pt")
 
 
 def main(argv=None) -> None:

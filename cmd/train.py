@@ -24,6 +24,22 @@ from fourierdiffusion_amd.utils.callbacks import SamplingCallback  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_training_params  # noqa: E402
 
 
+def check_labels(score_model, datamodule) -> None:
+    """A class-conditional model needs a datamodule with labels 0 .. n_classes - 1: fail before the first step, not inside it."""
+    K = int(getattr(score_model, "n_classes", 0))
+    if K <= 0:
+        return
+    y = getattr(datamodule, "y_train", None)
+    name = type(datamodule).__name__
+    if y is None:
+        raise ValueError(f"score_model.n_classes = {K}, but {name} has no labels (y_train is None): use a labelled datamodule "
+                         "(datamodule=synthetic_classes, datamodule=ecg) or score_model.n_classes=0")
+    lo, hi = int(y.min()), int(y.max())
+    if lo < 0 or hi >= K:
+        raise ValueError(f"score_model.n_classes = {K}, but the labels of {name} lie in [{lo}, {hi}]: set "
+                         f"score_model.n_classes={hi + 1}")
+
+
 class TrainingRunner:
     def __init__(self, cfg) -> None:
         torch.manual_seed(cfg.random_seed)
@@ -42,6 +58,7 @@ class TrainingRunner:
         self.datamodule.setup("fit")
         if isinstance(self.score_model, partial):
             self.score_model = self.score_model(**get_training_params(self.datamodule, self.trainer))
+        check_labels(self.score_model, self.datamodule)
         for callback in self.trainer.callbacks:
             if isinstance(callback, SamplingCallback):
                 callback.setup_datamodule(datamodule=self.datamodule)

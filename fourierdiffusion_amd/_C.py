@@ -80,6 +80,12 @@ _PROTOS = {
     "fd_score_layout_ex": (C.c_int, [C.POINTER(ModelDims), C.c_int, C.c_int, C.POINTER(ParamEntry), C.POINTER(C.c_int)]),
     "fd_score_create_ex": (C.c_int, [_vp, C.POINTER(ModelDims), C.c_int, C.c_int, C.POINTER(_vp)]),
     "fd_score_destroy": (C.c_int, [_vp]),
+    "fd_score_param_count_cond": (C.c_int64, [C.POINTER(ModelDims), C.c_int]),
+    "fd_score_layout_cond": (C.c_int, [C.POINTER(ModelDims), C.c_int, C.POINTER(ParamEntry), C.POINTER(C.c_int)]),
+    "fd_score_create_cond": (C.c_int, [_vp, C.POINTER(ModelDims), C.c_int, C.POINTER(_vp)]),
+    "fd_score_set_labels": (C.c_int, [_vp, _vp, C.c_int]),
+    "fd_score_set_label_dropout": (C.c_int, [_vp, C.c_float]),
+    "fd_label_dropout": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _vp]),
     "fd_score_prepare": (C.c_int, [_vp, _vp, _vp]),
     "fd_score_rebind": (C.c_int, [_vp, _vp]),
     "fd_score_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
@@ -115,6 +121,10 @@ _PROTOS = {
     "fd_sampler_run_dpm": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "fd_dpm_stage": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, C.c_int,
                                C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, C.c_float, _vp,
+                                     C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_ode_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_int, C.c_int,
+                                         _vp]),
     "fd_prior_logp": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run_adaptive": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
@@ -211,19 +221,29 @@ def model_dims(n_channels, max_len, d_model, n_head, num_layers, dim_ff=2048) ->
     return ModelDims(int(n_channels), int(max_len), int(d_model), int(n_head), int(num_layers), int(dim_ff))
 
 
-def score_layout(dims: ModelDims, backbone: int = 0, d_mlp: int = 0):
-    """[(name, offset, numel, shape, trainable)] + total float count, straight from the engine."""
+def score_layout(dims: ModelDims, backbone: int = 0, d_mlp: int = 0, n_classes: int = 0):
+    """[(name, offset, numel, shape, trainable)] + total float count, straight from the engine.  n_classes > 0 (transformer only):
+    the class-conditional layout, one trailing ``class_encoder.weight``."""
     n = C.c_int(0)
-    rc = lib().fd_score_layout_ex(C.byref(dims), backbone, d_mlp, None, C.byref(n))
+    if n_classes > 0:
+        def layout(arr):
+            return lib().fd_score_layout_cond(C.byref(dims), int(n_classes), arr, C.byref(n))
+    else:
+        def layout(arr):
+            return lib().fd_score_layout_ex(C.byref(dims), backbone, d_mlp, arr, C.byref(n))
+    rc = layout(None)
     if rc != 0:
         raise FdError(f"fd_score_layout failed ({rc}): bad model dims")
     arr = (ParamEntry * n.value)()
-    rc = lib().fd_score_layout_ex(C.byref(dims), backbone, d_mlp, arr, C.byref(n))
+    rc = layout(arr)
     if rc != 0:
         raise FdError(f"fd_score_layout failed ({rc})")
     out = []
     for e in arr:
         shape = (e.rows, e.cols) if e.cols else (e.rows,)
         out.append((e.name.decode(), int(e.offset), int(e.numel), shape, bool(e.trainable)))
-    total = int(lib().fd_score_param_count_ex(C.byref(dims), backbone, d_mlp))
+    if n_classes > 0:
+        total = int(lib().fd_score_param_count_cond(C.byref(dims), int(n_classes)))
+    else:
+        total = int(lib().fd_score_param_count_ex(C.byref(dims), backbone, d_mlp))
     return out, total

@@ -7,6 +7,12 @@ torch's generator: every engine call that needs noise draws ONE 62-bit key from 
 generator (host-side plumbing) and uses counters [rank_base, rank_base + n/4) under that key.
 ``torch.manual_seed(s)`` therefore reproduces a run exactly as it does for the reference, and
 data-parallel ranks (same seed) get disjoint counter ranges through ``set_rank``.
+
+Counter ranges under one key (offsets relative to the rank's base, ``rank << 56``):
+  perturbation / prior / step noise   [0, n / 4) of the call's own key (one key per call)
+  dropout site s of encoder layer l   [(4 l + s) << 40, (4 l + s + 1) << 40) of the training call's key (fd_dropout_site_offset)
+  label dropout (class conditioning)  [0xFFFF << 40, 0xFFFF << 40 + B / 4] of the same training call's key: the window of "layer
+                                      16383, site 3", which no encoder layer reaches; label b is lane b % 4 of counter b / 4
 """
 from __future__ import annotations
 

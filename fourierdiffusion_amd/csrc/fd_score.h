@@ -51,7 +51,33 @@ struct fd_score {
     int train_mode = 0;             // FD_MODE_F32 (exact-f32 kernels) or FD_MODE_BF16 for fd_score_forward_train
     uint64_t saved_ws_gen = 0;      // ctx->ws_gen right after the training forward carved the arena
     void* saved_ws = nullptr;       // arena base then (a regrow moves it)
+    // ---- class conditioning (fd_score_create_cond; not in the reference): class_encoder.weight (n_classes + 1, D) at cls_w, the
+    // LAST tensor of the layout; row n_classes is the null (unconditional) token.  n_classes == 0: an unlabelled model.
+    int n_classes = 0;
+    int64_t cls_w = 0;
+    const int* labels = nullptr;    // borrowed device int32[labels_B] (fd_score_set_labels), or null: every row reads the null token
+    int labels_B = 0;
+    float label_dropout = 0.f;      // training forwards replace a label by the null token with this probability (fd_score_set_label_dropout)
+    int* y_eff = nullptr;           // engine-owned device int32[y_eff_cap]: the labels the last training forward really used
+    int y_eff_cap = 0;
 };
+
+// the class-embedding operands of k_time_embed: y (B) int32 or null (every row the null token), table (K + 1, D) fp32; table == null:
+// an unlabelled model, nothing is added
+struct fd_cls {
+    const int* y = nullptr;
+    const float* table = nullptr;
+    int K = 0;
+};
+inline fd_cls fd_cls_eval(const fd_score* m) {      // the labels bound by fd_score_set_labels
+    return m->n_classes > 0 ? fd_cls{m->labels, m->params + m->cls_w, m->n_classes} : fd_cls{};
+}
+inline fd_cls fd_cls_train(const fd_score* m) {     // the labels behind label dropout (fd_labels_prepare_train)
+    return m->n_classes > 0 ? fd_cls{m->y_eff, m->params + m->cls_w, m->n_classes} : fd_cls{};
+}
+// Philox counters of label dropout under the training call's (seed, offset): label b is lane b % 4 of counter offset + kLabelCtrBase
+// + b / 4 -- the window of (layer 16383, site 3) in fd_dropout_site_offset's numbering, which no encoder layer reaches
+constexpr uint64_t kLabelCtrBase = (uint64_t)0xFFFF << 40;
 
 // activations kept by the training forward, carved from the ctx workspace
 struct fd_saved_layer {
@@ -74,7 +100,22 @@ struct fd_saved {
     std::vector<fd_saved_layer> layers;
 };
 
+// fd_cfg.hip: class conditioning (not in the reference)
+// FD_ERR_ARG when labels are bound for another batch size than B (who: the entry point's name in the message)
+int fd_labels_check(fd_score* m, int B, const char* who);
+// a labelled model's training forward: y_eff[0 .. B) = the bound labels (null token where none are bound or a label is out of range)
+// behind label dropout from Philox(seed, offset + kLabelCtrBase); a no-op on an unlabelled model
+int fd_labels_prepare_train(fd_score* m, int B, uint64_t seed, uint64_t offset, hipStream_t s);
+// d class_encoder.weight[k, :] (+)= sum over the rows b with y_eff[b] == k of dtemb[b, :], b ascending (no atomics); no-op when unlabelled
+int fd_class_table_backward(fd_score* m, const float* dtemb, float* grads, int B, int accumulate, hipStream_t s);
+void fd_labels_destroy(fd_score* m);
+
 // fd_score_f32.hip
+namespace fdf32 {
+void time_embed_cls(const float* t, const float* W, const float* Wd, const float* bd, float* temb, int B, int D, hipStream_t s, fd_cls cls);
+}
+int fd_time_embed_train_cls(const float* t, const float* W, const float* Wd, const float* bd, float* emb, float* temb, int B, int D,
+                            hipStream_t s, fd_cls cls);
 int fd_score_forward_f32(fd_score* m, const float* x, const float* t, float* out, int B, hipStream_t s,
                          bool train, float dropout_p, uint64_t seed, uint64_t offset);
 size_t fd_score_f32_workspace(const fd_score* m, int B, bool train);

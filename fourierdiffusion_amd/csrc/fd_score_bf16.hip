@@ -1172,6 +1172,9 @@ static MegaPlan plan_mega_nw(const fd_score* m, int B, int nw) {
 static MegaPlan plan_mega(const fd_score* m, int B) {
     const fd_bf16_images* im = m->bf16;
     if (!im || !im->mega) return MegaPlan{};
+    // a class-conditional model's time embedding differs per series; the persistent kernel shares one per step (temb_table): not ok,
+    // so that its forward takes the per-layer kernels and every loop runs step by step
+    if (m->n_classes > 0) return MegaPlan{};
     return plan_mega_nw(m, B, 8);
 }
 
@@ -1285,7 +1288,7 @@ int fd_score_forward_bf16(fd_score* m, const float* x, const float* t, float* ou
     if (int rc = fd_ws_reserve(ctx, fd_score_f32_workspace(m, B, false))) return rc;
     fd_ws ws(ctx);
     LayerBufs lb = carve_layer_bufs(m, B, ws);
-    fdf32::time_embed(t, P + m->tW, P + m->td_w, P + m->td_b, lb.temb, B, D, s);
+    fdf32::time_embed_cls(t, P + m->tW, P + m->td_w, P + m->td_b, lb.temb, B, D, s, fd_cls_eval(m));
     fdf32::embed(x, P + m->emb_w, P + m->emb_b, P + m->pos, lb.temb, lb.h0, M, T, C, D, s);
     if (int rc = bf16_layer_stack(m, B, lb, s)) return rc;
     fdgemm::linear_fwd(lb.h0, P + m->un_w, P + m->un_b, out, M, C, D, false, s);
@@ -1640,6 +1643,7 @@ static int run_layers(fd_score* m, const std::vector<Row>& rows, const float* G,
     fd_ctx* ctx = m->ctx;
     const fd_bf16_images* im = m->bf16;
     if (!im || !im->supported || !im->mega || getenv("FDIFF_SAMPLER_UNFUSED_STEP")) return FD_ERR_UNSUPPORTED;
+    if (m->n_classes > 0) return FD_ERR_UNSUPPORTED;      // (k_unembed_step_embed shares one time embedding per step, as the persistent kernel)
     const bool k35 = im->ks1 == 3 && im->dt == 5, k24 = im->ks1 == 2 && im->dt == 4, k12 = im->ks1 == 1 && im->dt == 2,
                k11 = im->ks1 == 1 && im->dt == 1;
     if (!(k35 || k24 || k12 || k11) || m->d.n_channels > 40 || m->d.d_model % 4 != 0) return FD_ERR_UNSUPPORTED;
@@ -1862,7 +1866,7 @@ extern "C" int fd_score_plan(fd_score* m, int B, int mode, char* out /* >= 192 b
         return FD_OK;
     }
     if (mode == FD_MODE_F32) {
-        snprintf(out, 192, "fp32 parity path (per-op kernels, fd_score_f32.hip)");
+        snprintf(out, 192, "fp32 parity path (per-op kernels, fd_score_f32.hip)%s", m->n_classes > 0 ? "; class-conditional" : "");
         return FD_OK;
     }
     FD_REQUIRE(ctx, mode == FD_MODE_BF16, "fd_score_plan: unknown mode %d", mode);
@@ -1878,11 +1882,13 @@ extern "C" int fd_score_plan(fd_score* m, int B, int mode, char* out /* >= 192 b
         const fd_bf16_images* im = m->bf16;
         const int hd = m->d.d_model / m->d.n_head;
         const bool fuse = im->mega && im->kso == 3 && (im->ks1 == 3 || im->ks1 == 2);
-        snprintf(out, 192, "per-layer bf16 kernels (k_attention_bf16 + k_ffn_ln): attention %s, k_ffn_ln<%d,%d>%s",
+        char cls[48] = "";
+        if (m->n_classes > 0) snprintf(cls, sizeof cls, "; class-conditional (%d classes)", m->n_classes);
+        snprintf(out, 192, "per-layer bf16 kernels (k_attention_bf16 + k_ffn_ln): attention %s, k_ffn_ln<%d,%d>%s%s",
                  hd > 32 ? "exact-f32 kernel (head_dim > 32) on bf16-MFMA projections"
                  : hd > 7 ? "bf16 k_attention_wide (one head per contraction) on bf16-MFMA projections"
                         : (im->mega ? "bf16 with fused Q/K/V projections" : "bf16 on bf16-MFMA projections"),
-                 im->ks1, im->dt, fuse ? " with fused out-proj + LN1" : "");
+                 im->ks1, im->dt, fuse ? " with fused out-proj + LN1" : "", cls);
     }
     return FD_OK;
 }

@@ -712,6 +712,7 @@ extern "C" int fd_score_backward(fd_score* m, const float* dout, float* grads, i
     }
 
     if (int rc = fd_embed_backward(m, dh, sv.emb, dtemb, grads, B, skp, kSplitKFloats, s)) return rc;
+    if (int rc = fd_class_table_backward(m, dtemb, grads, B, accumulate, s)) return rc;
     FD_LAUNCH_CHECK(ctx);
     return fd_take_deferred(ctx);
 }
@@ -725,6 +726,7 @@ extern "C" int fd_score_input_vjp(fd_score* m, const float* dout, float* dx, voi
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, dout && dx, "fd_score_input_vjp: null pointer");
     if (!m->have_saved) return fd_fail(ctx, FD_ERR_STATE, "fd_score_input_vjp: no training forward to differentiate");
+    if (int rc = fd_labels_check(m, m->saved_B, "fd_score_input_vjp")) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (ctx->ws_gen != m->saved_ws_gen || ctx->ws != m->saved_ws)
         return fd_fail(ctx, FD_ERR_STATE, "fd_score_input_vjp: another engine call used the context workspace after "

@@ -37,7 +37,8 @@ struct LayoutBuilder {
     }
 };
 
-int64_t build_layout(const fd_model_dims& d, fd_score* m, std::vector<fd_param_entry>* entries, int backbone = 0, int d_mlp = 0) {
+int64_t build_layout(const fd_model_dims& d, fd_score* m, std::vector<fd_param_entry>* entries, int backbone = 0, int d_mlp = 0,
+                     int n_classes = 0) {
     LayoutBuilder lb;
     lb.out = entries;
     const int D = d.d_model, C = d.n_channels, T = d.max_len, F = d.dim_ff;
@@ -94,6 +95,11 @@ int64_t build_layout(const fd_model_dims& d, fd_score* m, std::vector<fd_param_e
         lo.n2_b = lb.add(p + "norm2.bias", D, 0);
         if (m) m->layers.push_back(lo);
     }
+    // class conditioning (not in the reference): behind every other tensor, so that no existing offset moves; row n_classes = null token
+    if (n_classes > 0) {
+        const int64_t cls = lb.add("class_encoder.weight", n_classes + 1, D);
+        if (m) { m->cls_w = cls; m->n_classes = n_classes; }
+    }
     return lb.off;
 }
 
@@ -147,6 +153,33 @@ extern "C" int fd_score_layout_ex(const fd_model_dims* dims, int backbone, int d
     return FD_OK;
 }
 
+// The class-conditional forms (include/fdiff_hip.h): transformer backbone, n_classes >= 0 (0: the unlabelled layout, bit for bit)
+constexpr int kMaxClasses = 1 << 20;
+extern "C" int64_t fd_score_param_count_cond(const fd_model_dims* dims, int n_classes) {
+    if (!dims_ok(dims) || n_classes < 0 || n_classes > kMaxClasses) return FD_ERR_ARG;
+    return build_layout(*dims, nullptr, nullptr, FD_BACKBONE_TRANSFORMER, 0, n_classes);
+}
+
+extern "C" int fd_score_layout_cond(const fd_model_dims* dims, int n_classes, fd_param_entry* entries, int* n_entries) {
+    if (!dims_ok(dims) || !n_entries || n_classes < 0 || n_classes > kMaxClasses) return FD_ERR_ARG;
+    std::vector<fd_param_entry> v;
+    build_layout(*dims, nullptr, &v, FD_BACKBONE_TRANSFORMER, 0, n_classes);
+    if (entries) {
+        if (*n_entries < (int)v.size()) return FD_ERR_ARG;
+        memcpy(entries, v.data(), v.size() * sizeof(fd_param_entry));
+    }
+    *n_entries = (int)v.size();
+    return FD_OK;
+}
+
+extern "C" int fd_score_create_cond(fd_ctx* ctx, const fd_model_dims* dims, int n_classes, fd_score** out) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, n_classes >= 0 && n_classes <= kMaxClasses, "fd_score_create_cond: n_classes=%d", n_classes);
+    if (int rc = fd_score_create_ex(ctx, dims, FD_BACKBONE_TRANSFORMER, 0, out)) return rc;
+    (*out)->nparams = build_layout(*dims, *out, nullptr, FD_BACKBONE_TRANSFORMER, 0, n_classes);
+    return FD_OK;
+}
+
 extern "C" int fd_score_create_ex(fd_ctx* ctx, const fd_model_dims* dims, int backbone, int d_mlp, fd_score** out) {
     if (!ctx) return FD_ERR_ARG;
     FD_REQUIRE(ctx, out != nullptr, "fd_score_create: null out");
@@ -180,6 +213,7 @@ extern "C" int fd_score_create(fd_ctx* ctx, const fd_model_dims* dims, fd_score*
 extern "C" int fd_score_destroy(fd_score* m) {
     if (!m) return FD_ERR_ARG;
     fd_bf16_destroy(m);
+    fd_labels_destroy(m);
     if (m->prep_event) (void)hipEventDestroy(m->prep_event);
     if (m->img_event) (void)hipEventDestroy(m->img_event);
     delete m;
@@ -206,9 +240,12 @@ __global__ __launch_bounds__(64) void k_renorm_rows(float* __restrict__ P, int T
 
 // Gaussian-Fourier features + dense (transformer.py:80-89).  The phase is formed in float32 in the
 // reference's op order ((t*W)*2)*pi; sinf/cosf are the full-range-reduction OCML versions.
+// Class conditioning (not in the reference): with a table (K + 1, D), row y[b] of it is added last, in fp32; y == null or a label
+// outside [0, K] reads the null row K, so the table is never read out of bounds.
 __global__ __launch_bounds__(128) void k_time_embed(const float* __restrict__ t, const float* __restrict__ W,
                                                      const float* __restrict__ Wd, const float* __restrict__ bd,
-                                                     float* __restrict__ emb_out, float* __restrict__ temb, int D) {
+                                                     float* __restrict__ emb_out, float* __restrict__ temb, int D,
+                                                     const int* __restrict__ y, const float* __restrict__ table, int K) {
     extern __shared__ float emb[];
     const int b = blockIdx.x;
     const int half = (D + 1) / 2;
@@ -221,10 +258,16 @@ __global__ __launch_bounds__(128) void k_time_embed(const float* __restrict__ t,
         if (emb_out) emb_out[(size_t)b * D + j] = v;
     }
     __syncthreads();
+    int yb = K;
+    if (table && y) {
+        yb = y[b];
+        if ((unsigned)yb > (unsigned)K) yb = K;
+    }
     for (int d = threadIdx.x; d < D; d += blockDim.x) {
         float acc = bd[d];
         const float* w = Wd + (size_t)d * D;
         for (int j = 0; j < D; ++j) acc = fmaf(w[j], emb[j], acc);
+        if (table) acc += table[(size_t)yb * D + d];
         temb[(size_t)b * D + d] = acc;
     }
 }
@@ -531,8 +574,12 @@ uint64_t fd_dropout_site_offset(uint64_t base, int layer, int site) {
 namespace fdf32 {
 void time_embed(const float* t, const float* W, const float* Wd, const float* bd, float* temb, int B, int D,
                 hipStream_t s) {
-    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, (float*)nullptr, temb,
-                       D);
+    time_embed_cls(t, W, Wd, bd, temb, B, D, s, fd_cls{});
+}
+void time_embed_cls(const float* t, const float* W, const float* Wd, const float* bd, float* temb, int B, int D, hipStream_t s,
+                    fd_cls cls) {
+    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, (float*)nullptr, temb, D, cls.y, cls.table,
+                       cls.K);
 }
 // The weights-in-registers form for a channel count that is not a multiple of four (the reference's datasets: 1, 5, 13 channels;
 // BASELINE nasdaq: 6): scalar loads of the 4 x C weight slice and of the row's x, the same fma order over c -- bit-identical to
@@ -712,8 +759,9 @@ int fd_score_forward_f32(fd_score* m, const float* x, const float* t, float* out
         tmp = ws.take<float>((size_t)M * D);
     }
 
+    const fd_cls cls = train ? fd_cls_train(m) : fd_cls_eval(m);
     hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, P + m->tW, P + m->td_w,
-                       P + m->td_b, sv.emb, sv.temb, D);
+                       P + m->td_b, sv.emb, sv.temb, D, cls.y, cls.table, cls.K);
     float* h_in = (L > 0) ? (train ? sv.layers[0].x0 : scratch.x0) : sv.hL;
     fdf32::embed(x, P + m->emb_w, P + m->emb_b, P + m->pos, sv.temb, h_in, M, T, C, D, s);
     for (int i = 0; i < L; ++i) {
@@ -804,6 +852,7 @@ extern "C" int fd_score_forward(fd_score* m, const float* x, const float* t, flo
     FD_REQUIRE(ctx, B > 0, "fd_score_forward: B=%d", B);
     if (!m->prepared) return fd_fail(ctx, FD_ERR_STATE, "fd_score_forward: call fd_score_prepare first");
     if (mode != FD_MODE_F32 && mode != FD_MODE_BF16) return fd_fail(ctx, FD_ERR_ARG, "fd_score_forward: unknown mode %d", mode);
+    if (int rc = fd_labels_check(m, B, "fd_score_forward")) return rc;
     return fd_score_forward_any(m, x, t, out, B, mode, (hipStream_t)stream);
 }
 
@@ -826,6 +875,8 @@ extern "C" int fd_score_forward_train(fd_score* m, const float* x, const float* 
         return fd_fail(ctx, FD_ERR_UNSUPPORTED, "fd_score_forward_train: bf16 training kernels are not instantiated for this "
                        "model (needs bf16 weight images -- fd_score_plan says which widths have them --, dim_ff %% 1024 == 0, dim_ff <= 2048, "
                        "max_len <= 1024); select FD_MODE_F32");
+    if (int rc = fd_labels_check(m, B, "fd_score_forward_train")) return rc;
+    if (int rc = fd_labels_prepare_train(m, B, seed, offset, (hipStream_t)stream)) return rc;
     ++ctx->tr_fwd_serial;               // (whatever the flags of an earlier persistent forward said is history: fd_score_train_cluster_xcds)
     int rc = (m->backbone != FD_BACKBONE_TRANSFORMER)
                  ? fd_bb_forward(m, x, t, out, B, (hipStream_t)stream, true, dropout_p, seed, offset)
@@ -860,6 +911,8 @@ extern "C" int fd_score_train_dsm(fd_score* m, const float* x, const float* t, c
     if (m->train_mode != FD_MODE_BF16 || m->backbone != FD_BACKBONE_TRANSFORMER || !fd_train_bf16_supported(m) ||
         getenv("FDIFF_TRAIN_DSM_UNFUSED"))
         return fd_fail(ctx, FD_ERR_UNSUPPORTED, "fd_score_train_dsm: the fused step exists on the bf16 transformer training path only");
+    if (int rc = fd_labels_check(m, B, "fd_score_train_dsm")) return rc;
+    if (int rc = fd_labels_prepare_train(m, B, seed, offset, (hipStream_t)stream)) return rc;
     return fd_score_train_dsm_bf16(m, x, t, target, std, likelihood_weighting, grad_weight, B, dropout_p, seed, offset, loss_out, grads,
                                    accumulate, (hipStream_t)stream);
 }
@@ -919,7 +972,11 @@ extern "C" int fd_score_set_train_mode(fd_score* m, int mode) {
 
 int fd_time_embed_train(const float* t, const float* W, const float* Wd, const float* bd, float* emb, float* temb, int B, int D,
                         hipStream_t s) {
-    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, emb, temb, D);
+    return fd_time_embed_train_cls(t, W, Wd, bd, emb, temb, B, D, s, fd_cls{});
+}
+int fd_time_embed_train_cls(const float* t, const float* W, const float* Wd, const float* bd, float* emb, float* temb, int B, int D,
+                            hipStream_t s, fd_cls cls) {
+    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, emb, temb, D, cls.y, cls.table, cls.K);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -957,7 +1014,8 @@ extern "C" int fd_time_embed_add(fd_ctx* ctx, const float* x, const float* t, co
     hipStream_t s = (hipStream_t)stream;
     if (int rc = fd_ws_reserve(ctx, fd_ws::padded((size_t)B * D * sizeof(float)))) return rc;
     float* temb = (float*)ctx->ws;
-    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, (float*)nullptr, temb, D);
+    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, (float*)nullptr, temb, D,
+                       (const int*)nullptr, (const float*)nullptr, 0);
     const size_t n = (size_t)B * (T > 0 ? T : 1) * D;
     size_t blocks = std::min((n + 255) / 256, (size_t)ctx->num_cu * 8);
     hipLaunchKernelGGL(k_bcast_add, dim3((unsigned)blocks), dim3(256), 0, s, x, temb, out, n, T, D, 1);

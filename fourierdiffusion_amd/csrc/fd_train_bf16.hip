@@ -2679,7 +2679,7 @@ int tr_forward_t(fd_score* m, const float* x, const float* t, float* out, int B,
     const int M = B * T;
     const float* P = m->params;
     const TrDims d = make_dims(m, B, p, seed);
-    if (fd_time_embed_train(t, P + m->tW, P + m->td_w, P + m->td_b, tb.emb, tb.temb, B, D, s)) return FD_ERR_HIP;
+    if (fd_time_embed_train_cls(t, P + m->tW, P + m->td_w, P + m->td_b, tb.emb, tb.temb, B, D, s, fd_cls_train(m))) return FD_ERR_HIP;
     float* h0 = L > 0 ? tb.layers[0].x0 : tb.hL;
     fdf32::embed(x, P + m->emb_w, P + m->emb_b, P + m->pos, tb.temb, h0, M, T, C, D, s);
     if (L > 0)
@@ -3127,7 +3127,8 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
         va.grads = grads; va.accumulate = accumulate;
         hipLaunchKernelGGL(k_tr_vecreduce, dim3(5, L), dim3(1024), 0, s, va);
     }
-    const int rc_embed = fd_embed_backward(m, tb.dh, tb.emb, tb.dtemb, grads, B, tb.skp, kSkpFloats, s);
+    int rc_embed = fd_embed_backward(m, tb.dh, tb.emb, tb.dtemb, grads, B, tb.skp, kSkpFloats, s);
+    if (!rc_embed) rc_embed = fd_class_table_backward(m, tb.dtemb, grads, B, accumulate, s);
     if (rc_embed) {
         // the weight-gradient launches on the side streams are still writing tb.part (arena memory): let them finish before the
         // caller sees the error and reuses or frees the arena

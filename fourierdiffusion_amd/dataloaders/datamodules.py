@@ -221,6 +221,58 @@ class SyntheticDatamodule(Datamodule):
         return "synthetic"
 
 
+class SyntheticClassesDatamodule(SyntheticDatamodule):
+    """Labelled sines (not in the reference): x_n = sin(n f + phi), phi ~ N(0,1), the class k of a series drawn uniformly from
+    ``n_classes`` and its frequency f uniform in the k-th of ``n_classes`` equal slices of (F_LO, F_HI) rad / step; every channel
+    of a series shares the class and draws its own f and phi.  ``y_train`` / ``y_test`` hold the classes;
+    ``class_band(k)`` is the slice, ``dominant_frequency`` the estimate scripts/cfg_quality.py classifies samples with."""
+    F_LO, F_HI = 0.15, 1.35
+
+    def __init__(self, data_dir: Path | str = Path.cwd() / "data", random_seed: int = 42, batch_size: int = 32,
+                 fourier_transform: bool = False, standardize: bool = False, max_len: int = 100, num_samples: int = 1000,
+                 n_channels: int = 1, n_classes: int = 3) -> None:
+        super().__init__(data_dir=data_dir, random_seed=random_seed, batch_size=batch_size, fourier_transform=fourier_transform,
+                         standardize=standardize, max_len=max_len, num_samples=num_samples, n_channels=n_channels)
+        if n_classes < 1:
+            raise ValueError(f"n_classes must be >= 1, got {n_classes}")
+        self.n_classes = int(n_classes)
+
+    def _file(self) -> Path:
+        return self.data_dir / f"sine_classes_K{self.n_classes}_T{self.max_len}_C{self.n_channels}_N{self.num_samples}.npz"
+
+    def class_band(self, k: int) -> Tuple[float, float]:
+        w = (self.F_HI - self.F_LO) / self.n_classes
+        return self.F_LO + k * w, self.F_LO + (k + 1) * w
+
+    @staticmethod
+    def dominant_frequency(X: torch.Tensor) -> torch.Tensor:
+        """(n, C): the angular frequency (rad / step) of the largest non-DC bin of each channel's spectrum, time-domain X (n,T,C)."""
+        spec = torch.fft.rfft(X.to(torch.float64), dim=1).abs()
+        spec[:, 0] = 0.0
+        return spec.argmax(dim=1).to(torch.float64) * (2.0 * np.pi / X.shape[1])
+
+    def setup(self, stage: str = "fit") -> None:
+        d = np.load(self._file())
+        X, y = torch.from_numpy(d["X"]), torch.from_numpy(d["y"]).to(torch.long)
+        self.X_train, self.X_test = X[: self.num_samples], X[self.num_samples:]
+        self.y_train, self.y_test = y[: self.num_samples], y[self.num_samples:]
+        self._train_set = None
+
+    def download_data(self) -> None:
+        rng = np.random.RandomState(self.random_seed)
+        n = 2 * self.num_samples
+        y = rng.randint(0, self.n_classes, size=n)
+        w = (self.F_HI - self.F_LO) / self.n_classes
+        phase = rng.normal(size=(n, 1, self.n_channels))
+        frequency = self.F_LO + w * (y[:, None, None] + rng.uniform(size=(n, 1, self.n_channels)))
+        timesteps = np.arange(self.max_len).reshape(1, -1, 1)
+        np.savez(self._file(), X=np.sin(timesteps * frequency + phase).astype(np.float32), y=y.astype(np.int64))
+
+    @property
+    def dataset_name(self) -> str:
+        return "synthetic_classes"
+
+
 class TensorDatamodule(Datamodule):
     """Datamodule over in-memory tensors (the role of the reference tests' DummyDatamodule,
     tests/test_datamodules.py:16-53)."""

@@ -12,6 +12,12 @@ No autograd graph is built: ``forward`` in training mode keeps activations insid
 
 Extension (not in the reference): an exponential moving average of the weights lives next to them in a second flat buffer
 (``ema_parameters``, filled by ``FusedAdamW(ema_decay=...)``); ``use_ema()`` runs every engine call on it.
+
+Extension (not in the reference, which drops ``batch.y``): ``n_classes = K > 0`` makes the transformer model class-conditional.  One
+more tensor, ``class_encoder.weight`` (K + 1, D), sits behind every other one in the flat buffer; row ``y_b`` of it is added to the time
+embedding of series b inside the engine's time-embedding kernel, row K being the null (unconditional) token that a missing label
+and, in training, a label dropped with probability ``label_dropout`` read.  ``DiffusionSampler.sample(y=, cfg_scale=)`` samples
+with classifier-free guidance.  ``n_classes = 0`` is the reference's model bit for bit.
 """
 from __future__ import annotations
 
@@ -55,7 +61,17 @@ class ScoreModule:
         num_training_steps: int = 1000,
         lr_max: float = 1e-3,
         likelihood_weighting: bool = False,
+        n_classes: int = 0,
+        label_dropout: float = 0.1,
     ) -> None:
+        self.n_classes = int(n_classes)
+        self.label_dropout = float(label_dropout)
+        if self.n_classes < 0:
+            raise ValueError(f"n_classes must be >= 0, got {n_classes}")
+        if self.n_classes > 0 and self._backbone != _C.FD_BACKBONE_TRANSFORMER:
+            raise ValueError(f"{type(self).__name__}: n_classes > 0 (class conditioning) exists for the transformer backbone only")
+        if not 0.0 <= self.label_dropout <= 1.0:
+            raise ValueError(f"label_dropout must lie in [0, 1], got {label_dropout}")
         self.max_len = int(max_len)
         self.n_channels = int(n_channels)
         self.noise_scheduler = noise_scheduler
@@ -77,6 +93,8 @@ class ScoreModule:
             n_channels=n_channels, max_len=max_len, noise_scheduler=noise_scheduler,
             fourier_noise_scaling=fourier_noise_scaling, d_model=d_model, num_layers=num_layers, n_head=n_head,
             num_training_steps=num_training_steps, lr_max=lr_max, likelihood_weighting=likelihood_weighting)
+        if self.n_classes > 0:      # (only then: a checkpoint of an unlabelled model stays readable by the reference's constructor)
+            self.hparams.update(n_classes=self.n_classes, label_dropout=self.label_dropout)
 
         self.training_loss_fn, self.validation_loss_fn = self.set_loss_fn()
 
@@ -84,7 +102,7 @@ class ScoreModule:
             raise AssertionError("embed_dim must be divisible by num_heads")
         self._dims = _C.model_dims(self.n_channels, self.max_len, self.d_model, self.n_head, self.num_layers,
                                    self.dim_feedforward)
-        self._layout, self._nparams = _C.score_layout(self._dims, self._backbone, self._d_mlp)
+        self._layout, self._nparams = _C.score_layout(self._dims, self._backbone, self._d_mlp, self.n_classes)
         self._flat = torch.zeros(self._nparams, dtype=torch.float32)
         self._ema: Optional[torch.Tensor] = None              # averaged weights, same layout (enable_ema)
         self._ema_scope: Optional[torch.Tensor] = None        # inside use_ema(): the raw buffer that `_flat` stopped naming
@@ -133,6 +151,8 @@ class ScoreModule:
         linear("embedder")
         linear("unembedder")
         self._init_backbone(v, linear)
+        if "class_encoder.weight" in v:      # nn.Embedding's N(0, 1), drawn behind everything the reference's constructor draws
+            init.normal_(v["class_encoder.weight"])
 
     def _init_backbone(self, v, linear) -> None:
         init = torch.nn.init
@@ -311,8 +331,13 @@ class ScoreModule:
         ctx = _C.ctx(self._flat.device)
         if self._handle is None:
             h = C.c_void_p()
-            rc = _C.lib().fd_score_create_ex(ctx, C.byref(self._dims), self._backbone, self._d_mlp, C.byref(h))
-            _C.check(rc, ctx)
+            if self.n_classes > 0:
+                rc = _C.lib().fd_score_create_cond(ctx, C.byref(self._dims), self.n_classes, C.byref(h))
+                _C.check(rc, ctx)
+                _C.check(_C.lib().fd_score_set_label_dropout(h, self.label_dropout), ctx)
+            else:
+                rc = _C.lib().fd_score_create_ex(ctx, C.byref(self._dims), self._backbone, self._d_mlp, C.byref(h))
+                _C.check(rc, ctx)
             self._handle = h
             self._dirty = self._other_dirty = True
             self._train_mode_set = None
@@ -380,6 +405,55 @@ class ScoreModule:
         _C.check(_C.lib().fd_score_train_cluster_xcds(h, B, buf, _C.stream_of(self._flat)), ctx)
         return torch.tensor(list(buf), dtype=torch.int32).view(B, KT)
 
+    # ------------------------------------------------------------------ labels (class conditioning; not in the reference)
+    def labels_on_device(self, y, batch_size: int, name: str = "y") -> Optional[torch.Tensor]:
+        """``y`` validated and uploaded: an int32 device vector of ``batch_size`` labels, or None for ``y is None``.  y: an int
+        (every row that class) or an integer tensor (batch_size,), every label in [0, n_classes] (n_classes itself is the null,
+        unconditional token).  ValueError on an unlabelled model, a wrong length, dtype or range -- checked on the host (a device
+        tensor is read back for it)."""
+        if y is None:
+            return None
+        K = self.n_classes
+        if K <= 0:
+            raise ValueError(f"{name} was given, but the model is not class-conditional (n_classes = 0)")
+        if isinstance(y, bool) or (not isinstance(y, (int, torch.Tensor))):
+            raise ValueError(f"{name} must be an int or an integer tensor of shape ({batch_size},), got {type(y).__name__}")
+        if isinstance(y, int):
+            y = torch.full((batch_size,), y, dtype=torch.int64)
+        if y.is_floating_point() or y.is_complex() or y.dtype == torch.bool:
+            raise ValueError(f"{name} must hold integers, got {y.dtype}")
+        if tuple(y.shape) != (batch_size,):
+            raise ValueError(f"{name} must have shape ({batch_size},), got {tuple(y.shape)}")
+        lo, hi = int(y.min()), int(y.max())
+        if lo < 0 or hi > K:
+            raise ValueError(f"{name} must lie in [0, {K}] ({K} = the null token), got values in [{lo}, {hi}]")
+        return y.to(device=self.device, dtype=torch.int32).contiguous()
+
+    @contextlib.contextmanager
+    def _labels_bound(self, h, ctx, yd: Optional[torch.Tensor]):
+        """Binds the label vector for the engine calls of the scope (fd_score_set_labels) and clears it afterwards."""
+        if yd is None:
+            yield
+            return
+        _C.check(_C.lib().fd_score_set_labels(h, yd.data_ptr(), int(yd.shape[0])), ctx)
+        try:
+            yield
+        finally:
+            _C.lib().fd_score_set_labels(h, None, 0)
+
+    def effective_labels(self, y, batch_size: int, key: int, offset: int, p: Optional[float] = None) -> torch.Tensor:
+        """The labels a training forward with the Philox stream (key, offset) uses for ``y`` (fd_label_dropout): int32 device vector,
+        the null token ``n_classes`` where label dropout (p, default ``label_dropout``) struck or ``y`` is None."""
+        if self.n_classes <= 0:
+            raise ValueError("effective_labels: the model is not class-conditional (n_classes = 0)")
+        yd = self.labels_on_device(y, batch_size)
+        ctx = _C.ctx(self.device)
+        out = torch.empty(batch_size, dtype=torch.int32, device=self.device)
+        rc = _C.lib().fd_label_dropout(ctx, _C.ptr(yd), out.data_ptr(), int(batch_size), self.n_classes,
+                                       float(self.label_dropout if p is None else p), int(key), int(offset), _C.stream_of(out))
+        _C.check(rc, ctx)
+        return out
+
     # ------------------------------------------------------------------ forward / backward
     def forward(self, batch: DiffusableBatch) -> torch.Tensor:
         X = batch.X
@@ -392,27 +466,32 @@ class ScoreModule:
         td = _C.dev_f32(timesteps.to(self.device), "batch.timesteps")
         out = torch.empty_like(Xd)
         B = Xd.shape[0]
-        if self.training:
-            p = float(self.dropout)
-            key, off = _rng.stream()
-            rc = _C.lib().fd_score_forward_train(h, Xd.data_ptr(), td.data_ptr(), out.data_ptr(), B, p,
-                                                 key, off, _C.stream_of(Xd))
-            self._train_inputs = (Xd, td)       # the engine reads them again in backward
-        else:
+        # a labelled model reads batch.y (None: the null token on every row); an unlabelled one ignores it, as the reference does
+        yd = self.labels_on_device(batch.y, B, "batch.y") if self.n_classes > 0 else None
+        if not self.training:
             mode = _PRECISIONS[self.precision_effective]
-            rc = _C.lib().fd_score_forward(h, Xd.data_ptr(), td.data_ptr(), out.data_ptr(), B, mode,
-                                           _C.stream_of(Xd))
+        with self._labels_bound(h, ctx, yd):
+            if self.training:
+                p = float(self.dropout)
+                key, off = _rng.stream()
+                rc = _C.lib().fd_score_forward_train(h, Xd.data_ptr(), td.data_ptr(), out.data_ptr(), B, p,
+                                                     key, off, _C.stream_of(Xd))
+                self._train_inputs = (Xd, td)       # the engine reads them again in backward
+            else:
+                rc = _C.lib().fd_score_forward(h, Xd.data_ptr(), td.data_ptr(), out.data_ptr(), B, mode,
+                                               _C.stream_of(Xd))
         _C.check(rc, ctx)
         return out
 
     __call__ = forward
 
     def train_dsm(self, x_noisy: torch.Tensor, timesteps: torch.Tensor, target: torch.Tensor, std: torch.Tensor,
-                  likelihood_weighting: bool = False, grad_weight: float = 1.0) -> Optional[torch.Tensor]:
+                  likelihood_weighting: bool = False, grad_weight: float = 1.0, y=None) -> Optional[torch.Tensor]:
         """Training forward + denoising score-matching loss + backward as one engine call (fd_score_train_dsm): the loss
         tensor, with the gradients ACCUMULATED into ``self.grads`` -- or None when this model has no fused step (exact-f32
         training, MLP / LSTM backbones, very wide C * d_model), in which case the caller runs forward -> fd_dsm_loss ->
-        backward.  Same Philox stream use as ``forward`` in training mode (one key per call)."""
+        backward.  Same Philox stream use as ``forward`` in training mode (one key per call).  y: the batch's labels for a
+        class-conditional model (as ``forward`` reads ``batch.y``; ignored by an unlabelled one)."""
         if not self.training or getattr(self, "_no_fused_dsm", False):     # (_no_fused_dsm: a manual switch, never latched here)
             return None
         ctx, h = self._engine()
@@ -435,12 +514,14 @@ class ScoreModule:
         td = _C.dev_f32(timesteps.to(self.device), "timesteps")
         tg = _C.dev_f32(target, "target")
         sd = _C.dev_f32(std, "std")
+        yd = self.labels_on_device(y, Bn) if self.n_classes > 0 else None
         grads, acc = self._grads_for_backward()
         loss = torch.empty(1, device=self.device, dtype=torch.float32)
         key, off = _rng.stream()
-        rc = _C.lib().fd_score_train_dsm(h, Xd.data_ptr(), td.data_ptr(), tg.data_ptr(), sd.data_ptr(),
-                                         1 if likelihood_weighting else 0, float(grad_weight), Xd.shape[0], float(self.dropout),
-                                         key, off, loss.data_ptr(), grads.data_ptr(), acc, _C.stream_of(Xd))
+        with self._labels_bound(h, ctx, yd):
+            rc = _C.lib().fd_score_train_dsm(h, Xd.data_ptr(), td.data_ptr(), tg.data_ptr(), sd.data_ptr(),
+                                             1 if likelihood_weighting else 0, float(grad_weight), Xd.shape[0], float(self.dropout),
+                                             key, off, loss.data_ptr(), grads.data_ptr(), acc, _C.stream_of(Xd))
         _C.check(rc, ctx)
         self._train_inputs = (Xd, td, tg, sd)
         return loss[0]
@@ -581,7 +662,9 @@ class MLPScoreModule(ScoreModule):
 
     def __init__(self, n_channels: int, max_len: int, noise_scheduler: SDE, fourier_noise_scaling: bool = True, d_model: int = 72,
                  d_mlp: int = 512, num_layers: int = 3, num_training_steps: int = 1000, lr_max: float = 1e-3,
-                 likelihood_weighting: bool = False) -> None:
+                 likelihood_weighting: bool = False, n_classes: int = 0) -> None:
+        if n_classes:
+            raise ValueError("MLPScoreModule: n_classes > 0 (class conditioning) exists for the transformer backbone only")
         self._d_mlp = int(d_mlp)
         self.d_mlp = int(d_mlp)
         super().__init__(n_channels=n_channels, max_len=max_len, noise_scheduler=noise_scheduler,
@@ -608,7 +691,9 @@ class LSTMScoreModule(ScoreModule):
 
     def __init__(self, n_channels: int, max_len: int, noise_scheduler: SDE, fourier_noise_scaling: bool = True, d_model: int = 72,
                  num_layers: int = 3, num_training_steps: int = 1000, lr_max: float = 1e-3,
-                 likelihood_weighting: bool = False) -> None:
+                 likelihood_weighting: bool = False, n_classes: int = 0) -> None:
+        if n_classes:
+            raise ValueError("LSTMScoreModule: n_classes > 0 (class conditioning) exists for the transformer backbone only")
         super().__init__(n_channels=n_channels, max_len=max_len, noise_scheduler=noise_scheduler,
                          fourier_noise_scaling=fourier_noise_scaling, d_model=d_model, num_layers=num_layers, n_head=1,
                          num_training_steps=num_training_steps, lr_max=lr_max, likelihood_weighting=likelihood_weighting)

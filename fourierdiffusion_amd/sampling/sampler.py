@@ -30,6 +30,12 @@ marginals (Song et al. 2021, Sec. 4.3) by Euler or Heun, the whole loop one engi
 Likelihood (an extension, not in the reference): ``log_likelihood`` evaluates log p(x) under the probability-flow ODE
 (Song et al. 2021, Sec. 4.3, App. D.2): the ODE runs data -> latents with the divergence integral along it, one engine call
 per launch (fd_likelihood_run); ``sampling.likelihood.to_data_space`` maps the result to the series as the user holds them.
+
+Classifier-free guidance (an extension, not in the reference): on a class-conditional model (``ScoreModule(n_classes=K)``),
+``sample`` / ``sample_ode`` take labels ``y`` and a guidance scale ``cfg_scale`` = w and follow the score
+w s(x, t, y) + (1 - w) s(x, t, null): one evaluation per step at w = 1 (class-conditional sampling) and w = 0, else the two
+evaluations as one forward on twice the rows and one fused step kernel (fd_sampler_run_cfg, fd_sampler_run_ode_cfg).  The
+predictor-corrector sampler, ``impute`` and ``log_likelihood`` take no labels and run a labelled model unconditionally.
 """
 from __future__ import annotations
 
@@ -50,10 +56,13 @@ from .likelihood import ESTIMATORS, EXACT_MAX_DIMS, RK45_MAX_EVALS, LikelihoodRe
 
 class DiffusionSampler:
     def __init__(self, score_model: ScoreModule, sample_batch_size: int, corrector_steps: int = 0, snr: float = 0.16,
-                 merge_batches: bool = True) -> None:
+                 merge_batches: bool = True, cfg_scale: float = 1.0, labels=None) -> None:
         """corrector_steps > 0 turns the predictor-only sampler of the reference into a predictor-corrector one
         (`corrector_steps` Langevin steps at signal-to-noise ratio `snr` before every predictor step; an extension, not in
-        the reference: default off)."""
+        the reference: default off).  cfg_scale / labels: the front end's guidance settings (cmd/conf/sampler/*.yaml), kept for
+        cmd/sample.py, which turns ``labels`` into the ``y`` of ``sample``; ``sample`` itself takes both as arguments."""
+        self.cfg_scale = float(cfg_scale)
+        self.labels = labels
         self.corrector_steps = int(corrector_steps)
         self.snr = float(snr)
         self.score_model = score_model
@@ -76,19 +85,40 @@ class DiffusionSampler:
     def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None,
                step_noise: Optional[Sequence[torch.Tensor]] = None,
-               corrector_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
+               corrector_noise: Optional[Sequence[torch.Tensor]] = None, y=None, cfg_scale: float = 1.0) -> torch.Tensor:
         """Returns a CPU tensor (n, max_len, n_channels), n = num_batches * batch_size.
 
         prior_noise[b] (bs,T,C) and step_noise[b] (N,bs,T,C) inject the N(0,1) draws of batch b (parity
-        tests); by default everything comes from the engine's Philox stream."""
+        tests); by default everything comes from the engine's Philox stream.
+
+        y, cfg_scale (class-conditional models only; ValueError otherwise): the labels -- an int, or an integer tensor with one
+        label per returned sample -- and the classifier-free guidance scale w.  y=None samples unconditionally; w = 1 samples the
+        class, w > 1 trades diversity for class fidelity (two score evaluations per step, run as one forward on 2 x the rows)."""
+        guided, pair = self._guided(y, cfg_scale)
+        if guided and self.corrector_steps > 0:
+            raise ValueError("sample: y / cfg_scale are not supported by the predictor-corrector sampler (corrector_steps=0)")
         self.score_model.eval()
         N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
         ctx, h, p, G, mode = self._engine_args()
         dev = self.score_model.device
         all_samples: List[torch.Tensor] = []
-        sizes = self._batches(num_samples, mode, not (prior_noise is None and step_noise is None and corrector_noise is None))
+        injected = not (prior_noise is None and step_noise is None and corrector_noise is None)
+        sizes = self._batches(num_samples, mode, injected, pair=pair)
+        labels = self._labels(y, sum(sizes)) if guided else None
+        lo = 0
         for b, bs in enumerate(sizes):
             X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
+            if guided:
+                z = None if step_noise is None else self._noise(step_noise[b], (N, bs), "step_noise")
+                key, off = (0, 0) if z is not None else _rng.stream()
+                yb = None if labels is None else labels[lo:lo + bs].contiguous()
+                lo += bs
+                Xs = self._cfg_state(X, pair)
+                rc = _C.lib().fd_sampler_run_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, Xs.data_ptr(), _C.ptr(yb),
+                                                 float(cfg_scale), _C.ptr(z), key, off, bs, mode, _C.stream_of(Xs))
+                _C.check(rc, ctx)
+                all_samples.append(Xs[:bs])
+                continue
             z = None
             if step_noise is not None:
                 z = _C.dev_f32(step_noise[b].to(dev), "step_noise")
@@ -116,23 +146,73 @@ class DiffusionSampler:
     _SCHEDULES = ("time", "logsnr")
 
     def sample_ode(self, num_samples: int, num_diffusion_steps: Optional[int] = None, solver: str = "heun",
-                   prior_noise: Optional[Sequence[torch.Tensor]] = None, schedule: str = "time") -> torch.Tensor:
+                   prior_noise: Optional[Sequence[torch.Tensor]] = None, schedule: str = "time", y=None,
+                   cfg_scale: float = 1.0) -> torch.Tensor:
         """Samples by the probability-flow ODE from t = 1 to t = eps in N steps: N score evaluations for Euler, 2N for Heun, N for
         "ddim" (the first-order exponential integrator in data-prediction form) and "dpmpp2m" (DPM-Solver++ 2M, its second-order
         multistep form).  schedule: "time", the grid ``linspace(1, eps, N + 1)``, or "logsnr", N + 1 points uniform in
         ``noise_scheduler.log_snr`` between t = 1 and t = eps.  Batching, launch merging and the prior as ``sample``;
-        prior_noise[b] (bs,T,C) injects the prior draws of batch b.  Returns a CPU tensor (n, max_len, n_channels) in sample
-        space."""
+        prior_noise[b] (bs,T,C) injects the prior draws of batch b.  y, cfg_scale: labels and classifier-free guidance scale as in
+        ``sample`` (every solver).  Returns a CPU tensor (n, max_len, n_channels) in sample space."""
         model = self.score_model
         self._check_solver(solver, dpm=True)
         N = model.num_training_steps if num_diffusion_steps is None else int(num_diffusion_steps)
         grid = self._ode_grid(N, to_noise=False, schedule=schedule)
-        sizes = self._batches(num_samples, _PRECISIONS[model.precision_effective], prior_noise is not None)
+        guided, pair = self._guided(y, cfg_scale)
+        sizes = self._batches(num_samples, _PRECISIONS[model.precision_effective], prior_noise is not None, pair=pair)
+        labels = self._labels(y, sum(sizes)) if guided else None
         out: List[torch.Tensor] = []
+        lo = 0
         for b, bs in enumerate(sizes):
             X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
-            out.append(self._run_ode(X, grid, solver))
+            if guided:
+                yb = None if labels is None else labels[lo:lo + bs].contiguous()
+                lo += bs
+                out.append(self._run_ode_cfg(self._cfg_state(X, pair), grid, solver, yb, float(cfg_scale), bs))
+            else:
+                out.append(self._run_ode(X, grid, solver))
         return torch.cat([x.cpu() for x in out], dim=0)
+
+    # ------------------------------------------------------------ classifier-free guidance (extension, not in the reference)
+    def _guided(self, y, cfg_scale) -> tuple:
+        """(guided, pair): whether the call runs a guided loop at all (labels or a non-default scale on a labelled model), and
+        whether that loop evaluates the score twice per step (as one forward on 2 x the rows).  ValueError for labels or a scale
+        on an unlabelled model, or a scale that is not a finite number."""
+        if isinstance(cfg_scale, bool) or not isinstance(cfg_scale, (int, float)) or not math.isfinite(cfg_scale):
+            raise ValueError(f"cfg_scale must be a finite number, got {cfg_scale!r}")
+        if self.score_model.n_classes <= 0:
+            if y is not None or float(cfg_scale) != 1.0:
+                raise ValueError("y / cfg_scale need a class-conditional model (ScoreModule(n_classes=K)); this one has n_classes = 0")
+            return False, False
+        guided = y is not None or float(cfg_scale) != 1.0
+        # (FDIFF_CFG_FORCE_PAIR, tests: the two-evaluation form also where the combine is exact; the engine reads the same switch)
+        pair = y is not None and (float(cfg_scale) not in (0.0, 1.0) or bool(os.environ.get("FDIFF_CFG_FORCE_PAIR")))
+        return guided, pair
+
+    def _labels(self, y, total: int) -> Optional[torch.Tensor]:
+        """The labels of all ``total`` returned samples as an int32 device vector (None: unconditional)."""
+        if y is not None and not isinstance(y, int) and isinstance(y, torch.Tensor) and y.dim() == 1 and y.shape[0] != total:
+            raise ValueError(f"y must hold one label per returned sample: {total} (whole batches of sample_batch_size), got {y.shape[0]}")
+        return self.score_model.labels_on_device(y, total, "y")
+
+    @staticmethod
+    def _cfg_state(X: torch.Tensor, pair: bool) -> torch.Tensor:
+        """The state buffer of a guided loop: X itself, or (2 bs, T, C) with X in its first half for the two-evaluation form."""
+        if not pair:
+            return X
+        Xs = torch.empty((2 * X.shape[0],) + tuple(X.shape[1:]), device=X.device, dtype=X.dtype)
+        Xs[:X.shape[0]].copy_(X)
+        return Xs
+
+    def _run_ode_cfg(self, Xs: torch.Tensor, grid, solver: str, yb: Optional[torch.Tensor], w: float, bs: int) -> torch.Tensor:
+        self.score_model.eval()
+        ctx, h, p, G, mode = self._engine_args()
+        ts_arr, N = grid
+        sid = self._DPM_SOLVERS[solver] if solver in self._DPM_SOLVERS else self._SOLVERS[solver]
+        rc = _C.lib().fd_sampler_run_ode_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, Xs.data_ptr(), _C.ptr(yb), w, bs, mode,
+                                             _C.stream_of(Xs))
+        _C.check(rc, ctx)
+        return Xs[:bs]
 
     def encode(self, X: torch.Tensor, num_diffusion_steps: int, solver: str = "heun", schedule: str = "time") -> torch.Tensor:
         """Latents of X (n, max_len, n_channels) in sample space: the probability-flow ODE from t = eps to t = 1 by Euler or Heun
@@ -558,15 +638,20 @@ class DiffusionSampler:
             return dft_standardize(y0, mean, std) if std is not None else dft(y0)
         return ((y0 - mean) / std).contiguous() if std is not None else y0.contiguous()
 
-    def _batches(self, num_samples: int, mode: int, injected: bool) -> List[int]:
+    def _batches(self, num_samples: int, mode: int, injected: bool, pair: bool = False) -> List[int]:
         """Launch sizes of ``sample`` / ``sample_ode``: the reference's batches (``max(1, num_samples // sample_batch_size)`` of
         them, the last one possibly short), merged by ``_launch_sizes`` unless merge_batches is off, there is one batch, or noise is
-        injected (one launch per batch then)."""
+        injected (one launch per batch then).  pair: a guided loop that evaluates 2 x the rows per step -- its launches are cut to
+        half a batch, so that the forward workspace stays that of ``sample_batch_size`` rows (not with injected noise, whose
+        tensors are shaped per batch)."""
         bs = self.sample_batch_size
         num_batches = max(1, num_samples // bs)
         sizes = [min(num_samples - b * bs, bs) for b in range(num_batches)]
         if self.merge_batches and num_batches > 1 and not injected:
             sizes = self._launch_sizes(sum(sizes), mode)
+        if pair and not injected:
+            half = max(1, bs // 2)
+            sizes = [min(half, n - lo) for n in sizes for lo in range(0, n, half)]
         return sizes
 
     def _launch_sizes(self, total: int, mode: int) -> List[int]:
@@ -629,14 +714,38 @@ class DiffusionSampler:
         raise NotImplementedError("Scheduler not recognized.")
 
 
+def parse_labels(spec, n: int, n_classes: int) -> Optional[torch.Tensor]:
+    """The ``labels`` setting of the sampler configs as the ``y`` of ``sample`` for n samples: None / "null" -> None (unconditional),
+    an int (or its string) -> that class for every sample, "balanced" -> 0, 1, ..., n_classes - 1 cycled.  ValueError otherwise,
+    for a class outside [0, n_classes), or for any labels on an unlabelled model."""
+    if spec is None or (isinstance(spec, str) and spec.strip().lower() in ("null", "none", "")):
+        return None
+    if n_classes <= 0:
+        raise ValueError(f"labels={spec!r}, but the model is not class-conditional (score_model.n_classes = 0)")
+    if isinstance(spec, str) and spec.strip().lower() == "balanced":
+        return torch.arange(n, dtype=torch.int64) % n_classes
+    if isinstance(spec, bool):
+        raise ValueError(f"labels must be an int, 'balanced' or null, got {spec!r}")
+    try:
+        k = int(spec) if not isinstance(spec, float) or spec.is_integer() else None
+    except (TypeError, ValueError):
+        k = None
+    if k is None:
+        raise ValueError(f"labels must be an int, 'balanced' or null, got {spec!r}")
+    if not 0 <= k < n_classes:
+        raise ValueError(f"labels={k} is not a class of this model (0 .. {n_classes - 1})")
+    return torch.full((n,), k, dtype=torch.int64)
+
+
 class ODESampler(DiffusionSampler):
     """A DiffusionSampler whose ``sample`` integrates the probability-flow ODE (``sample_ode``) with the constructor's ``solver``
     ("heun", "euler", "ddim" or "dpmpp2m") and ``schedule`` ("time" or "logsnr"):
     ``python cmd/sample.py sampler=ode num_diffusion_steps=50``, ``python cmd/sample.py sampler=dpm num_diffusion_steps=20``."""
 
     def __init__(self, score_model: ScoreModule, sample_batch_size: int, solver: str = "heun", merge_batches: bool = True,
-                 schedule: str = "time") -> None:
-        super().__init__(score_model=score_model, sample_batch_size=sample_batch_size, merge_batches=merge_batches)
+                 schedule: str = "time", cfg_scale: float = 1.0, labels=None) -> None:
+        super().__init__(score_model=score_model, sample_batch_size=sample_batch_size, merge_batches=merge_batches,
+                         cfg_scale=cfg_scale, labels=labels)
         self._check_solver(solver, dpm=True)
         if schedule not in self._SCHEDULES:
             raise ValueError(f"schedule must be one of {list(self._SCHEDULES)}, got {schedule!r}")
@@ -644,5 +753,6 @@ class ODESampler(DiffusionSampler):
         self.schedule = schedule
 
     def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None,
-               prior_noise: Optional[Sequence[torch.Tensor]] = None) -> torch.Tensor:
-        return self.sample_ode(num_samples, num_diffusion_steps, solver=self.solver, prior_noise=prior_noise, schedule=self.schedule)
+               prior_noise: Optional[Sequence[torch.Tensor]] = None, y=None, cfg_scale: float = 1.0) -> torch.Tensor:
+        return self.sample_ode(num_samples, num_diffusion_steps, solver=self.solver, prior_noise=prior_noise, schedule=self.schedule,
+                               y=y, cfg_scale=cfg_scale)

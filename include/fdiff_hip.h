@@ -217,6 +217,32 @@ int fd_score_layout_ex(const fd_model_dims* dims, int backbone, int d_mlp, fd_pa
 int fd_score_create_ex(fd_ctx* ctx, const fd_model_dims* dims, int backbone, int d_mlp, fd_score** out);
 int fd_score_destroy(fd_score* m);
 
+/* Class-conditional score models (NOT in the reference: its ScoreModule.forward, score_models.py:67-94, never reads batch.y).
+ * A transformer-backbone model with n_classes = K > 0 owns one more tensor, class_encoder.weight (K + 1, D), appended BEHIND every
+ * tensor of fd_score_layout (no existing offset moves); row K is the null (unconditional) token.  Row y_b of the table is added to
+ * the time embedding of series b, in fp32, inside the time-embedding kernel of every forward and training path.  n_classes = 0 is
+ * fd_score_layout / fd_score_create exactly.  The persistent kernel shares one time embedding per diffusion step, so a labelled
+ * model runs the per-layer kernels and every sampling loop step by step (fd_score_plan says so).
+ *   fd_score_set_labels        binds a DEVICE int32 vector of B labels to the model (borrowed; y == NULL clears it).  While labels
+ *                              are bound, fd_score_forward, fd_score_forward_train, fd_score_train_dsm and fd_score_input_vjp with
+ *                              another B return FD_ERR_ARG.  With nothing bound every row reads the null token, so every entry
+ *                              point that takes no labels runs a labelled model as its unconditional model.  A label outside
+ *                              [0, K] reads the null token (the table is never read out of bounds).
+ *   fd_score_set_label_dropout p in [0, 1]: every TRAINING forward replaces each row's label by the null token with probability p,
+ *                              decided by the Philox stream of that call: label b is lane b % 4 (uniform < p) of counter
+ *                              offset + (0xFFFF << 40) + b / 4 under the call's seed -- the counter window of encoder layer 16383,
+ *                              which the dropout sites never reach.  Eval forwards never drop.  The class-table gradient
+ *                              dTable[k] = sum_{b: y_b = k} dtemb[b] is summed over b in ascending order (no atomics).
+ *   fd_label_dropout           the decision kernel alone: y_out[b] = the label the training forward of (seed, offset) uses for
+ *                              y[b] (y == NULL: all null).  y, y_out: device int32[B]. */
+int64_t fd_score_param_count_cond(const fd_model_dims* dims, int n_classes);
+int fd_score_layout_cond(const fd_model_dims* dims, int n_classes, fd_param_entry* entries, int* n_entries);
+int fd_score_create_cond(fd_ctx* ctx, const fd_model_dims* dims, int n_classes, fd_score** out);
+int fd_score_set_labels(fd_score* m, const int32_t* y, int B);
+int fd_score_set_label_dropout(fd_score* m, float p);
+int fd_label_dropout(fd_ctx* ctx, const int32_t* y, int32_t* y_out, int B, int n_classes, float p, uint64_t seed, uint64_t offset,
+                     void* stream);
+
 /* Derive the engine-side weight images from the flat fp32 parameters (device pointer):
  * max_norm-renormed positional table (the reference renorms in place inside forward,
  * transformer.py:13-15,27), bf16 MFMA-fragment-ordered matrices, folded biases.
@@ -415,6 +441,22 @@ int fd_sampler_run_dpm(fd_score* m, const fd_sde_params* sde, const float* G, co
                        float* x, int B, int mode, void* stream);
 int fd_dpm_stage(fd_ctx* ctx, const fd_sde_params* sde, const float* G, const float* x, const float* score, const float* d_prev,
                  double t_prev, double t, double t_next, float* x_out, float* d_out, int B, int T, int C, void* stream);
+
+/* Classifier-free guidance (NOT in the reference; Ho & Salimans 2022) on a class-conditional model: every loop above with the score
+ *   s = w s(x, t, y) + (1 - w) s(x, t, null)        (the two products as written: w = 1 is s(x, t, y), w = 0 is s(x, t, null), exactly)
+ * y: device int32[B] labels or NULL.  w == 1: one evaluation per step with y bound; w == 0 or y == NULL: one evaluation with the
+ * null token; x is (B,T,C) then and the loop is fd_sampler_run's / fd_sampler_run_ode's step-wise form.  Otherwise the two
+ * evaluations of a step run as ONE forward on 2B rows and x is a (2B,T,C) buffer: rows [0, B) in/out, rows [B, 2B) the same state
+ * evaluated with the null token (overwritten on entry and by every step).  One fused kernel per step reads x and both scores and
+ * writes the new state to both halves.
+ *   fd_sampler_run_cfg    : the reverse-SDE loop; timesteps, dt, z_steps (n_steps,B,T,C) and the Philox counters (n = B T C elements
+ *                           per step) as fd_sampler_run.
+ *   fd_sampler_run_ode_cfg: solver 0 Euler, 1 Heun (grid as fd_sampler_run_ode), 2 DDIM, 3 DPM-Solver++ 2M (grid as fd_sampler_run_dpm).
+ * FD_ERR_ARG on an unlabelled model.  No host synchronisation inside the loops. */
+int fd_sampler_run_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
+                       const int32_t* y, float w, const float* z_steps, uint64_t seed, uint64_t offset, int B, int mode, void* stream);
+int fd_sampler_run_ode_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
+                           float* x, const int32_t* y, float w, int B, int mode, void* stream);
 
 /* Likelihood extension (NOT in the reference; Song et al. 2021, Sec. 4.3 and App. D.2): the exact log-density of the
  * probability-flow ODE above,
