@@ -4,29 +4,23 @@
 // A labelled model owns one more tensor, class_encoder.weight (K + 1, D), row K the null (unconditional) token; k_time_embed adds
 // row y_b of it to the time embedding of series b (fd_score_f32.hip), which conditions every forward and training path outside the
 // persistent kernel.  Here: the label path of the ABI (fd_score_set_labels), label dropout (k_label_dropout), the class-table
-// gradient (k_class_table_bwd) and the guided sampling loops with their fused step kernels:
+// gradient (k_class_table_bwd) and guided sampling:
 //   s = w s_cond + (1 - w) s_uncond                (the two products as written: w = 1 gives s_cond, w = 0 gives s_uncond, exactly)
-// The two evaluations of a step run as ONE forward on 2B rows -- rows [0, B) carry the labels, rows [B, 2B) the same state with the
-// null token -- and ONE kernel then reads x from the conditional half and the score from both, applies the reverse-SDE step (the
-// arithmetic, Philox counters and element-to-lane layout of k_sde_step over n = B T C) or the ODE / data-prediction stage
-// (fd_mega_params.h), and writes the new state to both halves.  No LDS, no atomics.
+// Guidance is an option (fd_guide, fd_loop.h) of the two plain step-by-step loops of fd_sampler.hip, not a loop of its own: the entry
+// points here check their arguments, plan the guide and call the shared loop body.  The two evaluations of a step run as ONE
+// forward on 2B rows -- rows [0, B) carry the labels, rows [B, 2B) the same state with the null token -- and ONE kernel then reads
+// x from the conditional half and the score from both, applies the reverse-SDE step (k_cfg_sde_step here: the arithmetic, Philox
+// counters and element-to-lane layout of k_sde_step over n = B T C) or the ODE / data-prediction stage (k_stage<.., PAIR>,
+// fd_ode.hip), and writes the new state to both halves.  No LDS, no atomics.
 #include <cmath>
 
-#include "fd_ode.h"
+#include "fd_loop.h"
 #include "fd_philox.h"
-#include "fd_score.h"
 #include "fd_sde.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline int grid_for(size_t items, int num_cu) {
-    size_t blocks = (items + kBlock - 1) / kBlock;
-    const size_t cap = (size_t)num_cu * 64;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
 
 // out[b] = y[b] (the null token K when y is null or the label lies outside [0, K]), replaced by K with probability p: label b is
 // lane b % 4 of Philox counter ctr0 + b / 4
@@ -70,11 +64,6 @@ __global__ __launch_bounds__(kBlock) void k_cfg_labels(const int* __restrict__ y
     lab[i] = v;
 }
 
-// the guided score of one element; the intrinsics keep the two products and the sum from being contracted into an fma
-__device__ __forceinline__ float guided(float sc, float su, float w, float omw) {
-    return __fadd_rn(__fmul_rn(w, sc), __fmul_rn(omw, su));
-}
-
 // Guided Euler-Maruyama step: x (2n) in place, score (2n); group g = elements 4g .. 4g + 3 of the conditional half and Philox counter
 // offset + g, as k_sde_step.  V4 (C % 4 == 0, hence n % 4 == 0 and both halves 16-byte aligned): 16-byte accesses, one row per
 // group; else scalar accesses.
@@ -98,10 +87,10 @@ __global__ __launch_bounds__(kBlock) void k_cfg_sde_step(const float* __restrict
             const float4 su = *reinterpret_cast<const float4*>(score + n + e);
             const float Gt = G[(e / (size_t)C) % (size_t)T];
             float4 o;
-            o.x = fd_sde_apply(xv.x, guided(sc.x, su.x, w, omw), z[0], Gt, cf);
-            o.y = fd_sde_apply(xv.y, guided(sc.y, su.y, w, omw), z[1], Gt, cf);
-            o.z = fd_sde_apply(xv.z, guided(sc.z, su.z, w, omw), z[2], Gt, cf);
-            o.w = fd_sde_apply(xv.w, guided(sc.w, su.w, w, omw), z[3], Gt, cf);
+            o.x = fd_sde_apply(xv.x, fd_guided(sc.x, su.x, w, omw), z[0], Gt, cf);
+            o.y = fd_sde_apply(xv.y, fd_guided(sc.y, su.y, w, omw), z[1], Gt, cf);
+            o.z = fd_sde_apply(xv.z, fd_guided(sc.z, su.z, w, omw), z[2], Gt, cf);
+            o.w = fd_sde_apply(xv.w, fd_guided(sc.w, su.w, w, omw), z[3], Gt, cf);
             *reinterpret_cast<float4*>(x + e) = o;
             *reinterpret_cast<float4*>(x + n + e) = o;
         } else {
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void k_cfg_sde_step(const float* __restrict
                 const size_t ei = e + i;
                 if (ei < n) {
                     const float zi = zin ? zin[ei] : z[i];
-                    const float o = fd_sde_apply(x[ei], guided(score[ei], score[n + ei], w, omw), zi, G[(ei / (size_t)C) % (size_t)T], cf);
+                    const float o = fd_sde_apply(x[ei], fd_guided(score[ei], score[n + ei], w, omw), zi, G[(ei / (size_t)C) % (size_t)T], cf);
                     x[ei] = o;
                     x[n + ei] = o;
                 }
@@ -119,46 +108,12 @@ __global__ __launch_bounds__(kBlock) void k_cfg_sde_step(const float* __restrict
     }
 }
 
-// Guided ODE / data-prediction stage: ownership and arithmetic of k_ode_stage / k_dpm_stage (fd_ode.hip) on the conditional half,
-// the solver state x0 / v0 (B,T,C) as there; the new state goes to both halves
-template <bool V4, bool DPM>
-__global__ __launch_bounds__(kBlock) void k_cfg_ode_stage(const float* __restrict__ G, float* __restrict__ x,
-                                                            const float* __restrict__ score, float* __restrict__ x0,
-                                                            float* __restrict__ v0, size_t n, int T, int C, fd_ode_step_coef c,
-                                                            fd_dpm_coef dw, float w, float omw) {
-    const size_t items = V4 ? n / 4 : n;
-    for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < items; i += (size_t)gridDim.x * kBlock) {
-        if (V4) {
-            const size_t e = 4 * i;
-            const float gk = c.g * G[(e / (size_t)C) % (size_t)T];
-            const float4 xv = *reinterpret_cast<const float4*>(x + e);
-            const float4 sc = *reinterpret_cast<const float4*>(score + e);
-            const float4 su = *reinterpret_cast<const float4*>(score + n + e);
-            const float s0 = guided(sc.x, su.x, w, omw), s1 = guided(sc.y, su.y, w, omw), s2 = guided(sc.z, su.z, w, omw),
-                        s3 = guided(sc.w, su.w, w, omw);
-            const float4 o = DPM ? fd_dpm_stage4(xv, s0, s1, s2, s3, gk, c, dw, x0 + e) : fd_ode_stage4(xv, s0, s1, s2, s3, gk, c, x0 + e, v0 + e);
-            *reinterpret_cast<float4*>(x + e) = o;
-            *reinterpret_cast<float4*>(x + n + e) = o;
-        } else {
-            const float gk = c.g * G[(i / (size_t)C) % (size_t)T];
-            const float s = guided(score[i], score[n + i], w, omw);
-            const float o = DPM ? fd_dpm_stage1(x[i], s, gk, c, dw, x0 + i) : fd_ode_stage1(x[i], s, gk, c, x0 + i, v0 + i);
-            x[i] = o;
-            x[n + i] = o;
-        }
-    }
-}
-
-// What a guided loop runs: pair = two evaluations per step as one forward on 2B rows; else one evaluation on B rows with `bound`
-// labels (y, or null = the null token on every row)
-struct CfgPlan {
-    bool pair;
-    const int* bound;
-};
-CfgPlan cfg_plan(const int* y, float w) {
+// What a guided loop runs: pair = two evaluations per step as one forward on 2B rows; else one evaluation on B rows with y bound
+// (or null = the null token on every row)
+fd_guide cfg_plan(const int* y, float w) {
     // FDIFF_CFG_FORCE_PAIR (tests): the two-evaluation form also at w = 1 and w = 0, where the combine is exact
     const bool pair = y && ((w != 1.f && w != 0.f) || getenv("FDIFF_CFG_FORCE_PAIR"));
-    return CfgPlan{pair, (!pair && y && w != 0.f) ? y : nullptr};
+    return fd_guide{pair, (pair || w != 0.f) ? y : nullptr, w, (float)(1.0 - (double)w)};
 }
 
 int cfg_check(fd_score* m, const void* G, const void* timesteps, const void* x, int n_steps, float w, const char* who) {
@@ -169,22 +124,6 @@ int cfg_check(fd_score* m, const void* G, const void* timesteps, const void* x, 
     FD_REQUIRE(ctx, std::isfinite(w), "%s: the guidance scale is not finite", who);
     return FD_OK;
 }
-
-// binds the loop's own label vector for its forwards; the caller's binding is back when the scope ends (the kernels have taken their
-// pointers at launch)
-struct LabelScope {
-    fd_score* m;
-    const int* y;
-    int B;
-    LabelScope(fd_score* mm, const int* lab, int rows) : m(mm), y(mm->labels), B(mm->labels_B) {
-        m->labels = lab;
-        m->labels_B = lab ? rows : 0;
-    }
-    ~LabelScope() {
-        m->labels = y;
-        m->labels_B = B;
-    }
-};
 
 }  // namespace
 
@@ -264,8 +203,27 @@ extern "C" int fd_label_dropout(fd_ctx* ctx, const int32_t* y, int32_t* y_out, i
 }
 
 // ------------------------------------------------------------------ guided loops
-// Workspace of a guided loop behind the forward scratch of R rows: score (R,T,C), nstate solver buffers (B,T,C), labels (2B) when
-// pair; then fd_step_table's t vectors.
+int fd_guide_begin(fd_score* m, const fd_guide* g, int* lab, float* x, int B, hipStream_t s) {
+    if (!g || !g->pair) return FD_OK;
+    const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
+    hipLaunchKernelGGL(k_cfg_labels, dim3((2 * B + kBlock - 1) / kBlock), dim3(kBlock), 0, s, g->y, lab, B, m->n_classes);
+    FD_HIP(m->ctx, hipMemcpyAsync(x + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return FD_OK;
+}
+
+int fd_cfg_sde_step(fd_ctx* ctx, const fd_sde_params* sde, const float* G, float* x, const float* score, const float* z, uint64_t seed,
+                    uint64_t offset, double t, float dt, const fd_guide& g, int B, int T, int C, hipStream_t s) {
+    const size_t n = (size_t)B * T * C;
+    const SdeCoef cf = fd_sde_coef(*sde, t, dt);
+    const dim3 grid(fd_grid_for((n + 3) / 4, kBlock, ctx->num_cu));
+    if (C % 4 == 0)
+        hipLaunchKernelGGL(k_cfg_sde_step<true>, grid, dim3(kBlock), 0, s, G, x, score, z, n, T, C, cf, g.w, g.omw, seed, offset);
+    else
+        hipLaunchKernelGGL(k_cfg_sde_step<false>, grid, dim3(kBlock), 0, s, G, x, score, z, n, T, C, cf, g.w, g.omw, seed, offset);
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
+}
+
 extern "C" int fd_sampler_run_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt,
                                   float* x, const int32_t* y, float w, const float* z_steps, uint64_t seed, uint64_t offset, int B,
                                   int mode, void* stream) {
@@ -273,46 +231,8 @@ extern "C" int fd_sampler_run_cfg(fd_score* m, const fd_sde_params* sde, const f
     fd_ctx* ctx = m->ctx;
     if (int rc = cfg_check(m, G, timesteps, x, n_steps, w, "fd_sampler_run_cfg")) return rc;
     FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_cfg: step size must be > 0 (sde.py:158)");
-    hipStream_t s = (hipStream_t)stream;
-    const CfgPlan pl = cfg_plan(y, w);
-    const int T = m->d.max_len, C = m->d.n_channels, K = m->n_classes;
-    const int R = pl.pair ? 2 * B : B;
-    const size_t n = (size_t)B * T * C;
-    const size_t fwd = fd_loop_fwd_workspace(m, R);
-    const size_t sbytes = fd_ws::padded((size_t)R * T * C * sizeof(float));
-    const size_t lbytes = pl.pair ? fd_ws::padded((size_t)R * sizeof(int)) : 0;
-    float* tvec0 = nullptr;
-    size_t tstride = 0;
-    if (int rc = fd_step_table(ctx, fwd, sbytes + lbytes, timesteps, n_steps, R, s, &tvec0, &tstride)) return rc;
-    float* score = (float*)((char*)ctx->ws + fwd);
-    int* lab = (int*)((char*)ctx->ws + fwd + sbytes);
-    if (pl.pair) {
-        hipLaunchKernelGGL(k_cfg_labels, dim3((R + kBlock - 1) / kBlock), dim3(kBlock), 0, s, y, lab, B, K);
-        FD_HIP(ctx, hipMemcpyAsync(x + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    LabelScope scope(m, pl.pair ? lab : pl.bound, R);
-    const float omw = (float)(1.0 - (double)w);
-    const uint64_t per_step = (uint64_t)((n + 3) / 4);
-    for (int i = 0; i < n_steps; ++i) {
-        float* tvec = tvec0 + (size_t)i * tstride;
-        if (!tstride) fd_fill(tvec, R, timesteps[i], s);
-        if (int rc = fd_score_forward_any(m, x, tvec, score, R, mode, s)) return rc;
-        const float* z = z_steps ? z_steps + (size_t)i * n : nullptr;
-        const uint64_t ctr = offset + (uint64_t)i * per_step;
-        if (!pl.pair) {
-            if (int rc = fd_sde_step(ctx, sde, G, x, score, z, seed, ctr, (double)timesteps[i], dt, x, B, T, C, stream)) return rc;
-            continue;
-        }
-        const SdeCoef cf = fd_sde_coef(*sde, (double)timesteps[i], dt);
-        if (C % 4 == 0)
-            hipLaunchKernelGGL(k_cfg_sde_step<true>, dim3(grid_for(per_step, ctx->num_cu)), dim3(kBlock), 0, s, G, x, (const float*)score, z,
-                               n, T, C, cf, w, omw, seed, ctr);
-        else
-            hipLaunchKernelGGL(k_cfg_sde_step<false>, dim3(grid_for(per_step, ctx->num_cu)), dim3(kBlock), 0, s, G, x, (const float*)score, z,
-                               n, T, C, cf, w, omw, seed, ctr);
-    }
-    FD_LAUNCH_CHECK(ctx);
-    return FD_OK;
+    const fd_guide g = cfg_plan(y, w);
+    return fd_sampler_sde_loop(m, sde, G, timesteps, n_steps, dt, x, z_steps, seed, offset, B, mode, (hipStream_t)stream, &g);
 }
 
 // solver: 0 Euler, 1 Heun (fd_sampler_run_ode's grids), 2 DDIM, 3 DPM-Solver++ 2M (fd_sampler_run_dpm's)
@@ -322,61 +242,6 @@ extern "C" int fd_sampler_run_ode_cfg(fd_score* m, const fd_sde_params* sde, con
     fd_ctx* ctx = m->ctx;
     if (int rc = cfg_check(m, G, timesteps, x, n_steps, w, "fd_sampler_run_ode_cfg")) return rc;
     FD_REQUIRE(ctx, solver >= 0 && solver <= 3, "fd_sampler_run_ode_cfg: solver %d (0 Euler, 1 Heun, 2 DDIM, 3 DPM-Solver++ 2M)", solver);
-    std::vector<fd_ode_step_coef> rows;
-    std::vector<fd_dpm_coef> dpm;
-    const bool is_dpm = solver >= 2;
-    if (is_dpm) {
-        if (int rc = fd_dpm_table(ctx, sde, timesteps, n_steps, solver, &rows, &dpm)) return rc;
-    } else if (int rc = fd_ode_table(ctx, sde, timesteps, n_steps, solver, &rows)) {
-        return rc;
-    }
-    const int nstate = solver == 1 ? 2 : solver == 3 ? 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    const CfgPlan pl = cfg_plan(y, w);
-    const int T = m->d.max_len, C = m->d.n_channels, K = m->n_classes;
-    const int R = pl.pair ? 2 * B : B;
-    const int n_eval = (int)rows.size();
-    const size_t n = (size_t)B * T * C;
-    const size_t fwd = fd_loop_fwd_workspace(m, R);
-    const size_t sbytes = fd_ws::padded((size_t)R * T * C * sizeof(float));
-    const size_t buf = fd_ws::padded(n * sizeof(float));
-    const size_t lbytes = pl.pair ? fd_ws::padded((size_t)R * sizeof(int)) : 0;
-    std::vector<float> t_eval(n_eval);
-    for (int k = 0; k < n_eval; ++k) t_eval[k] = rows[k].t;
-    float* tvec0 = nullptr;
-    size_t tstride = 0;
-    if (int rc = fd_step_table(ctx, fwd, sbytes + nstate * buf + lbytes, t_eval.data(), n_eval, R, s, &tvec0, &tstride)) return rc;
-    char* base = (char*)ctx->ws + fwd;
-    float* score = (float*)base;
-    float* x0 = nstate > 0 ? (float*)(base + sbytes) : nullptr;
-    float* v0 = nstate > 1 ? (float*)(base + sbytes + buf) : nullptr;
-    int* lab = (int*)(base + sbytes + nstate * buf);
-    if (pl.pair) {
-        hipLaunchKernelGGL(k_cfg_labels, dim3((R + kBlock - 1) / kBlock), dim3(kBlock), 0, s, y, lab, B, K);
-        FD_HIP(ctx, hipMemcpyAsync(x + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    LabelScope scope(m, pl.pair ? lab : pl.bound, R);
-    const float omw = (float)(1.0 - (double)w);
-    const bool v4 = C % 4 == 0;
-    const int grid = grid_for(v4 ? n / 4 : n, ctx->num_cu);
-    for (int k = 0; k < n_eval; ++k) {
-        float* tvec = tvec0 + (size_t)k * tstride;
-        if (!tstride) fd_fill(tvec, R, t_eval[k], s);
-        if (int rc = fd_score_forward_any(m, x, tvec, score, R, mode, s)) return rc;
-        if (!pl.pair) {
-            if (int rc = fd_ode_stage(ctx, G, x, score, x0, v0, rows[k], B, T, C, s, is_dpm ? &dpm[k] : nullptr)) return rc;
-            continue;
-        }
-        const fd_dpm_coef dw = is_dpm ? dpm[k] : fd_dpm_coef{};
-#define FD_CFG_ODE(V4_, DPM_)                                                                                                         \
-    hipLaunchKernelGGL((k_cfg_ode_stage<V4_, DPM_>), dim3(grid), dim3(kBlock), 0, s, G, x, (const float*)score, x0, v0, n, T, C, rows[k], \
-                       dw, w, omw)
-        if (v4 && is_dpm) FD_CFG_ODE(true, true);
-        else if (v4) FD_CFG_ODE(true, false);
-        else if (is_dpm) FD_CFG_ODE(false, true);
-        else FD_CFG_ODE(false, false);
-#undef FD_CFG_ODE
-    }
-    FD_LAUNCH_CHECK(ctx);
-    return FD_OK;
+    const fd_guide g = cfg_plan(y, w);
+    return fd_sampler_ode_loop(m, sde, G, timesteps, n_steps, solver, x, B, mode, (hipStream_t)stream, &g);
 }

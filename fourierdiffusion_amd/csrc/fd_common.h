@@ -202,3 +202,11 @@ struct fd_ws {
 };
 
 static inline int fd_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// grid of a grid-stride elementwise kernel: one thread per item, at most 64 workgroups per CU
+inline int fd_grid_for(size_t items, int block, int num_cu) {
+    size_t blocks = (items + block - 1) / block;
+    const size_t cap = (size_t)num_cu * 64;
+    if (blocks > cap) blocks = cap;
+    return (int)(blocks < 1 ? 1 : blocks);
+}

@@ -24,8 +24,8 @@
 
 #include "fd_common.h"
 #include "fd_engine.h"
+#include "fd_loop.h"
 #include "fd_philox.h"
-#include "fd_score.h"
 #include "fd_sde.h"
 
 namespace {

@@ -25,8 +25,8 @@
 
 #include "fd_common.h"
 #include "fd_engine.h"
+#include "fd_loop.h"
 #include "fd_philox.h"
-#include "fd_score.h"
 #include "fd_sde.h"
 
 namespace {
@@ -325,22 +325,16 @@ extern "C" int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, 
         al[i] = (float)aa;
         sd[i] = (float)ss;
     }
-    // workspace as fd_sampler_run's step-by-step path
     const size_t n = (size_t)B * T * C;
-    const size_t fwd = fd_loop_fwd_workspace(m, B);
-    float* tvec0 = nullptr;
-    size_t tstride = 0;
-    if (int rc = fd_step_table(ctx, fwd, fd_ws::padded(n * sizeof(float)), timesteps, n_steps, B, s, &tvec0, &tstride)) return rc;
-    float* score = (float*)((char*)ctx->ws + fwd);
+    fd_step_loop lp;
+    if (int rc = fd_step_loop_open(&lp, m, B, mode, 0, timesteps, n_steps, s)) return rc;
 
     // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run), observation noise behind them
     const uint64_t per_step = (uint64_t)((n + 3) / 4);
-    a.x = x; a.out = x; a.score = score;
+    a.x = x; a.out = x; a.score = lp.score;
     a.seed = seed;
     for (int i = 0; i < n_steps; ++i) {
-        float* tvec = tvec0 + (size_t)i * tstride;
-        if (!tstride) fd_fill(tvec, B, timesteps[i], s);
-        if (int rc = fd_score_forward_any(m, x, tvec, score, B, mode, s)) return rc;
+        if (int rc = fd_step_loop_eval(&lp, i, x)) return rc;
         a.zstep = z_steps ? z_steps + (size_t)i * n : nullptr;
         a.zobs = zobs_steps ? zobs_steps + (size_t)i * n : nullptr;
         a.cf = cf[i];

@@ -11,8 +11,8 @@
 #include <cmath>
 
 #include "fd_engine.h"
+#include "fd_loop.h"
 #include "fd_ode.h"
-#include "fd_score.h"
 #include "fd_sde.h"
 
 namespace {

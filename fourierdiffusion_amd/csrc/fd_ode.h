@@ -15,10 +15,16 @@ int fd_ode_table(fd_ctx* ctx, const fd_sde_params* sde, const float* timesteps, 
 // log-SNR lambda = log(alpha / s) strictly increasing along it.
 int fd_dpm_table(fd_ctx* ctx, const fd_sde_params* sde, const float* timesteps, int n_steps, int solver,
                  std::vector<fd_ode_step_coef>* rows, std::vector<fd_dpm_coef>* dpm);
+// The table of solver 0 Euler, 1 Heun (fd_ode_table), 2 DDIM, 3 DPM-Solver++ 2M (fd_dpm_table; *dpm stays empty for 0 and 1) and
+// the number of (B,T,C) state buffers its step-by-step loop keeps: Heun 2, DPM-Solver++ 2M 1, else 0.
+int fd_solver_rows(fd_ctx* ctx, const fd_sde_params* sde, const float* timesteps, int n_steps, int solver,
+                   std::vector<fd_ode_step_coef>* rows, std::vector<fd_dpm_coef>* dpm, int* nstate);
 // x <- stage(x, score) in place on (B,T,C); x0 / v0: the Heun state, (B,T,C) each (not read for FD_ODE_EULER).  Data-prediction
-// stages (FD_ODE_DDIM and above): w is their second coefficient pair and x0 holds D_prev (not touched by FD_ODE_DDIM).
+// stages (FD_ODE_DDIM and above): w is their second coefficient pair and x0 holds D_prev (not touched by FD_ODE_DDIM).  A paired
+// guide g (fd_loop.h): x and score are (2B,T,C), the stage runs on the guided score and writes both halves of x.
+struct fd_guide;
 int fd_ode_stage(fd_ctx* ctx, const float* G, float* x, const float* score, float* x0, float* v0, const fd_ode_step_coef& c,
-                 int B, int T, int C, hipStream_t s, const fd_dpm_coef* w = nullptr);
+                 int B, int T, int C, hipStream_t s, const fd_dpm_coef* w = nullptr, const fd_guide* g = nullptr);
 // the loop forms of fd_score_bf16.hip; FD_ERR_UNSUPPORTED (x untouched) when the model / shape has no such path.  dpm: the
 // data-prediction solvers' second coefficient pair of every row, or null (Euler / Heun)
 int fd_sampler_run_ode_mega(fd_score* m, const std::vector<fd_ode_step_coef>& rows, const float* G, float* x, int B, hipStream_t s,

@@ -6,22 +6,17 @@
 // step-by-step loop (fp32 parity mode, the MLP / LSTM backbones, FDIFF_SAMPLER_STEPWISE).  No random numbers are drawn.
 //
 // The data-prediction solvers (DDIM, DPM-Solver++ 2M; fd_mega_params.h) run on the same rows and through the same loop forms: their
-// table (fd_dpm_table), their elementwise stage and its step-wise entry point (fd_dpm_stage) are here as well.
+// table (fd_dpm_table) and their step-wise entry point (fd_dpm_stage) are here as well.  ONE stage kernel (k_stage) serves both
+// families, plain and under classifier-free guidance (fd_guide, fd_loop.h).
 #include <cmath>
 
+#include "fd_loop.h"
 #include "fd_ode.h"
 #include "fd_sde.h"
 
 namespace {
 
 constexpr int kBlock = 256;
-
-inline int grid_for(size_t items, int num_cu) {
-    size_t blocks = (items + kBlock - 1) / kBlock;
-    const size_t cap = (size_t)num_cu * 64;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
-}
 
 // v = -a x - 0.5 (g G_k)^2 s, one element per thread and iteration
 __global__ __launch_bounds__(kBlock) void k_ode_drift(const float* __restrict__ G, const float* __restrict__ x,
@@ -33,44 +28,50 @@ __global__ __launch_bounds__(kBlock) void k_ode_drift(const float* __restrict__ 
     }
 }
 
-// one stage on (B,T,C).  V4 (C % 4 == 0): a thread owns four elements of one row, as the persistent kernel's epilogue lanes do
-template <bool V4>
-__global__ __launch_bounds__(kBlock) void k_ode_stage(const float* __restrict__ G, float* __restrict__ x,
-                                                        const float* __restrict__ score, float* __restrict__ x0,
-                                                        float* __restrict__ v0, size_t n, int T, int C, fd_ode_step_coef c) {
+// One stage on (B,T,C), n = B T C elements.  V4 (C % 4 == 0): a thread owns four elements of one row, as the persistent kernel's
+// epilogue lanes do.  DPM: a data-prediction stage (dw its second coefficient pair, x0 = D_prev, updated in place; v0 unused), else
+// Euler / Heun with the Heun state x0 / v0.  PAIR (classifier-free guidance): x and score hold 2n elements, the score is
+// fd_guided(score[e], score[n + e]) and the new state goes to both halves.
+template <bool V4, bool DPM, bool PAIR>
+__global__ __launch_bounds__(kBlock) void k_stage(const float* __restrict__ G, float* __restrict__ x, const float* __restrict__ score,
+                                                    float* __restrict__ x0, float* __restrict__ v0, size_t n, int T, int C,
+                                                    fd_ode_step_coef c, fd_dpm_coef dw, float w, float omw) {
     const size_t items = V4 ? n / 4 : n;
     for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < items; i += (size_t)gridDim.x * kBlock) {
         if (V4) {
             const size_t e = 4 * i;
             const float gk = c.g * G[(e / (size_t)C) % (size_t)T];
             const float4 xv = *reinterpret_cast<const float4*>(x + e);
-            const float4 sv = *reinterpret_cast<const float4*>(score + e);
-            *reinterpret_cast<float4*>(x + e) = fd_ode_stage4(xv, sv.x, sv.y, sv.z, sv.w, gk, c, x0 + e, v0 + e);
+            float4 sv = *reinterpret_cast<const float4*>(score + e);
+            if (PAIR) {
+                const float4 su = *reinterpret_cast<const float4*>(score + n + e);
+                sv.x = fd_guided(sv.x, su.x, w, omw);
+                sv.y = fd_guided(sv.y, su.y, w, omw);
+                sv.z = fd_guided(sv.z, su.z, w, omw);
+                sv.w = fd_guided(sv.w, su.w, w, omw);
+            }
+            const float4 o = DPM ? fd_dpm_stage4(xv, sv.x, sv.y, sv.z, sv.w, gk, c, dw, x0 + e)
+                                 : fd_ode_stage4(xv, sv.x, sv.y, sv.z, sv.w, gk, c, x0 + e, v0 + e);
+            *reinterpret_cast<float4*>(x + e) = o;
+            if (PAIR) *reinterpret_cast<float4*>(x + n + e) = o;
         } else {
             const float gk = c.g * G[(i / (size_t)C) % (size_t)T];
-            x[i] = fd_ode_stage1(x[i], score[i], gk, c, x0 + i, v0 + i);
+            const float sv = PAIR ? fd_guided(score[i], score[n + i], w, omw) : score[i];
+            const float o = DPM ? fd_dpm_stage1(x[i], sv, gk, c, dw, x0 + i) : fd_ode_stage1(x[i], sv, gk, c, x0 + i, v0 + i);
+            x[i] = o;
+            if (PAIR) x[n + i] = o;
         }
     }
 }
 
-// one data-prediction stage on (B,T,C), same ownership as k_ode_stage; dprev: D_prev, updated in place
-template <bool V4>
-__global__ __launch_bounds__(kBlock) void k_dpm_stage(const float* __restrict__ G, float* __restrict__ x,
-                                                        const float* __restrict__ score, float* __restrict__ dprev, size_t n, int T,
-                                                        int C, fd_ode_step_coef c, fd_dpm_coef w) {
-    const size_t items = V4 ? n / 4 : n;
-    for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < items; i += (size_t)gridDim.x * kBlock) {
-        if (V4) {
-            const size_t e = 4 * i;
-            const float gk = c.g * G[(e / (size_t)C) % (size_t)T];
-            const float4 xv = *reinterpret_cast<const float4*>(x + e);
-            const float4 sv = *reinterpret_cast<const float4*>(score + e);
-            *reinterpret_cast<float4*>(x + e) = fd_dpm_stage4(xv, sv.x, sv.y, sv.z, sv.w, gk, c, w, dprev + e);
-        } else {
-            const float gk = c.g * G[(i / (size_t)C) % (size_t)T];
-            x[i] = fd_dpm_stage1(x[i], score[i], gk, c, w, dprev + i);
-        }
-    }
+template <bool V4, bool DPM>
+void launch_stage(fd_ctx* ctx, const float* G, float* x, const float* score, float* x0, float* v0, size_t n, int T, int C,
+                  const fd_ode_step_coef& c, const fd_dpm_coef& dw, const fd_guide* g, hipStream_t s) {
+    const dim3 grid(fd_grid_for(V4 ? n / 4 : n, kBlock, ctx->num_cu));
+    if (g && g->pair)
+        hipLaunchKernelGGL((k_stage<V4, DPM, true>), grid, dim3(kBlock), 0, s, G, x, score, x0, v0, n, T, C, c, dw, g->w, g->omw);
+    else
+        hipLaunchKernelGGL((k_stage<V4, DPM, false>), grid, dim3(kBlock), 0, s, G, x, score, x0, v0, n, T, C, c, dw, 0.f, 0.f);
 }
 
 // (alpha, s, lambda = log(alpha / s)) of the perturbation kernel at t, in double (sde.py:108-123, 187-210).  VP: s^2 = 1 - alpha^2
@@ -156,19 +157,23 @@ int fd_ode_table(fd_ctx* ctx, const fd_sde_params* sde, const float* ts, int n_s
     return FD_OK;
 }
 
+int fd_solver_rows(fd_ctx* ctx, const fd_sde_params* sde, const float* ts, int n_steps, int solver, std::vector<fd_ode_step_coef>* rows,
+                   std::vector<fd_dpm_coef>* dpm, int* nstate) {
+    *nstate = solver == 1 ? 2 : solver == 3 ? 1 : 0;
+    dpm->clear();
+    return solver >= 2 ? fd_dpm_table(ctx, sde, ts, n_steps, solver, rows, dpm) : fd_ode_table(ctx, sde, ts, n_steps, solver, rows);
+}
+
 int fd_ode_stage(fd_ctx* ctx, const float* G, float* x, const float* score, float* x0, float* v0, const fd_ode_step_coef& c, int B,
-                 int T, int C, hipStream_t s, const fd_dpm_coef* w) {
+                 int T, int C, hipStream_t s, const fd_dpm_coef* w, const fd_guide* g) {
     const size_t n = (size_t)B * T * C;
-    if (c.stage >= FD_ODE_DDIM) {
-        FD_REQUIRE(ctx, w && (x0 || c.stage == FD_ODE_DDIM), "fd_ode_stage: a data-prediction stage needs its coefficients and state");
-        if (C % 4 == 0)
-            hipLaunchKernelGGL(k_dpm_stage<true>, dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0, s, G, x, score, x0, n, T, C, c, *w);
-        else
-            hipLaunchKernelGGL(k_dpm_stage<false>, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, s, G, x, score, x0, n, T, C, c, *w);
-    } else if (C % 4 == 0)
-        hipLaunchKernelGGL(k_ode_stage<true>, dim3(grid_for(n / 4, ctx->num_cu)), dim3(kBlock), 0, s, G, x, score, x0, v0, n, T, C, c);
-    else
-        hipLaunchKernelGGL(k_ode_stage<false>, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, s, G, x, score, x0, v0, n, T, C, c);
+    const bool v4 = C % 4 == 0, dpm = c.stage >= FD_ODE_DDIM;
+    FD_REQUIRE(ctx, !dpm || (w && (x0 || c.stage == FD_ODE_DDIM)), "fd_ode_stage: a data-prediction stage needs its coefficients and state");
+    const fd_dpm_coef dw = dpm ? *w : fd_dpm_coef{};
+    if (v4 && dpm) launch_stage<true, true>(ctx, G, x, score, x0, v0, n, T, C, c, dw, g, s);
+    else if (v4) launch_stage<true, false>(ctx, G, x, score, x0, v0, n, T, C, c, dw, g, s);
+    else if (dpm) launch_stage<false, true>(ctx, G, x, score, x0, v0, n, T, C, c, dw, g, s);
+    else launch_stage<false, false>(ctx, G, x, score, x0, v0, n, T, C, c, dw, g, s);
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
 }
@@ -182,7 +187,7 @@ extern "C" int fd_pf_ode_drift(fd_ctx* ctx, const fd_sde_params* sde, const floa
     FD_REQUIRE(ctx, std::isfinite(t), "fd_pf_ode_drift: t is not finite");
     const size_t n = (size_t)B * T * C;
     const SdeCoef c = fd_sde_coef(*sde, t, 0.f);
-    hipLaunchKernelGGL(k_ode_drift, dim3(grid_for(n, ctx->num_cu)), dim3(kBlock), 0, (hipStream_t)stream, G, x, score, v_out, n, T, C,
+    hipLaunchKernelGGL(k_ode_drift, dim3(fd_grid_for(n, kBlock, ctx->num_cu)), dim3(kBlock), 0, (hipStream_t)stream, G, x, score, v_out, n, T, C,
                        c.a_x, c.g);
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;

@@ -136,16 +136,7 @@ int fd_bb_backward(fd_score* m, const float* dout, float* grads, int accumulate,
 size_t fd_bb_workspace(const fd_score* m, int B, bool train);
 // any backbone, eval mode (sampler loop, fd_score_forward)
 int fd_score_forward_any(fd_score* m, const float* x, const float* t, float* out, int B, int mode, hipStream_t s);
-// fd_sampler.hip: the scaffolding of the step-by-step engine loops (sampler, predictor-corrector, ODE, impute, likelihood)
-// the checks every loop entry point opens with: model, SDE kind, B > 0, mode, fd_score_prepare done (who: its name in the messages)
-int fd_loop_check(fd_score* m, const fd_sde_params* sde, int B, int mode, const char* who);
-// forward scratch of one step-by-step score evaluation (fd_score_forward_any), at the arena base
-size_t fd_loop_fwd_workspace(const fd_score* m, int B);
-// reserves fwd + own (+ the t vectors of every step) in the arena; returns the t vector of step 0 at ws + fwd + own and the stride
-// between steps, 0 when one vector is refilled every step with fd_fill (FDIFF_SAMPLER_FILL_PER_STEP, or n_steps * B beyond 16 Mi)
-int fd_step_table(fd_ctx* ctx, size_t fwd, size_t own, const float* timesteps, int n_steps, int B, hipStream_t s, float** tvec,
-                  size_t* stride);
-void fd_fill(float* p, int n, float v, hipStream_t s);      // p[0 .. n) = v
+// (the scaffolding of the step-by-step engine loops: fd_loop.h)
 // fd_train_bf16.hip: bf16 MFMA training path (forward with dropout, backward)
 bool fd_train_bf16_supported(const fd_score* m);
 bool fd_score_train_dsm_bf16_supported(const fd_score* m, int B);

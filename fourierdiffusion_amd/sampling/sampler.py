@@ -100,7 +100,6 @@ class DiffusionSampler:
         self.score_model.eval()
         N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
         ctx, h, p, G, mode = self._engine_args()
-        dev = self.score_model.device
         all_samples: List[torch.Tensor] = []
         injected = not (prior_noise is None and step_noise is None and corrector_noise is None)
         sizes = self._batches(num_samples, mode, injected, pair=pair)
@@ -108,27 +107,18 @@ class DiffusionSampler:
         lo = 0
         for b, bs in enumerate(sizes):
             X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
+            z = None if step_noise is None else self._noise(step_noise[b], (N, bs), "step_noise")
+            key, off = (0, 0) if z is not None else _rng.stream()
             if guided:
-                z = None if step_noise is None else self._noise(step_noise[b], (N, bs), "step_noise")
-                key, off = (0, 0) if z is not None else _rng.stream()
                 yb = None if labels is None else labels[lo:lo + bs].contiguous()
                 lo += bs
-                Xs = self._cfg_state(X, pair)
-                rc = _C.lib().fd_sampler_run_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, Xs.data_ptr(), _C.ptr(yb),
-                                                 float(cfg_scale), _C.ptr(z), key, off, bs, mode, _C.stream_of(Xs))
-                _C.check(rc, ctx)
-                all_samples.append(Xs[:bs])
-                continue
-            z = None
-            if step_noise is not None:
-                z = _C.dev_f32(step_noise[b].to(dev), "step_noise")
-                assert tuple(z.shape) == (N, bs, self.max_len, self.n_channels)
-            key, off = (0, 0) if z is not None else _rng.stream()
-            if self.corrector_steps > 0:
+                X = self._cfg_state(X, pair)      # (the state buffer is all a guided launch differs in, besides its entry point)
+                rc = _C.lib().fd_sampler_run_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), _C.ptr(yb),
+                                                 float(cfg_scale), _C.ptr(z), key, off, bs, mode, _C.stream_of(X))
+            elif self.corrector_steps > 0:
                 zc = None
                 if corrector_noise is not None:
-                    zc = _C.dev_f32(corrector_noise[b].to(dev), "corrector_noise")
-                    assert tuple(zc.shape) == (N, self.corrector_steps, bs, self.max_len, self.n_channels)
+                    zc = self._noise(corrector_noise[b], (N, self.corrector_steps, bs), "corrector_noise")
                 if zc is None and z is not None:
                     key, off = _rng.stream()
                 rc = _C.lib().fd_sampler_run_pc(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), _C.ptr(z), _C.ptr(zc),
@@ -137,7 +127,7 @@ class DiffusionSampler:
                 rc = _C.lib().fd_sampler_run(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), _C.ptr(z),
                                              key, off, bs, mode, _C.stream_of(X))
             _C.check(rc, ctx)
-            all_samples.append(X)
+            all_samples.append(X[:bs])
         return torch.cat([x.cpu() for x in all_samples], dim=0)
 
     # ------------------------------------------------------------ probability-flow ODE (extension, not in the reference)
@@ -165,12 +155,9 @@ class DiffusionSampler:
         lo = 0
         for b, bs in enumerate(sizes):
             X = self.sample_prior(bs, noise=None if prior_noise is None else prior_noise[b])
-            if guided:
-                yb = None if labels is None else labels[lo:lo + bs].contiguous()
-                lo += bs
-                out.append(self._run_ode_cfg(self._cfg_state(X, pair), grid, solver, yb, float(cfg_scale), bs))
-            else:
-                out.append(self._run_ode(X, grid, solver))
+            yb = None if labels is None else labels[lo:lo + bs].contiguous()
+            lo += bs
+            out.append(self._run_ode(self._cfg_state(X, pair), grid, solver, yb, float(cfg_scale), pair))
         return torch.cat([x.cpu() for x in out], dim=0)
 
     # ------------------------------------------------------------ classifier-free guidance (extension, not in the reference)
@@ -203,16 +190,6 @@ class DiffusionSampler:
         Xs = torch.empty((2 * X.shape[0],) + tuple(X.shape[1:]), device=X.device, dtype=X.dtype)
         Xs[:X.shape[0]].copy_(X)
         return Xs
-
-    def _run_ode_cfg(self, Xs: torch.Tensor, grid, solver: str, yb: Optional[torch.Tensor], w: float, bs: int) -> torch.Tensor:
-        self.score_model.eval()
-        ctx, h, p, G, mode = self._engine_args()
-        ts_arr, N = grid
-        sid = self._DPM_SOLVERS[solver] if solver in self._DPM_SOLVERS else self._SOLVERS[solver]
-        rc = _C.lib().fd_sampler_run_ode_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, Xs.data_ptr(), _C.ptr(yb), w, bs, mode,
-                                             _C.stream_of(Xs))
-        _C.check(rc, ctx)
-        return Xs[:bs]
 
     def encode(self, X: torch.Tensor, num_diffusion_steps: int, solver: str = "heun", schedule: str = "time") -> torch.Tensor:
         """Latents of X (n, max_len, n_channels) in sample space: the probability-flow ODE from t = eps to t = 1 by Euler or Heun
@@ -274,19 +251,26 @@ class DiffusionSampler:
             out.append(self._run_ode(xb, grid, solver))
         return torch.cat([x.cpu() for x in out], dim=0)
 
-    def _run_ode(self, X: torch.Tensor, grid, solver: str) -> torch.Tensor:
-        """X (bs,T,C) device float32, integrated in place over ``grid`` (ctypes float[N+1], N)."""
+    def _run_ode(self, X: torch.Tensor, grid, solver: str, yb: Optional[torch.Tensor] = None, w: float = 1.0,
+                 pair: bool = False) -> torch.Tensor:
+        """X device float32, integrated in place over ``grid`` (ctypes float[N+1], N): (bs,T,C), or the (2 bs,T,C) state of a
+        guided loop in its two-evaluation form (``pair``; ``_cfg_state``).  Labels yb or a scale w != 1 (``_guided``): the guided
+        entry point.  Returns the bs integrated rows."""
         self._check_solver(solver, dpm=True)
         self.score_model.eval()
         ctx, h, p, G, mode = self._engine_args()
         ts_arr, N = grid
-        if solver in self._DPM_SOLVERS:
-            run, sid = _C.lib().fd_sampler_run_dpm, self._DPM_SOLVERS[solver]
+        bs = X.shape[0] // 2 if pair else X.shape[0]
+        dpm = solver in self._DPM_SOLVERS
+        sid = self._DPM_SOLVERS[solver] if dpm else self._SOLVERS[solver]
+        if yb is not None or w != 1.0:
+            rc = _C.lib().fd_sampler_run_ode_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), _C.ptr(yb), w, bs, mode,
+                                                 _C.stream_of(X))
         else:
-            run, sid = _C.lib().fd_sampler_run_ode, self._SOLVERS[solver]
-        rc = run(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), X.shape[0], mode, _C.stream_of(X))
+            run = _C.lib().fd_sampler_run_dpm if dpm else _C.lib().fd_sampler_run_ode
+            rc = run(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), bs, mode, _C.stream_of(X))
         _C.check(rc, ctx)
-        return X
+        return X[:bs]
 
     # ------------------------------------------------------------ likelihood (extension, not in the reference)
     _LL_SOLVERS = {"euler": 0, "heun": 1, "rk45": 2}
