@@ -6,7 +6,8 @@ split's shape) next to the checkpoint, with the MSE / MAE over the hidden entrie
 num_samples_per_series=K > 1 draws an ensemble of K samples per series instead: imputations.pt is (n, K, T, C) and results.yaml
 holds the ensemble scores of sampling/forecast.py (CRPS, quantile CRPS and CRPS-sum, median errors, 90 % interval coverage) in
 place of the MSE / MAE.  conditioning=dps (guidance.scale, guidance.jacobian) replaces the projection by gradient guidance; the three
-keys are then recorded in the `impute` block.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+keys are then recorded in the `impute` block.  labels=data|<int> (class-conditional models) conditions every series on its test label
+(`datamodule.y_test`) or on one class, cfg_scale=w sets the classifier-free guidance scale; both are recorded only when set.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -24,6 +25,7 @@ from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_ya
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
 from fourierdiffusion_amd.sampling.forecast import ensemble_scores  # noqa: E402
 from fourierdiffusion_amd.sampling.masks import observation_mask  # noqa: E402
+from fourierdiffusion_amd.sampling.sampler import series_labels  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
 
@@ -86,6 +88,8 @@ class ImputationRunner:
         guidance = cfg.get("guidance", None) or {}
         self.guidance_scale = float(guidance.get("scale", 1.0))
         self.guidance_jacobian = bool(guidance.get("jacobian", True))
+        self.labels = cfg.get("labels", None)
+        self.cfg_scale = float(cfg.get("cfg_scale", 1.0))
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
         self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path,
@@ -106,6 +110,8 @@ class ImputationRunner:
                                 horizon=int(self.mask_cfg.get("horizon", 1)), generator=gen)
         observed = truth.masked_fill(~mask, float("nan"))                          # the sampler never sees a hidden entry
         lo, hi = shard_range(int(truth.shape[0]), self.dist.rank, self.dist.world)  # independent rows: no exchange
+        y = series_labels(self.labels, self.datamodule, int(truth.shape[0]), int(getattr(self.score_model, "n_classes", 0)))
+        guided = {} if (y is None and self.cfg_scale == 1.0) else dict(y=None if y is None else y[lo:hi], cfg_scale=self.cfg_scale)
         mean = std = None
         if self.datamodule.standardize:
             mean, std = self.datamodule.feature_mean_and_std
@@ -114,7 +120,7 @@ class ImputationRunner:
             X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
                                     feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K,
                                     conditioning=self.conditioning, guidance_scale=self.guidance_scale,
-                                    guidance_jacobian=self.guidance_jacobian)
+                                    guidance_jacobian=self.guidance_jacobian, **guided)
             shape = X.shape
             X = X.reshape(-1, *shape[-2:])                                          # (rows, T, C) for the maps back
             if std is not None:
@@ -136,6 +142,8 @@ class ImputationRunner:
             if self.conditioning != "replace":
                 results["impute"].update(conditioning=self.conditioning, guidance_scale=self.guidance_scale,
                                          guidance_jacobian=self.guidance_jacobian)
+            if guided:
+                results["impute"].update(labels=None if y is None else str(self.labels), cfg_scale=self.cfg_scale)
             logging.info(f"Saving imputations and errors to {self.save_dir}.\n{dict_to_str(results['impute'])}")
             yaml.dump(data=results, stream=open(results_path, "w"))
             torch.save(X, self.save_dir / "imputations.pt")

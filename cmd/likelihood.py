@@ -5,7 +5,8 @@ a Hutchinson or exact divergence, on the MI355X engine), mapped to the series as
 scale), so that a time-domain and a frequency-domain model are compared on one number.  Writes the key `likelihood` of
 results.yaml: mean and standard error over series of the data-space NLL, bits per dimension, the sample-space NLL and the
 settings; solver=rk45 (adaptive, rtol / atol) adds nfe_mean, nfe_max and n_not_converged and takes the NLL over the converged
-series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/impute.py does."""
+series.  labels=data|<int> (class-conditional models) evaluates log p(x | y) on the test labels (`datamodule.y_test`) or one class,
+recorded only when set.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/impute.py does."""
 from __future__ import annotations
 
 import logging
@@ -23,6 +24,7 @@ from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
 from fourierdiffusion_amd.sampling.likelihood import bits_per_dim, to_data_space  # noqa: E402
+from fourierdiffusion_amd.sampling.sampler import series_labels  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import dft  # noqa: E402
 
@@ -76,12 +78,13 @@ class LikelihoodRunner:
             mean, std = self.datamodule.feature_mean_and_std
             Xs = (Xs - mean.to(dev)) / std.to(dev)
         lo, hi = shard_range(int(X.shape[0]), self.dist.rank, self.dist.world)     # independent rows: no exchange
+        y = series_labels(cfg.get("labels", None), self.datamodule, int(X.shape[0]), int(getattr(self.score_model, "n_classes", 0)))
         adaptive = str(cfg.solver) == "rk45"
         kw = dict(rtol=float(cfg.rtol), atol=float(cfg.atol), max_evals=int(cfg.max_evals)) if adaptive else {}
         lp, nfe = torch.empty(0, dtype=torch.float64), torch.empty(0, dtype=torch.int64)
         if hi > lo:
             res = self.sampler.log_likelihood(Xs[lo:hi], int(cfg.num_diffusion_steps), str(cfg.solver), estimator=str(cfg.estimator),
-                                              n_probes=int(cfg.n_probes), **kw)
+                                              n_probes=int(cfg.n_probes), **kw, **({} if y is None else dict(y=y[lo:hi])))
             lp, nfe = res.log_prob, res.nfe
         if self.dist.world > 1:
             import torch.distributed as dist
@@ -108,6 +111,8 @@ class LikelihoodRunner:
                    "fourier_transform": bool(self.fourier_transform), "precision": self.score_model.precision_effective}
             if adaptive:
                 out.update(extra)
+            if y is not None:
+                out["labels"] = str(cfg.labels)
             results_path = self.save_dir / "results.yaml"
             results = yaml.safe_load(open(results_path)) if results_path.exists() else None
             results = results if isinstance(results, dict) else {}

@@ -84,6 +84,7 @@ _PROTOS = {
     "fd_score_layout_cond": (C.c_int, [C.POINTER(ModelDims), C.c_int, C.POINTER(ParamEntry), C.POINTER(C.c_int)]),
     "fd_score_create_cond": (C.c_int, [_vp, C.POINTER(ModelDims), C.c_int, C.POINTER(_vp)]),
     "fd_score_set_labels": (C.c_int, [_vp, _vp, C.c_int]),
+    "fd_score_get_labels": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
     "fd_score_set_label_dropout": (C.c_int, [_vp, C.c_float]),
     "fd_label_dropout": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _vp]),
     "fd_score_prepare": (C.c_int, [_vp, _vp, _vp]),
@@ -111,11 +112,19 @@ _PROTOS = {
                                         C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_impute_rep": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                             _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_impute_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                            _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp,
+                                            C.c_float, _vp]),
     "fd_impute_guidance": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp,
                                      _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_impute_dps": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                             _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                             _vp]),
+    "fd_impute_guidance_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int,
+                                         _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_float, _vp]),
+    "fd_sampler_run_impute_dps_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                                _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
+                                                C.c_int, _vp, C.c_float, _vp]),
     "fd_pf_ode_drift": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_dpm": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),

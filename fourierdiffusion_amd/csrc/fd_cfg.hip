@@ -108,21 +108,11 @@ __global__ __launch_bounds__(kBlock) void k_cfg_sde_step(const float* __restrict
     }
 }
 
-// What a guided loop runs: pair = two evaluations per step as one forward on 2B rows; else one evaluation on B rows with y bound
-// (or null = the null token on every row)
-fd_guide cfg_plan(const int* y, float w) {
-    // FDIFF_CFG_FORCE_PAIR (tests): the two-evaluation form also at w = 1 and w = 0, where the combine is exact
-    const bool pair = y && ((w != 1.f && w != 0.f) || getenv("FDIFF_CFG_FORCE_PAIR"));
-    return fd_guide{pair, (pair || w != 0.f) ? y : nullptr, w, (float)(1.0 - (double)w)};
-}
-
 int cfg_check(fd_score* m, const void* G, const void* timesteps, const void* x, int n_steps, float w, const char* who) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, G && timesteps && x, "%s: null pointer", who);
     FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
-    FD_REQUIRE(ctx, m->n_classes > 0, "%s: the model has no class table (fd_score_create_cond with n_classes > 0)", who);
-    FD_REQUIRE(ctx, std::isfinite(w), "%s: the guidance scale is not finite", who);
-    return FD_OK;
+    return fd_guide_check(m, w, who);
 }
 
 }  // namespace
@@ -182,6 +172,13 @@ extern "C" int fd_score_set_labels(fd_score* m, const int32_t* y, int B) {
     return FD_OK;
 }
 
+extern "C" int fd_score_get_labels(fd_score* m, const int32_t** y, int* B) {
+    if (!m || !y || !B) return FD_ERR_ARG;
+    *y = m->labels;
+    *B = m->labels_B;
+    return FD_OK;
+}
+
 extern "C" int fd_score_set_label_dropout(fd_score* m, float p) {
     if (!m) return FD_ERR_ARG;
     fd_ctx* ctx = m->ctx;
@@ -203,6 +200,19 @@ extern "C" int fd_label_dropout(fd_ctx* ctx, const int32_t* y, int32_t* y_out, i
 }
 
 // ------------------------------------------------------------------ guided loops
+fd_guide fd_guide_plan(const int* y, float w) {
+    // FDIFF_CFG_FORCE_PAIR (tests): the two-evaluation form also at w = 1 and w = 0, where the combine is exact
+    const bool pair = y && ((w != 1.f && w != 0.f) || getenv("FDIFF_CFG_FORCE_PAIR"));
+    return fd_guide{pair, (pair || w != 0.f) ? y : nullptr, w, (float)(1.0 - (double)w)};
+}
+
+int fd_guide_check(fd_score* m, float w, const char* who) {
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, m->n_classes > 0, "%s: the model has no class table (fd_score_create_cond with n_classes > 0)", who);
+    FD_REQUIRE(ctx, std::isfinite(w), "%s: the guidance scale is not finite", who);
+    return FD_OK;
+}
+
 int fd_guide_begin(fd_score* m, const fd_guide* g, int* lab, float* x, int B, hipStream_t s) {
     if (!g || !g->pair) return FD_OK;
     const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
@@ -231,7 +241,7 @@ extern "C" int fd_sampler_run_cfg(fd_score* m, const fd_sde_params* sde, const f
     fd_ctx* ctx = m->ctx;
     if (int rc = cfg_check(m, G, timesteps, x, n_steps, w, "fd_sampler_run_cfg")) return rc;
     FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_cfg: step size must be > 0 (sde.py:158)");
-    const fd_guide g = cfg_plan(y, w);
+    const fd_guide g = fd_guide_plan(y, w);
     return fd_sampler_sde_loop(m, sde, G, timesteps, n_steps, dt, x, z_steps, seed, offset, B, mode, (hipStream_t)stream, &g);
 }
 
@@ -242,6 +252,6 @@ extern "C" int fd_sampler_run_ode_cfg(fd_score* m, const fd_sde_params* sde, con
     fd_ctx* ctx = m->ctx;
     if (int rc = cfg_check(m, G, timesteps, x, n_steps, w, "fd_sampler_run_ode_cfg")) return rc;
     FD_REQUIRE(ctx, solver >= 0 && solver <= 3, "fd_sampler_run_ode_cfg: solver %d (0 Euler, 1 Heun, 2 DDIM, 3 DPM-Solver++ 2M)", solver);
-    const fd_guide g = cfg_plan(y, w);
+    const fd_guide g = fd_guide_plan(y, w);
     return fd_sampler_ode_loop(m, sde, G, timesteps, n_steps, solver, x, B, mode, (hipStream_t)stream, &g);
 }

@@ -19,6 +19,14 @@
 // (no atomics).  k_dps_step: elementwise over k_sde_step's Philox groups; a row's ||r||^2 is the sum of its blocks in order, so
 // runs are bit-identical.  Every stage buffer lives in ctx->ll_buf, outside the arena that holds the training forward's saved
 // activations.
+//
+// Classifier-free guidance (fd_guide, fd_loop.h; the _cfg entry points): the score above is s = w s_c + (1 - w) s_u, the halves of ONE
+// forward on 2B rows with the labels [y ; null], and its Jacobian is J = w J_c + (1 - w) J_u, so
+//   dx = J^T v = w J_c^T v + (1 - w) J_u^T v,   v = s^2 G^2 u
+// is ONE input VJP on 2B rows whose input is (w v ; (1 - w) v) -- the network treats its rows independently, so the conditional half
+// of the VJP's output is J_c^T (w v) and the null half J_u^T ((1 - w) v) -- and the step kernel adds the two halves, conditional
+// first.  k_dps_residual<.., PAIR> forms the guided score, writes u for B rows and the VJP input for 2B; k_dps_step<.., PAIR> steps
+// with the guided score over the Philox groups of n = B T C and writes both halves of the state.
 #include <algorithm>
 #include <cmath>
 
@@ -50,12 +58,37 @@ struct ResArgs {
     int T, C, Tp, ncb, mask_per_series, obs_rep;
     float alpha, s2;
 };
+// PAIR: x and score are (2B,T,C), dout too (w v in the conditional half, (1 - w) v in the null half); u and part stay B rows
+struct ResArgsPair : ResArgs {
+    size_t half;             // B T C: where the null half starts
+    float w, omw;            // the guidance scale and 1 - w
+};
+template <bool PAIR>
+struct ResArgsOf { typedef ResArgs type; };
+template <>
+struct ResArgsOf<true> { typedef ResArgsPair type; };
 
 __device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k == T)) ? 1.0f : 2.0f; }
 __device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB + c) * 4 + (k & 3); }
 
-template <bool FOURIER>
-__global__ __launch_bounds__(kThreads) void k_dps_residual(ResArgs a) {
+// the score Tweedie's estimate reads at element e, and the VJP input s^2 G^2 u of element e
+template <bool PAIR, class Args>
+__device__ __forceinline__ float res_score(const Args& a, size_t e) {
+    if constexpr (PAIR) return fd_guided(a.score[e], a.score[a.half + e], a.w, a.omw);
+    else return a.score[e];
+}
+template <bool PAIR, class Args>
+__device__ __forceinline__ void res_dout(const Args& a, size_t e, float v) {
+    if constexpr (PAIR) {
+        a.dout[e] = __fmul_rn(a.w, v);
+        a.dout[a.half + e] = __fmul_rn(a.omw, v);
+    } else {
+        a.dout[e] = v;
+    }
+}
+
+template <bool FOURIER, bool PAIR = false>
+__global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PAIR>::type a) {
     extern __shared__ float lds[];
     __shared__ double red[kThreads];
     const int tid = threadIdx.x;
@@ -72,12 +105,12 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(ResArgs a) {
             const size_t tc = (size_t)t * C + c, e = base + tc;
             const float Gt = a.G[t], sg2 = a.s2 * (Gt * Gt);
             const float sd = a.stdv ? a.stdv[tc] : 1.0f;
-            const float x0h = (a.x[e] + sg2 * a.score[e]) / a.alpha;
+            const float x0h = (a.x[e] + sg2 * res_score<PAIR>(a, e)) / a.alpha;
             const float r = mrow[tc] ? sd * (a.x0[obase + tc] - x0h) : 0.f;
             rr += (double)r * (double)r;
             const float uv = sd * r;
             a.u[e] = uv;
-            if (a.dout) a.dout[e] = sg2 * uv;
+            if (a.dout) res_dout<PAIR>(a, e, sg2 * uv);
         }
     } else {
         float* U = lds;                            // sigma (x0_obs - x0_hat) / rho, frequency rows
@@ -91,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(ResArgs a) {
             const size_t kc = (size_t)k * C + c, e = base + kc;
             const float Gk = a.G[k];
             const float sd = a.stdv ? a.stdv[kc] : 1.0f;
-            const float x0h = (a.x[e] + a.s2 * (Gk * Gk) * a.score[e]) / a.alpha;
+            const float x0h = (a.x[e] + a.s2 * (Gk * Gk) * res_score<PAIR>(a, e)) / a.alpha;
             U[quad_idx(k, cl)] = sd * (a.x0[obase + kc] - x0h) * inv_r(k, T);
         }
         __syncthreads();
@@ -150,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(ResArgs a) {
                 a.u[e] = uv;
                 if (a.dout) {
                     const float Gk = a.G[k];
-                    a.dout[e] = a.s2 * (Gk * Gk) * uv;
+                    res_dout<PAIR>(a, e, a.s2 * (Gk * Gk) * uv);
                 }
             }
         }
@@ -183,11 +216,20 @@ struct StepArgs {
     double zeta;
     uint64_t seed, offset;
 };
+// PAIR: x, score and dx are (2B,T,C), n = B T C the size of one half; u, part, gout and rn2_out stay B rows
+struct StepArgsPair : StepArgs {
+    float w, omw;
+};
+template <bool PAIR>
+struct StepArgsOf { typedef StepArgs type; };
+template <>
+struct StepArgsOf<true> { typedef StepArgsPair type; };
 
 // STEP: x' = fd_sde_apply(x, score, z) + (zeta / ||r||) g over the Philox groups of k_sde_step (group q = elements 4q .. 4q+3 of the
-// whole (B,T,C) tensor, drawn at offset + q).  GRAD: g and ||r||^2 alone.
-template <bool GRAD>
-__global__ __launch_bounds__(kStepBlock) void k_dps_step(StepArgs a) {
+// whole (B,T,C) tensor, drawn at offset + q).  GRAD: g and ||r||^2 alone.  PAIR: the guided score, dx = the conditional half of the
+// VJP plus the null half, and the new state to both halves; groups and counters those of the unpaired launch over n = B T C.
+template <bool GRAD, bool PAIR = false>
+__global__ __launch_bounds__(kStepBlock) void k_dps_step(typename StepArgsOf<PAIR>::type a) {
     const size_t ngroups = (a.n + 3) / 4;
     for (size_t q = blockIdx.x * (size_t)kStepBlock + threadIdx.x; q < ngroups; q += (size_t)gridDim.x * kStepBlock) {
         float z[4] = {0.f, 0.f, 0.f, 0.f};
@@ -207,34 +249,46 @@ __global__ __launch_bounds__(kStepBlock) void k_dps_step(StepArgs a) {
             const size_t b = e / a.TC, loc = e - b * a.TC;
             double rn2 = 0.0;
             for (int k = 0; k < a.ncb; ++k) rn2 += a.part[b * a.ncb + k];
-            const float gv = (2.0f / a.alpha) * (a.u[e] + (a.dx ? a.dx[e] : 0.f));
+            float dxe = a.dx ? a.dx[e] : 0.f;
+            if constexpr (PAIR)
+                if (a.dx) dxe = __fadd_rn(dxe, a.dx[a.n + e]);
+            const float gv = (2.0f / a.alpha) * (a.u[e] + dxe);
             if (GRAD) {
                 a.gout[e] = gv;
                 if (loc == 0) a.rn2_out[b] = rn2;
             } else {
                 const int t = (int)(loc / a.C);
-                float xv = fd_sde_apply(a.x[e], a.score[e], z[j], a.G[t], a.cf);
+                float sc = a.score[e];
+                if constexpr (PAIR) sc = fd_guided(sc, a.score[a.n + e], a.w, a.omw);
+                float xv = fd_sde_apply(a.x[e], sc, z[j], a.G[t], a.cf);
                 const float coef = rn2 > 0.0 ? (float)(a.zeta / sqrt(rn2)) : 0.f;
                 if (coef != 0.f) xv += coef * gv;
                 a.x[e] = xv;
+                if constexpr (PAIR) a.x[a.n + e] = xv;
             }
         }
     }
 }
 
-// the stage buffers of one run (fd_ll_carve: outside the arena)
+// the stage buffers of one run (fd_ll_carve: outside the arena).  R: the rows of a forward (B, or 2B for a paired guide, whose label
+// vector lab and -- fd_impute_guidance_cfg, whose x is the caller's -- state copy xpair follow the unpaired layout)
 struct DpsBufs {
     float *tvec, *score, *u, *dout, *dx;
     double* part;
+    int* lab;
+    float* xpair;
 };
-int dps_buffers(fd_ctx* ctx, int B, size_t n, int ncb, bool jac, DpsBufs* o) {
+int dps_buffers(fd_ctx* ctx, int B, int R, size_t n, int ncb, bool jac, bool xpair, DpsBufs* o) {
+    const size_t nR = n / B * R;
     return fd_ll_carve(ctx, [&](auto take) {
-        o->tvec = (float*)take(B * sizeof(float));
-        o->score = (float*)take(n * sizeof(float));
+        o->tvec = (float*)take(R * sizeof(float));
+        o->score = (float*)take(nR * sizeof(float));
         o->u = (float*)take(n * sizeof(float));
-        o->dout = jac ? (float*)take(n * sizeof(float)) : nullptr;
-        o->dx = jac ? (float*)take(n * sizeof(float)) : nullptr;
+        o->dout = jac ? (float*)take(nR * sizeof(float)) : nullptr;
+        o->dx = jac ? (float*)take(nR * sizeof(float)) : nullptr;
         o->part = (double*)take((size_t)B * ncb * sizeof(double));
+        o->lab = R != B ? (int*)take((size_t)R * sizeof(int)) : nullptr;
+        o->xpair = xpair ? (float*)take(nR * sizeof(float)) : nullptr;
     });
 }
 
@@ -262,96 +316,119 @@ int dps_prepare(fd_score* m, ResArgs& r, const float* G, const float* x, const f
     return FD_OK;
 }
 
-template <bool FOURIER>
-int launch_residual(fd_ctx* ctx, const ResArgs& r, int B, hipStream_t s) {
+template <bool FOURIER, bool PAIR>
+int launch_residual(fd_ctx* ctx, const typename ResArgsOf<PAIR>::type& r, int B, hipStream_t s) {
     static unsigned long long attr_set = 0;
     const size_t lds = FOURIER ? (size_t)2 * r.Tp * kCB * sizeof(float) : 0;
     if (FOURIER && fd_first_on_device(attr_set, ctx->device))
-        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_dps_residual<FOURIER>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    hipLaunchKernelGGL((k_dps_residual<FOURIER>), dim3((unsigned)(B * r.ncb)), dim3(kThreads), lds, s, r);
+        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_dps_residual<FOURIER, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        128 * 1024));
+    hipLaunchKernelGGL((k_dps_residual<FOURIER, PAIR>), dim3((unsigned)(B * r.ncb)), dim3(kThreads), lds, s, r);
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
 }
 
+// the step (or, GRAD, the gradient) over the B rows of a.n; g: a paired guide, or null
 template <bool GRAD>
-int launch_step(fd_ctx* ctx, const StepArgs& a, hipStream_t s) {
+int launch_step(fd_ctx* ctx, const StepArgs& a, const fd_guide* g, hipStream_t s) {
     const size_t ngroups = (a.n + 3) / 4;
     const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((ngroups + kStepBlock - 1) / kStepBlock,
                                                                          (size_t)ctx->num_cu * 16));
-    hipLaunchKernelGGL((k_dps_step<GRAD>), dim3(grid), dim3(kStepBlock), 0, s, a);
+    if (g) {
+        StepArgsPair ap{};
+        static_cast<StepArgs&>(ap) = a;
+        ap.w = g->w;
+        ap.omw = g->omw;
+        hipLaunchKernelGGL((k_dps_step<GRAD, true>), dim3(grid), dim3(kStepBlock), 0, s, ap);
+    } else {
+        hipLaunchKernelGGL((k_dps_step<GRAD, false>), dim3(grid), dim3(kStepBlock), 0, s, a);
+    }
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
 }
 
-// One guidance evaluation at (x, tvec): the score (training forward with the Jacobian, else the sampler's forward), the residual,
-// and the VJP; leaves score, u, dx and the block sums in the buffers
-int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, bool jac, bool fourier, int mode, hipStream_t s) {
+// One guidance evaluation at (x, tvec) on R network rows (B, or 2B under a paired guide g): the score (training forward with the
+// Jacobian, else the sampler's forward), the residual of the B state rows, and the VJP; leaves score, u, dx and the block sums in
+// the buffers
+int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, int R, const fd_guide* g, bool jac, bool fourier,
+             int mode, hipStream_t s) {
     fd_ctx* ctx = m->ctx;
     if (jac) {
-        if (int rc = fd_score_forward_train(m, x, bf.tvec, bf.score, B, 0.f, 0, 0, s)) return rc;
+        if (int rc = fd_score_forward_train(m, x, bf.tvec, bf.score, R, 0.f, 0, 0, s)) return rc;
     } else {
-        if (int rc = fd_score_forward_any(m, x, bf.tvec, bf.score, B, mode, s)) return rc;
+        if (int rc = fd_score_forward_any(m, x, bf.tvec, bf.score, R, mode, s)) return rc;
     }
     r.x = x;
     r.score = bf.score;
-    if (int rc = fourier ? launch_residual<true>(ctx, r, B, s) : launch_residual<false>(ctx, r, B, s)) return rc;
+    if (g) {
+        ResArgsPair rp{};
+        static_cast<ResArgs&>(rp) = r;
+        rp.half = (size_t)B * r.T * r.C;
+        rp.w = g->w;
+        rp.omw = g->omw;
+        if (int rc = fourier ? launch_residual<true, true>(ctx, rp, B, s) : launch_residual<false, true>(ctx, rp, B, s)) return rc;
+    } else {
+        if (int rc = fourier ? launch_residual<true, false>(ctx, r, B, s) : launch_residual<false, false>(ctx, r, B, s)) return rc;
+    }
     if (jac)
         if (int rc = fd_score_input_vjp(m, bf.dout, bf.dx, s)) return rc;
     return FD_OK;
 }
 
-}  // namespace
-
-extern "C" int fd_impute_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
-                                  const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian,
-                                  float* g_out, double* rnorm2_out, int B, int obs_replicas, int mode, void* stream) {
-    if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance")) return rc;
+// the body of fd_impute_guidance (g == null) and fd_impute_guidance_cfg, the arguments checked under the name `who`
+int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                 const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian, float* g_out,
+                 double* rnorm2_out, int B, int obs_replicas, int mode, hipStream_t s, const fd_guide* g, const char* who) {
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, g_out && rnorm2_out, "fd_impute_guidance: null pointer");
-    FD_REQUIRE(ctx, std::isfinite(t) && t > 0.f, "fd_impute_guidance: t=%g must be finite and > 0", (double)t);
-    hipStream_t s = (hipStream_t)stream;
+    FD_REQUIRE(ctx, g_out && rnorm2_out, "%s: null pointer", who);
+    FD_REQUIRE(ctx, std::isfinite(t) && t > 0.f, "%s: t=%g must be finite and > 0", who, (double)t);
     ResArgs r{};
-    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, "fd_impute_guidance"))
-        return rc;
-    const bool jac = jacobian != 0;
+    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
+    const bool jac = jacobian != 0, pair = g && g->pair;
     const size_t n = (size_t)B * r.T * r.C;
+    const int R = fd_guide_rows(g, B);
     DpsBufs bf;
-    if (int rc = dps_buffers(ctx, B, n, r.ncb, jac, &bf)) return rc;
+    if (int rc = dps_buffers(ctx, B, R, n, r.ncb, jac, pair, &bf)) return rc;
     double al = 1.0, sd = 0.0;
     fd_marginal_coef(*sde, (double)t, &al, &sd);
     r.alpha = (float)al;
     r.s2 = (float)(sd * sd);
     r.u = bf.u; r.dout = bf.dout; r.part = bf.part;
+    if (pair) {      // the state twice, behind the caller's x
+        FD_HIP(ctx, hipMemcpyAsync(bf.xpair, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (int rc = fd_guide_begin(m, g, bf.lab, bf.xpair, B, s)) return rc;
+        x = bf.xpair;
+    }
+    fd_guide_scope scope(m, g, bf.lab, R);
     fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
-    fd_fill(bf.tvec, B, t, s);
-    if (int rc = dps_eval(m, r, bf, x, B, jac, fourier != 0, mode, s)) return rc;
+    fd_label_dropout_scope ld(m, 0.f);
+    fd_fill(bf.tvec, R, t, s);
+    if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s)) return rc;
     StepArgs a{};
     a.G = G; a.u = bf.u; a.dx = bf.dx; a.part = bf.part; a.gout = g_out; a.rn2_out = rnorm2_out;
     a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
     a.alpha = r.alpha;
-    return launch_step<true>(ctx, a, s);
+    return launch_step<true>(ctx, a, pair ? g : nullptr, s);
 }
 
-extern "C" int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
-                                         float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
-                                         const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
-                                         uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode, void* stream) {
-    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_dps")) return rc;
+// the body of fd_sampler_run_impute_dps (g == null) and fd_sampler_run_impute_dps_cfg; a paired guide runs on x (2B,T,C)
+int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
+             const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
+             float guidance_scale, int jacobian, const float* z_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
+             hipStream_t s, const fd_guide* g, const char* who) {
     fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, timesteps, "fd_sampler_run_impute_dps: null pointer");
-    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_impute_dps: n_steps=%d", n_steps);
-    FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_impute_dps: step size must be > 0 (sde.py:158)");
-    FD_REQUIRE(ctx, std::isfinite(guidance_scale) && guidance_scale >= 0.f,
-               "fd_sampler_run_impute_dps: guidance_scale=%g must be finite and >= 0", (double)guidance_scale);
-    hipStream_t s = (hipStream_t)stream;
+    FD_REQUIRE(ctx, timesteps, "%s: null pointer", who);
+    FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
+    FD_REQUIRE(ctx, dt > 0.f, "%s: step size must be > 0 (sde.py:158)", who);
+    FD_REQUIRE(ctx, std::isfinite(guidance_scale) && guidance_scale >= 0.f, "%s: guidance_scale=%g must be finite and >= 0", who,
+               (double)guidance_scale);
     ResArgs r{};
-    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s,
-                             "fd_sampler_run_impute_dps"))
-        return rc;
-    const bool jac = jacobian != 0;
+    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
+    const bool jac = jacobian != 0, pair = g && g->pair;
     const size_t n = (size_t)B * r.T * r.C;
+    const int R = fd_guide_rows(g, B);
     DpsBufs bf;
-    if (int rc = dps_buffers(ctx, B, n, r.ncb, jac, &bf)) return rc;
+    if (int rc = dps_buffers(ctx, B, R, n, r.ncb, jac, false, &bf)) return rc;
     r.u = bf.u; r.dout = bf.dout; r.part = bf.part;
     // per-step coefficients on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and Tweedie's (alpha, s) at t_i
     std::vector<SdeCoef> cf(n_steps);
@@ -363,7 +440,10 @@ extern "C" int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, 
         al[i] = (float)aa;
         s2[i] = (float)(ss * ss);
     }
+    if (int rc = fd_guide_begin(m, g, bf.lab, x, B, s)) return rc;
+    fd_guide_scope scope(m, g, bf.lab, R);
     fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
+    fd_label_dropout_scope ld(m, 0.f);
     StepArgs a{};
     a.G = G; a.x = x; a.score = bf.score; a.u = bf.u; a.dx = bf.dx; a.part = bf.part;
     a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
@@ -372,15 +452,62 @@ extern "C" int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, 
     // Philox: predictor noise of step i at offset + i*ceil(BTC/4) (as fd_sampler_run)
     const uint64_t per_step = (uint64_t)((n + 3) / 4);
     for (int i = 0; i < n_steps; ++i) {
-        fd_fill(bf.tvec, B, timesteps[i], s);
+        fd_fill(bf.tvec, R, timesteps[i], s);
         r.alpha = al[i];
         r.s2 = s2[i];
-        if (int rc = dps_eval(m, r, bf, x, B, jac, fourier != 0, mode, s)) return rc;
+        if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s)) return rc;
         a.zin = z_steps ? z_steps + (size_t)i * n : nullptr;
         a.cf = cf[i];
         a.alpha = al[i];
         a.offset = offset + (uint64_t)i * per_step;
-        if (int rc = launch_step<false>(ctx, a, s)) return rc;
+        if (int rc = launch_step<false>(ctx, a, pair ? g : nullptr, s)) return rc;
     }
     return FD_OK;
+}
+
+}  // namespace
+
+extern "C" int fd_impute_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                                  const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian,
+                                  float* g_out, double* rnorm2_out, int B, int obs_replicas, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance")) return rc;
+    return dps_guidance(m, sde, G, t, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, jacobian, g_out, rnorm2_out, B,
+                        obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_impute_guidance");
+}
+
+// fd_impute_guidance on a class-conditional model under classifier-free guidance: y (B) one label per row or null, w the scale;
+// g_out and rnorm2_out for the B rows.  A paired call copies x twice into its own buffers.
+extern "C" int fd_impute_guidance_cfg(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x,
+                                      const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
+                                      int fourier, int jacobian, float* g_out, double* rnorm2_out, int B, int obs_replicas, int mode,
+                                      const int32_t* y, float cfg_scale, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance_cfg")) return rc;
+    if (int rc = fd_guide_check(m, cfg_scale, "fd_impute_guidance_cfg")) return rc;
+    const fd_guide g = fd_guide_plan(y, cfg_scale);
+    return dps_guidance(m, sde, G, t, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, jacobian, g_out, rnorm2_out, B,
+                        obs_replicas, mode, (hipStream_t)stream, &g, "fd_impute_guidance_cfg");
+}
+
+extern "C" int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                         float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                         const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
+                                         uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_dps")) return rc;
+    return dps_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, guidance_scale, jacobian,
+                    z_steps, seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_dps");
+}
+
+// fd_sampler_run_impute_dps under classifier-free guidance: y (B) one label per state row or null, w the scale.  A paired call
+// (labels and w outside {0, 1}, or FDIFF_CFG_FORCE_PAIR) takes x (2B,T,C) with the state in its first half and leaves both halves
+// equal; else one evaluation per step on B rows with y bound.
+extern "C" int fd_sampler_run_impute_dps_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                             int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                             int mask_per_series, const float* feat_std, int fourier, float guidance_scale,
+                                             int jacobian, const float* z_steps, uint64_t seed, uint64_t offset, int B,
+                                             int obs_replicas, int mode, const int32_t* y, float cfg_scale, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_dps_cfg")) return rc;
+    if (int rc = fd_guide_check(m, cfg_scale, "fd_sampler_run_impute_dps_cfg")) return rc;
+    const fd_guide g = fd_guide_plan(y, cfg_scale);
+    return dps_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, guidance_scale, jacobian,
+                    z_steps, seed, offset, B, obs_replicas, mode, (hipStream_t)stream, &g, "fd_sampler_run_impute_dps_cfg");
 }

@@ -31,6 +31,15 @@ struct fd_train_mode_scope {
     ~fd_train_mode_scope() { m->train_mode = saved; }
 };
 
+// The same for label dropout: the training forwards of an evaluation loop (fd_dps.hip, fd_likelihood.hip) read the bound labels as
+// they are -- fd_labels_prepare_train draws a model's label_dropout on every training forward otherwise
+struct fd_label_dropout_scope {
+    fd_score* m;
+    float saved;
+    fd_label_dropout_scope(fd_score* mm, float p) : m(mm), saved(mm->label_dropout) { m->label_dropout = p; }
+    ~fd_label_dropout_scope() { m->label_dropout = saved; }
+};
+
 // the training arithmetic of an evaluation that differentiates the network: bf16 where the model has the bf16 training kernels
 // (the transformer at its supported widths), else exact f32
 inline int fd_diff_train_mode(const fd_score* m, int mode) {

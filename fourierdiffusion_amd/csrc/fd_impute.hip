@@ -52,6 +52,14 @@ struct ImpArgs {
     float alpha, s;
     uint64_t seed, off_step, off_obs;
 };
+// PAIR (classifier-free guidance, fd_loop.h): x, score and out are (2B,T,C), rows [B, 2B) the null-token twin of rows [0, B)
+struct ImpArgsPair : ImpArgs {
+    float w, omw;            // the guidance scale and 1 - w
+};
+template <bool PAIR>
+struct ImpArgsOf { typedef ImpArgs type; };
+template <>
+struct ImpArgsOf<true> { typedef ImpArgsPair type; };
 
 // 1 / r of packed row k: 1 at DC and Nyquist (T even), 2 at every other bin (the Hermitian pair it stands for)
 __device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k == T)) ? 1.0f : 2.0f; }
@@ -59,8 +67,11 @@ __device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k 
 // LDS image index of (k, channel) in k-quad order
 __device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB + c) * 4 + (k & 3); }
 
-template <bool STEP, bool FOURIER>
-__global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
+// PAIR: the workgroup of (b, channel block) reads x[b], steps with the guided score fd_guided(score[b], score[B + b]) and writes
+// every final value to rows b and B + b, so the two halves stay bit-equal; the Philox counters and lanes are those of the unpaired
+// launch over n = B T C (the second half draws nothing).
+template <bool STEP, bool FOURIER, bool PAIR = false>
+__global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::type a) {
     extern __shared__ float lds[];
     float* U = lds;                            // sigma d / r, frequency rows
     float* W = lds + (size_t)a.Tp * kCB;       // m . idft(sigma d), time rows
@@ -69,6 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
     const int T = a.T, C = a.C, Tp = a.Tp;
     const size_t TC = (size_t)T * C, base = (size_t)b * TC, obase = (size_t)(b / a.obs_rep) * TC;
     const uint8_t* mrow = a.mask + (a.mask_per_series ? obase : 0);
+    [[maybe_unused]] const size_t half = (size_t)a.B * TC;      // PAIR: the null half of x / score / out starts here
 
     if (FOURIER)
         for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
@@ -118,14 +130,20 @@ __global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
             const int t = loc[j] / C, c = loc[j] % C;
             const float Gt = a.G[t];
             float xv = a.x[e];
-            if (STEP) xv = fd_sde_apply(xv, a.score[e], zs[j], Gt, a.cf);
+            if (STEP) {
+                float sc = a.score[e];
+                if constexpr (PAIR) sc = fd_guided(sc, a.score[half + e], a.w, a.omw);
+                xv = fd_sde_apply(xv, sc, zs[j], Gt, a.cf);
+            }
             const float xo = a.alpha * a.x0[obase + loc[j]] + a.s * (Gt * zo[j]);
             if (FOURIER) {
                 a.out[e] = xv;
                 const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
                 U[quad_idx(t, c - c0)] = sd * (xo - xv) * inv_r(t, T);
             } else {
-                a.out[e] = mrow[(size_t)t * C + c] ? xo : xv;
+                const float o = mrow[(size_t)t * C + c] ? xo : xv;
+                a.out[e] = o;
+                if constexpr (PAIR) a.out[half + e] = o;
             }
         }
     }
@@ -185,7 +203,9 @@ __global__ __launch_bounds__(kThreads) void k_impute(ImpArgs a) {
             if (r >= T) continue;
             const size_t e = base + (size_t)r * C + c;
             const float sd = a.stdv ? a.stdv[(size_t)r * C + c] : 1.0f;
-            a.out[e] = a.out[e] + (acc0[v] + acc1[v]) / sd;
+            const float o = a.out[e] + (acc0[v] + acc1[v]) / sd;
+            a.out[e] = o;
+            if constexpr (PAIR) a.out[half + e] = o;
         }
     }
 }
@@ -209,12 +229,13 @@ __global__ __launch_bounds__(256) void k_impute_basis(float* __restrict__ Fm, fl
     }
 }
 
-template <bool STEP, bool FOURIER>
-int launch_variant(fd_ctx* ctx, const ImpArgs& a, size_t lds, hipStream_t s) {
+template <bool STEP, bool FOURIER, bool PAIR = false>
+int launch_variant(fd_ctx* ctx, const typename ImpArgsOf<PAIR>::type& a, size_t lds, hipStream_t s) {
     static unsigned long long attr_set = 0;
     if (FOURIER && fd_first_on_device(attr_set, ctx->device))
-        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_impute<STEP, FOURIER>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((k_impute<STEP, FOURIER>), dim3((unsigned)(a.B * a.ncb)), dim3(kThreads), FOURIER ? lds : 0, s, a);
+        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_impute<STEP, FOURIER, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        160 * 1024));
+    hipLaunchKernelGGL((k_impute<STEP, FOURIER, PAIR>), dim3((unsigned)(a.B * a.ncb)), dim3(kThreads), FOURIER ? lds : 0, s, a);
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
 }
@@ -245,6 +266,69 @@ int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s
     const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
     if (step) return fourier ? launch_variant<true, true>(ctx, a, lds, s) : launch_variant<true, false>(ctx, a, lds, s);
     return fourier ? launch_variant<false, true>(ctx, a, lds, s) : launch_variant<false, false>(ctx, a, lds, s);
+}
+
+// the guided step + projection on the paired state (a.B series, 2 a.B rows)
+int launch_pair(fd_ctx* ctx, const ImpArgs& a, const fd_guide& g, bool fourier, hipStream_t s) {
+    const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
+    ImpArgsPair ap{};
+    static_cast<ImpArgs&>(ap) = a;
+    ap.w = g.w;
+    ap.omw = g.omw;
+    return fourier ? launch_variant<true, true, true>(ctx, ap, lds, s) : launch_variant<true, false, true>(ctx, ap, lds, s);
+}
+
+// The loop behind fd_sampler_run_impute_rep (g == null) and fd_sampler_run_impute_cfg: the arguments of the former, checked under
+// the name `who`; a paired guide runs on x (2B,T,C) with its labels (2B) behind the score
+int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
+                const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
+                const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
+                hipStream_t s, const fd_guide* g, const char* who) {
+    fd_ctx* ctx = m->ctx;
+    FD_REQUIRE(ctx, G && timesteps && x, "%s: null pointer", who);
+    FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
+    FD_REQUIRE(ctx, dt > 0.f, "%s: step size must be > 0 (sde.py:158)", who);
+    FD_REQUIRE(ctx, obs_replicas > 0 && B % obs_replicas == 0, "%s: B=%d is not a multiple of obs_replicas=%d", who, B, obs_replicas);
+    const int T = m->d.max_len, C = m->d.n_channels;
+    ImpArgs a{};
+    if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, who)) return rc;
+    a.obs_rep = obs_replicas;
+    // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
+    // at the next grid point; the last step projects hard (alpha = 1, s = 0)
+    std::vector<SdeCoef> cf(n_steps);
+    std::vector<float> al(n_steps), sd(n_steps);
+    for (int i = 0; i < n_steps; ++i) {
+        cf[i] = fd_sde_coef(*sde, (double)timesteps[i], dt);
+        double aa = 1.0, ss = 0.0;
+        if (i + 1 < n_steps) fd_marginal_coef(*sde, (double)timesteps[i + 1], &aa, &ss);
+        al[i] = (float)aa;
+        sd[i] = (float)ss;
+    }
+    const size_t n = (size_t)B * T * C;
+    const int R = fd_guide_rows(g, B);
+    const bool pair = g && g->pair;
+    fd_step_loop lp;
+    if (int rc = fd_step_loop_open(&lp, m, R, mode, fd_guide_bytes(g, B), timesteps, n_steps, s)) return rc;
+    int* lab = (int*)lp.own;
+    if (int rc = fd_guide_begin(m, g, lab, x, B, s)) return rc;
+    fd_guide_scope scope(m, g, lab, R);
+
+    // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run), observation noise behind them
+    const uint64_t per_step = (uint64_t)((n + 3) / 4);
+    a.x = x; a.out = x; a.score = lp.score;
+    a.seed = seed;
+    for (int i = 0; i < n_steps; ++i) {
+        if (int rc = fd_step_loop_eval(&lp, i, x)) return rc;
+        a.zstep = z_steps ? z_steps + (size_t)i * n : nullptr;
+        a.zobs = zobs_steps ? zobs_steps + (size_t)i * n : nullptr;
+        a.cf = cf[i];
+        a.alpha = al[i];
+        a.s = sd[i];
+        a.off_step = offset + (uint64_t)i * per_step;
+        a.off_obs = offset + (uint64_t)(n_steps + i) * per_step;
+        if (int rc = pair ? launch_pair(ctx, a, *g, fourier != 0, s) : launch(ctx, a, true, fourier != 0, s)) return rc;
+    }
+    return FD_OK;
 }
 
 }  // namespace
@@ -302,49 +386,24 @@ extern "C" int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, 
                                          const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
                                          void* stream) {
     if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute")) return rc;
-    fd_ctx* ctx = m->ctx;
-    FD_REQUIRE(ctx, G && timesteps && x, "fd_sampler_run_impute: null pointer");
-    FD_REQUIRE(ctx, n_steps > 0, "fd_sampler_run_impute: n_steps=%d", n_steps);
-    FD_REQUIRE(ctx, dt > 0.f, "fd_sampler_run_impute: step size must be > 0 (sde.py:158)");
-    FD_REQUIRE(ctx, obs_replicas > 0 && B % obs_replicas == 0, "fd_sampler_run_impute: B=%d is not a multiple of obs_replicas=%d", B,
-               obs_replicas);
-    hipStream_t s = (hipStream_t)stream;
-    const int T = m->d.max_len, C = m->d.n_channels;
-    ImpArgs a{};
-    if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, "fd_sampler_run_impute"))
-        return rc;
-    a.obs_rep = obs_replicas;
-    // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
-    // at the next grid point; the last step projects hard (alpha = 1, s = 0)
-    std::vector<SdeCoef> cf(n_steps);
-    std::vector<float> al(n_steps), sd(n_steps);
-    for (int i = 0; i < n_steps; ++i) {
-        cf[i] = fd_sde_coef(*sde, (double)timesteps[i], dt);
-        double aa = 1.0, ss = 0.0;
-        if (i + 1 < n_steps) fd_marginal_coef(*sde, (double)timesteps[i + 1], &aa, &ss);
-        al[i] = (float)aa;
-        sd[i] = (float)ss;
-    }
-    const size_t n = (size_t)B * T * C;
-    fd_step_loop lp;
-    if (int rc = fd_step_loop_open(&lp, m, B, mode, 0, timesteps, n_steps, s)) return rc;
+    return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
+                       seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute");
+}
 
-    // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run), observation noise behind them
-    const uint64_t per_step = (uint64_t)((n + 3) / 4);
-    a.x = x; a.out = x; a.score = lp.score;
-    a.seed = seed;
-    for (int i = 0; i < n_steps; ++i) {
-        if (int rc = fd_step_loop_eval(&lp, i, x)) return rc;
-        a.zstep = z_steps ? z_steps + (size_t)i * n : nullptr;
-        a.zobs = zobs_steps ? zobs_steps + (size_t)i * n : nullptr;
-        a.cf = cf[i];
-        a.alpha = al[i];
-        a.s = sd[i];
-        a.off_step = offset + (uint64_t)i * per_step;
-        a.off_obs = offset + (uint64_t)(n_steps + i) * per_step;
-        if (int rc = launch(ctx, a, true, fourier != 0, s)) return rc;
-    }
-    return FD_OK;
+// fd_sampler_run_impute_rep on a class-conditional model under classifier-free guidance: y (B) one label per state row or null,
+// w the guidance scale.  Labels and w outside {0, 1} (or FDIFF_CFG_FORCE_PAIR): x is (2B,T,C) with the state in its first half, the
+// two evaluations of a step run as one forward on 2B rows and k_impute<.., PAIR> steps and projects on the guided score; else one
+// evaluation on B rows with y bound (w = 0 or y null: the null token), the unpaired kernel.
+extern "C" int fd_sampler_run_impute_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                         int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                         int mask_per_series, const float* feat_std, int fourier, const float* z_steps,
+                                         const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
+                                         const int32_t* y, float cfg_scale, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_cfg")) return rc;
+    if (int rc = fd_guide_check(m, cfg_scale, "fd_sampler_run_impute_cfg")) return rc;
+    const fd_guide g = fd_guide_plan(y, cfg_scale);
+    return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
+                       seed, offset, B, obs_replicas, mode, (hipStream_t)stream, &g, "fd_sampler_run_impute_cfg");
 }
 
 extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,

@@ -112,6 +112,7 @@ int ll_buffers(fd_ctx* ctx, int B, size_t n, bool heun, LlBufs* o) {
 template <class Body>
 int ll_frame(fd_score* m, int mode, const float* G, const float* probes, float* dout, int B, hipStream_t s, Body body) {
     fd_train_mode_scope tm(m, fd_diff_train_mode(m, mode));
+    fd_label_dropout_scope ld(m, 0.f);      // log p(x | y) of the labels as bound (fd_score_set_labels)
     const int T = m->d.max_len, C = m->d.n_channels;
     const size_t n = (size_t)B * T * C;
     const unsigned ew = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)m->ctx->num_cu * 16);

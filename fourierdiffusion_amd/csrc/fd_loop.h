@@ -1,5 +1,6 @@
 // fd_loop.h -- the scaffolding of the step-by-step engine loops (fd_sampler.hip): the entry checks, the arena layout and t vectors of
-// a loop (fd_step_loop), and classifier-free guidance as an option of the two plain loops (fd_guide, fd_cfg.hip).
+// a loop (fd_step_loop), and classifier-free guidance as an option of the plain loops and of the conditional-sampling ones
+// (fd_guide, fd_cfg.hip; fd_impute.hip, fd_dps.hip).
 //
 // A loop form contributes what is its own -- its coefficients, its buffers behind the score, its step launch -- and runs
 //   fd_step_loop lp;  fd_step_loop_open(&lp, ...);  for (k ...) { fd_step_loop_eval(&lp, k, x);  <step kernel on lp.score> }
@@ -44,6 +45,11 @@ struct fd_guide {
     const int* y;           // device int32[B]
     float w, omw;           // the guidance scale and 1 - w
 };
+// What a guided loop runs (fd_cfg.hip): pair = labels present and w outside {0, 1}, or FDIFF_CFG_FORCE_PAIR; else one evaluation on B
+// rows with y bound (w = 0 or y null: the null token on every row)
+fd_guide fd_guide_plan(const int* y, float w);
+// the checks of every guided entry point: a class-conditional model (FD_ERR_ARG otherwise) and a finite guidance scale
+int fd_guide_check(fd_score* m, float w, const char* who);
 inline int fd_guide_rows(const fd_guide* g, int B) { return g && g->pair ? 2 * B : B; }
 // the label vector of the paired forward, the last of the loop's own buffers
 inline size_t fd_guide_bytes(const fd_guide* g, int B) { return g && g->pair ? fd_ws::padded((size_t)2 * B * sizeof(int)) : 0; }

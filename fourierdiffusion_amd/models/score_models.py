@@ -430,16 +430,20 @@ class ScoreModule:
         return y.to(device=self.device, dtype=torch.int32).contiguous()
 
     @contextlib.contextmanager
-    def _labels_bound(self, h, ctx, yd: Optional[torch.Tensor]):
-        """Binds the label vector for the engine calls of the scope (fd_score_set_labels) and clears it afterwards."""
+    def _labels_bound(self, h, ctx, yd: Optional[torch.Tensor], restore: bool = False):
+        """Binds the label vector for the engine calls of the scope (fd_score_set_labels) and clears it afterwards -- or, restore,
+        puts the binding it found (fd_score_get_labels) back."""
         if yd is None:
             yield
             return
+        old_y, old_B = C.c_void_p(), C.c_int(0)
+        if restore:
+            _C.check(_C.lib().fd_score_get_labels(h, C.byref(old_y), C.byref(old_B)), ctx)
         _C.check(_C.lib().fd_score_set_labels(h, yd.data_ptr(), int(yd.shape[0])), ctx)
         try:
             yield
         finally:
-            _C.lib().fd_score_set_labels(h, None, 0)
+            _C.lib().fd_score_set_labels(h, old_y, old_B.value)
 
     def effective_labels(self, y, batch_size: int, key: int, offset: int, p: Optional[float] = None) -> torch.Tensor:
         """The labels a training forward with the Philox stream (key, offset) uses for ``y`` (fd_label_dropout): int32 device vector,

@@ -34,8 +34,11 @@ per launch (fd_likelihood_run); ``sampling.likelihood.to_data_space`` maps the r
 Classifier-free guidance (an extension, not in the reference): on a class-conditional model (``ScoreModule(n_classes=K)``),
 ``sample`` / ``sample_ode`` take labels ``y`` and a guidance scale ``cfg_scale`` = w and follow the score
 w s(x, t, y) + (1 - w) s(x, t, null): one evaluation per step at w = 1 (class-conditional sampling) and w = 0, else the two
-evaluations as one forward on twice the rows and one fused step kernel (fd_sampler_run_cfg, fd_sampler_run_ode_cfg).  The
-predictor-corrector sampler, ``impute`` and ``log_likelihood`` take no labels and run a labelled model unconditionally.
+evaluations as one forward on twice the rows and one fused step kernel (fd_sampler_run_cfg, fd_sampler_run_ode_cfg).
+``impute`` (both conditionings, ensembles included) and ``impute_guidance`` take ``y`` (one label per series) and ``cfg_scale`` the
+same way (fd_sampler_run_impute_cfg, fd_sampler_run_impute_dps_cfg, fd_impute_guidance_cfg), and ``log_likelihood`` takes ``y`` and
+evaluates log p(x | y) -- no ``cfg_scale``: a guided vector field is the probability-flow ODE of no density.  The
+predictor-corrector sampler and ``encode`` / ``decode`` take no labels and run a labelled model unconditionally.
 """
 from __future__ import annotations
 
@@ -172,15 +175,25 @@ class DiffusionSampler:
                 raise ValueError("y / cfg_scale need a class-conditional model (ScoreModule(n_classes=K)); this one has n_classes = 0")
             return False, False
         guided = y is not None or float(cfg_scale) != 1.0
-        # (FDIFF_CFG_FORCE_PAIR, tests: the two-evaluation form also where the combine is exact; the engine reads the same switch)
-        pair = y is not None and (float(cfg_scale) not in (0.0, 1.0) or bool(os.environ.get("FDIFF_CFG_FORCE_PAIR")))
+        # The engine takes the scale as a float and decides on that value (fd_guide_plan), so a scale that rounds to 0 or 1 there
+        # is one evaluation here too.  (FDIFF_CFG_FORCE_PAIR, tests: the two-evaluation form also where the combine is exact; the
+        # engine reads the same switch.)
+        w32 = C.c_float(float(cfg_scale)).value
+        pair = y is not None and (w32 not in (0.0, 1.0) or bool(os.environ.get("FDIFF_CFG_FORCE_PAIR")))
         return guided, pair
 
     def _labels(self, y, total: int) -> Optional[torch.Tensor]:
         """The labels of all ``total`` returned samples as an int32 device vector (None: unconditional)."""
-        if y is not None and not isinstance(y, int) and isinstance(y, torch.Tensor) and y.dim() == 1 and y.shape[0] != total:
+        if isinstance(y, torch.Tensor) and y.dim() == 1 and y.shape[0] != total:
             raise ValueError(f"y must hold one label per returned sample: {total} (whole batches of sample_batch_size), got {y.shape[0]}")
         return self.score_model.labels_on_device(y, total, "y")
+
+    def _series_labels(self, y, n: int, who: str) -> Optional[torch.Tensor]:
+        """The labels of ``n`` conditioning series (``impute``, ``impute_guidance``, ``log_likelihood``: one label per series) as an
+        int32 device vector (None: unconditional)."""
+        if isinstance(y, torch.Tensor) and y.dim() == 1 and y.shape[0] != n:
+            raise ValueError(f"{who}: y must hold one label per series: {n}, got {y.shape[0]}")
+        return self.score_model.labels_on_device(y, n, "y")
 
     @staticmethod
     def _cfg_state(X: torch.Tensor, pair: bool) -> torch.Tensor:
@@ -277,7 +290,7 @@ class DiffusionSampler:
 
     def log_likelihood(self, X: torch.Tensor, num_diffusion_steps: int = 100, solver: str = "heun", *, estimator: str = "rademacher",
                        n_probes: int = 1, probes: Optional[torch.Tensor] = None, seed: Optional[int] = None, rtol: float = 1e-5,
-                       atol: float = 1e-5, max_evals: int = RK45_MAX_EVALS) -> LikelihoodResult:
+                       atol: float = 1e-5, max_evals: int = RK45_MAX_EVALS, y=None, cfg_scale=None) -> LikelihoodResult:
         """Log-density of every series of X (n, max_len, n_channels), in sample space, under the probability-flow ODE:
         log p_1(x_1) + the divergence integral along the ODE from t = eps to t = 1 on ``linspace(eps, 1, N + 1)`` (the grid and
         solver of ``encode``).  The trace of the score Jacobian is estimated per series with ``n_probes`` Hutchinson probes
@@ -288,11 +301,21 @@ class DiffusionSampler:
         [x, divergence integral], run by Dormand-Prince 5(4) with the step control of scipy's RK45 at rtol / atol, at most
         max_evals score evaluations per row (Song et al. 2021 report likelihoods at rtol = atol = 1e-5).  A series any of whose
         rows stops early (max_evals, or a step under scipy's min_step) has converged False and log_prob NaN.
+        y (class-conditional models only; ValueError otherwise): an int, or an integer tensor (n,) with one label per series --
+        log p(x | y) then, the labels replicated over a series' probe rows and bound for the run (the binding found is back
+        afterwards); both the fixed grids and rk45.  y=None evaluates the unconditional density (the null token).  There is no
+        guidance here, and any ``cfg_scale`` other than None is a ValueError: the guided field w s(x, t, y) + (1 - w) s(x, t, null) is the
+        probability-flow ODE of no model density for w outside {0, 1}, so its divergence integral is no log-likelihood.
         Returns a ``LikelihoodResult``; ``to_data_space`` converts ``log_prob`` to the series as the user holds them."""
+        if cfg_scale is not None:
+            raise ValueError("log_likelihood takes no cfg_scale: a guided vector field is not the probability-flow ODE of a model "
+                             "density (pass y for log p(x | y))")
+        self._guided(y, 1.0)
         adaptive = solver == "rk45"
         if adaptive:
             rtol, atol, max_evals = float(rtol), float(atol), int(max_evals)
         n, reps, N, grid, drift = self._ll_plan(X, num_diffusion_steps, solver, estimator, n_probes, probes, rtol, atol, max_evals)
+        labels = self._series_labels(y, n, "log_likelihood")
         ctx, h, p, G, mode = self._engine_args()
         dev = self.score_model.device
         T, Cn = self.max_len, self.n_channels
@@ -305,10 +328,12 @@ class DiffusionSampler:
             nb = min(per_launch, n - lo)
             x = X[lo:lo + nb].to(device=dev, dtype=torch.float32).repeat_interleave(reps, dim=0).contiguous()
             e, off = self._ll_probes(ctx, estimator, probes, lo, nb, reps, key, off)
-            if adaptive:
-                res = self._ll_run_adaptive(ctx, h, p, G, mode, x, e, grid, rtol, atol, max_evals)
-            else:
-                res = self._ll_run(ctx, h, p, G, mode, x, e, grid, N, solver)
+            yb = None if labels is None else labels[lo:lo + nb].repeat_interleave(reps).contiguous()
+            with self.score_model._labels_bound(h, ctx, yb, restore=True):
+                if adaptive:
+                    res = self._ll_run_adaptive(ctx, h, p, G, mode, x, e, grid, rtol, atol, max_evals)
+                else:
+                    res = self._ll_run(ctx, h, p, G, mode, x, e, grid, N, solver)
             x1 = x.view(nb, reps, T, Cn)[:, 0].contiguous()
             lp = torch.empty(nb, device=dev, dtype=torch.float32)
             _C.check(_C.lib().fd_prior_logp(ctx, C.byref(p), G.data_ptr(), x1.data_ptr(), lp.data_ptr(), nb, T, Cn, _C.stream_of(x1)), ctx)
@@ -441,7 +466,8 @@ class DiffusionSampler:
                fourier_transform: bool, feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
                obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None,
-               conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True) -> torch.Tensor:
+               conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True, y=None,
+               cfg_scale: float = 1.0) -> torch.Tensor:
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
         it back with the caller's destandardise / idft), one series per row of ``observed``.  ``num_samples`` = K >= 1: an
         ensemble of K samples per series instead, (n, K, max_len, n_channels); a launch holds max(1, sample_batch_size // K)
@@ -461,7 +487,17 @@ class DiffusionSampler:
         residual of Tweedie's estimate x0_hat at the observations, and the observed entries of the result are NOT reproduced
         exactly.  guidance_jacobian=False drops the network's Jacobian from the gradient (d x0_hat / d x ~ I / alpha): about the
         cost of the projection, against a training forward and an input VJP per step.  guidance_scale: finite, >= 0.  obs_noise is
-        an error under "dps" (no observation is noised)."""
+        an error under "dps" (no observation is noised).
+
+        y, cfg_scale (class-conditional models only; ValueError otherwise): y an int or an integer tensor (n,), ONE label per series
+        (the K rows of an ensemble share their series' label), cfg_scale = w the classifier-free guidance scale as in ``sample``:
+        every reverse step follows w s(x, t, y) + (1 - w) s(x, t, null), under both conditionings (fd_sampler_run_impute_cfg,
+        fd_sampler_run_impute_dps_cfg; under "dps" the gradient's Jacobian is the guided score's).  w = 1 conditions on the class
+        with one evaluation per step, w = 0 ignores the labels; otherwise the two evaluations of a step run as one forward on
+        twice the rows, and a launch holds max(1, sample_batch_size // (2 K)) series, so that the forward workspace stays that of
+        ``sample_batch_size`` rows (the injected noise of a launch is shaped accordingly).  y=None, cfg_scale=1.0: the call
+        without the two arguments, to the bit, on labelled and unlabelled models alike."""
+        guided, pair = self._guided(y, cfg_scale)
         if self.corrector_steps > 0:
             raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
         if num_samples is not None and (isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1):
@@ -482,7 +518,8 @@ class DiffusionSampler:
         ctx, h, p, G, mode = self._engine_args()
         fstd = std if (fourier_transform or dps) else None      # (the guidance weighs the residual by sigma in both domains)
         reps = 1 if num_samples is None else int(num_samples)
-        n, bs = obs.shape[0], max(1, self.sample_batch_size // reps)
+        n, bs = obs.shape[0], max(1, self.sample_batch_size // ((2 if pair else 1) * reps))
+        labels = self._series_labels(y, n, "impute") if guided else None
         out: List[torch.Tensor] = []
         for b, lo in enumerate(range(0, n, bs)):
             nb = min(bs, n - lo)
@@ -493,7 +530,22 @@ class DiffusionSampler:
             key, off = (0, 0) if (z is not None and (zo is not None or dps)) else _rng.stream()
             m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
             x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
-            if dps:
+            if guided:
+                yb = None if labels is None else labels[lo:lo + nb].repeat_interleave(reps).contiguous()
+                X = self._cfg_state(X, pair)
+                if dps:
+                    rc = _C.lib().fd_sampler_run_impute_dps_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(),
+                                                                x0.data_ptr(), m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                                int(bool(fourier_transform)), float(guidance_scale),
+                                                                int(guidance_jacobian), _C.ptr(z), key, off, rows, reps, mode,
+                                                                _C.ptr(yb), float(cfg_scale), _C.stream_of(X))
+                else:
+                    rc = _C.lib().fd_sampler_run_impute_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                            m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                            int(bool(fourier_transform)), _C.ptr(z), _C.ptr(zo), key, off, rows, reps,
+                                                            mode, _C.ptr(yb), float(cfg_scale), _C.stream_of(X))
+                X = X[:rows]
+            elif dps:
                 rc = _C.lib().fd_sampler_run_impute_dps(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
                                                         m_b.data_ptr(), int(per_series), _C.ptr(fstd), int(bool(fourier_transform)),
                                                         float(guidance_scale), int(guidance_jacobian), _C.ptr(z), key, off, rows,
@@ -541,11 +593,16 @@ class DiffusionSampler:
         return out
 
     def impute_guidance(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: float, *,
-                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None, jacobian: bool = True) -> tuple:
+                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None, jacobian: bool = True, y=None,
+                        cfg_scale: float = 1.0) -> tuple:
         """One guidance evaluation of ``impute(conditioning="dps")`` alone (fd_impute_guidance): X (B,T,C) in sample space at
         ``timestep`` -> (g, rnorm2), g = -grad_X ||r||^2 (B,T,C) float32 and rnorm2 = ||r||^2 per row (B,) float64, both on the
         device.  x0_obs from ``observed_to_sample_space``; feature_std: the datamodule's std when it standardises (used in both
-        domains), else None.  jacobian=False: the Jacobian-free gradient (the score from the sampler's forward)."""
+        domains), else None.  jacobian=False: the Jacobian-free gradient (the score from the sampler's forward).
+        y, cfg_scale (class-conditional models only; ValueError otherwise): one label per row (an int, or an integer tensor (B,)) and
+        the classifier-free guidance scale w -- the guidance of the guided score w s(x, t, y) + (1 - w) s(x, t, null), its Jacobian
+        w J_c + (1 - w) J_u (fd_impute_guidance_cfg); g and rnorm2 for the B rows."""
+        guided, _pair = self._guided(y, cfg_scale)
         T, Cn = self.max_len, self.n_channels
         if not (isinstance(X, torch.Tensor) and isinstance(x0_obs, torch.Tensor)) or x0_obs.shape != X.shape or X.dim() != 3 \
                 or tuple(X.shape[1:]) != (T, Cn) or X.shape[0] == 0:
@@ -563,6 +620,14 @@ class DiffusionSampler:
         ctx, h, p, G, mode = self._engine_args()
         g = torch.empty_like(xd)
         rn2 = torch.empty(B, dtype=torch.float64, device=xd.device)
+        if guided:
+            yb = self._series_labels(y, B, "impute_guidance")
+            rc = _C.lib().fd_impute_guidance_cfg(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(),
+                                                 m_u8.data_ptr(), int(per_series), _C.ptr(std), int(bool(fourier_transform)),
+                                                 int(bool(jacobian)), g.data_ptr(), rn2.data_ptr(), B, 1, mode, _C.ptr(yb),
+                                                 float(cfg_scale), _C.stream_of(xd))
+            _C.check(rc, ctx)
+            return g, rn2
         rc = _C.lib().fd_impute_guidance(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(),
                                          int(per_series), _C.ptr(std), int(bool(fourier_transform)), int(bool(jacobian)),
                                          g.data_ptr(), rn2.data_ptr(), B, 1, mode, _C.stream_of(xd))
@@ -698,27 +763,51 @@ class DiffusionSampler:
         raise NotImplementedError("Scheduler not recognized.")
 
 
-def parse_labels(spec, n: int, n_classes: int) -> Optional[torch.Tensor]:
+def parse_labels(spec, n: int, n_classes: int, allow_balanced: bool = True) -> Optional[torch.Tensor]:
     """The ``labels`` setting of the sampler configs as the ``y`` of ``sample`` for n samples: None / "null" -> None (unconditional),
-    an int (or its string) -> that class for every sample, "balanced" -> 0, 1, ..., n_classes - 1 cycled.  ValueError otherwise,
-    for a class outside [0, n_classes), or for any labels on an unlabelled model."""
+    an int (or its string) -> that class for every sample, "balanced" (unless ``allow_balanced`` is False) -> 0, 1, ...,
+    n_classes - 1 cycled.  ValueError otherwise, for a class outside [0, n_classes), or for any labels on an unlabelled model."""
     if spec is None or (isinstance(spec, str) and spec.strip().lower() in ("null", "none", "")):
         return None
     if n_classes <= 0:
         raise ValueError(f"labels={spec!r}, but the model is not class-conditional (score_model.n_classes = 0)")
-    if isinstance(spec, str) and spec.strip().lower() == "balanced":
+    if allow_balanced and isinstance(spec, str) and spec.strip().lower() == "balanced":
         return torch.arange(n, dtype=torch.int64) % n_classes
+    allowed = "an int, 'balanced' or null" if allow_balanced else "'data', an int or null"
     if isinstance(spec, bool):
-        raise ValueError(f"labels must be an int, 'balanced' or null, got {spec!r}")
+        raise ValueError(f"labels must be {allowed}, got {spec!r}")
     try:
         k = int(spec) if not isinstance(spec, float) or spec.is_integer() else None
     except (TypeError, ValueError):
         k = None
     if k is None:
-        raise ValueError(f"labels must be an int, 'balanced' or null, got {spec!r}")
+        raise ValueError(f"labels must be {allowed}, got {spec!r}")
     if not 0 <= k < n_classes:
         raise ValueError(f"labels={k} is not a class of this model (0 .. {n_classes - 1})")
     return torch.full((n,), k, dtype=torch.int64)
+
+
+def series_labels(spec, datamodule, n: int, n_classes: int) -> Optional[torch.Tensor]:
+    """The ``labels`` setting of cmd/impute.py and cmd/likelihood.py as the ``y`` of ``impute`` / ``log_likelihood`` for the first n
+    test series: None / "null" -> None (the model runs unconditionally), an int (or its string) -> that class for every series,
+    "data" -> ``datamodule.y_test[:n]``.  ValueError for any labels on an unlabelled model, a datamodule without labels, a label
+    outside [0, n_classes), or anything else."""
+    if not (isinstance(spec, str) and spec.strip().lower() == "data"):
+        return parse_labels(spec, n, n_classes, allow_balanced=False)
+    if n_classes <= 0:
+        raise ValueError("labels=data, but the model is not class-conditional (score_model.n_classes = 0)")
+    y = getattr(datamodule, "y_test", None)
+    name = type(datamodule).__name__
+    if y is None:
+        raise ValueError(f"labels=data, but {name} has no labels (y_test is None): use a labelled datamodule "
+                         "(datamodule=synthetic_classes, datamodule=ecg), labels=<int> or labels=null")
+    y = torch.as_tensor(y)[:n].to(torch.int64)
+    if y.shape[0] != n:
+        raise ValueError(f"labels=data: {name} holds {y.shape[0]} test labels for {n} series")
+    lo, hi = int(y.min()), int(y.max())
+    if lo < 0 or hi >= n_classes:
+        raise ValueError(f"labels=data: the test labels of {name} lie in [{lo}, {hi}], but the model has n_classes = {n_classes}")
+    return y
 
 
 class ODESampler(DiffusionSampler):

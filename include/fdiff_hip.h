@@ -233,12 +233,15 @@ int fd_score_destroy(fd_score* m);
  *                              offset + (0xFFFF << 40) + b / 4 under the call's seed -- the counter window of encoder layer 16383,
  *                              which the dropout sites never reach.  Eval forwards never drop.  The class-table gradient
  *                              dTable[k] = sum_{b: y_b = k} dtemb[b] is summed over b in ascending order (no atomics).
+ *   fd_score_get_labels        the binding as it stands: *y the bound vector (NULL: none) and *B its length, so that a caller can
+ *                              bind labels for a run and put the earlier binding back (log_likelihood with labels does).
  *   fd_label_dropout           the decision kernel alone: y_out[b] = the label the training forward of (seed, offset) uses for
  *                              y[b] (y == NULL: all null).  y, y_out: device int32[B]. */
 int64_t fd_score_param_count_cond(const fd_model_dims* dims, int n_classes);
 int fd_score_layout_cond(const fd_model_dims* dims, int n_classes, fd_param_entry* entries, int* n_entries);
 int fd_score_create_cond(fd_ctx* ctx, const fd_model_dims* dims, int n_classes, fd_score** out);
 int fd_score_set_labels(fd_score* m, const int32_t* y, int B);
+int fd_score_get_labels(fd_score* m, const int32_t** y, int* B);
 int fd_score_set_label_dropout(fd_score* m, float p);
 int fd_label_dropout(fd_ctx* ctx, const int32_t* y, int32_t* y_out, int B, int n_classes, float p, uint64_t seed, uint64_t offset,
                      void* stream);
@@ -376,6 +379,18 @@ int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, const float
                               float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                               const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
                               uint64_t offset, int B, int obs_replicas, int mode, void* stream);
+/* fd_sampler_run_impute_rep on a class-conditional model (fd_score_create_cond, n_classes > 0; FD_ERR_ARG otherwise) under
+ * classifier-free guidance: every step follows w s(x, t, y) + (1 - w) s(x, t, null).  y: device int32[B], one label per state row
+ * (n_classes = the null token), or NULL; cfg_scale = w, finite.  Labels and w outside {0, 1} (or FDIFF_CFG_FORCE_PAIR): x is
+ * (2B,T,C), the state in rows [0, B); the two evaluations run as one forward on 2B rows and one kernel steps and projects on the
+ * guided score and writes both halves (bit-equal on return).  Otherwise x is (B,T,C) and every step is one evaluation with y bound
+ * (w = 0 or y NULL: the null token) -- at w = 1 the numbers of fd_sampler_run_impute_rep with y bound by fd_score_set_labels.
+ * Philox counters, the noise tensors (n_steps,B,T,C) and the observation rows are those of fd_sampler_run_impute_rep over B rows;
+ * the caller's label binding is restored on return. */
+int fd_sampler_run_impute_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                              float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                              const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
+                              uint64_t offset, int B, int obs_replicas, int mode, const int32_t* y, float cfg_scale, void* stream);
 
 /* Gradient-guided conditional sampling extension (NOT in the reference; diffusion posterior sampling, Chung et al. 2023, and
  * TSDiff's observation self-guidance, Kollovieh et al. 2023).  The state is never overwritten; every reverse step is nudged along
@@ -404,6 +419,23 @@ int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, const float
                               float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
                               int fourier, float guidance_scale, int jacobian, const float* z_steps, uint64_t seed, uint64_t offset,
                               int B, int obs_replicas, int mode, void* stream);
+/* The two above under classifier-free guidance (class-conditional models; FD_ERR_ARG otherwise), y / cfg_scale and the pairing rule
+ * as fd_sampler_run_impute_cfg.  The score in x0_hat and in the step is the guided one, and
+ *   dx = w J_c^T v + (1 - w) J_u^T v,  v = s^2 G^2 . u:
+ * one training forward and one input VJP on 2B rows with the labels [y ; null], the VJP's input (w v ; (1 - w) v), its two output
+ * halves added (conditional first).  Label dropout is off in these forwards.
+ *   fd_impute_guidance_cfg       : x (B,T,C) (a paired call copies it twice into its own buffers); g_out, rnorm2_out for the B rows.
+ *   fd_sampler_run_impute_dps_cfg: a paired call takes x (2B,T,C), the state in rows [0, B), and leaves both halves equal; Philox
+ *                                  and z_steps (n_steps,B,T,C) as fd_sampler_run_impute_dps over B rows. */
+int fd_impute_guidance_cfg(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                           const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian,
+                           float* g_out, double* rnorm2_out, int B, int obs_replicas, int mode, const int32_t* y, float cfg_scale,
+                           void* stream);
+int fd_sampler_run_impute_dps_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                  float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                  const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
+                                  uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode, const int32_t* y,
+                                  float cfg_scale, void* stream);
 
 /* Probability-flow ODE extension (NOT in the reference, whose only sampler is Euler-Maruyama over the reverse SDE; Song et al. 2021,
  * Sec. 4.3): the deterministic ODE with the reverse SDE's marginals.  With a = a_x(t), g = g(t) of the SDE (VP: a = beta/2,
