@@ -92,14 +92,11 @@ def class_table_grad(sd, tab, sde, X, t, z, y, n_head, dim_ff=2048):
     import math
 
     import torch
-    from torch import nn
+
+    from tests import autograd_ref
     f64 = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))
     Dm = sd["embedder.weight"].shape[0]
-    L = sum(1 for k in sd if k.endswith("linear1.weight"))
-    layer = nn.TransformerEncoderLayer(d_model=Dm, nhead=n_head, dim_feedforward=dim_ff, dropout=0.0, batch_first=True)
-    enc = nn.TransformerEncoder(layer, num_layers=L, enable_nested_tensor=False).double()
-    enc.load_state_dict({k[len("backbone."):]: f64(v) for k, v in sd.items() if k.startswith("backbone.")})
-    enc.train()       # (dropout 0: the plain python path of the layer, no fused inference kernel)
+    enc = autograd_ref.encoder(sd, n_head, dim_ff)      # (nn.TransformerEncoder in float64, train mode, dropout 0)
     tabp = f64(tab).requires_grad_(True)
     bias = f64(sd["time_encoder.dense.bias"]).requires_grad_(True)
     Xn, target, std = O.perturb(sde, X, t, z)

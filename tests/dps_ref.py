@@ -64,13 +64,15 @@ def vjp(score_fn, x, t, v, rel=1e-7):
     return out
 
 
-def guidance(score_fn, sde, x, t, x0, m, sigma, fourier, jacobian=True, score=None, rel=1e-7):
-    """(g, ||r||^2 per row, score) at (x, t); score: the evaluation's score if the caller has it."""
+def guidance(score_fn, sde, x, t, x0, m, sigma, fourier, jacobian=True, score=None, rel=1e-7, vjp_fn=None):
+    """(g, ||r||^2 per row, score) at (x, t); score: the evaluation's score if the caller has it.  vjp_fn(x, t, v) -> J^T v replaces
+    the central differences (tests/autograd_ref.vjp_fn: exact, and affordable at any shape)."""
     alpha, s = coef(sde, t)
     x = np.asarray(x, dtype=np.float64)
     score = score_fn(x, t) if score is None else score
     r, u = residual(x, score, x0, m, sigma, sde.G, alpha, s, fourier)
-    dx = vjp(score_fn, x, t, (s * s) * (sde.G ** 2)[None, :, None] * u, rel) if jacobian else 0.0
+    v = (s * s) * (sde.G ** 2)[None, :, None] * u
+    dx = (vjp(score_fn, x, t, v, rel) if vjp_fn is None else vjp_fn(x, t, v)) if jacobian else 0.0
     return (2.0 / alpha) * (u + dx), (r * r).sum(axis=(1, 2)), score
 
 
@@ -81,16 +83,21 @@ def rnorm2(score_fn, sde, x, t, x0, m, sigma, fourier):
     return (r * r).sum(axis=(1, 2))
 
 
-def trajectory(score_fn, sde, z_prior, z_steps, x0, m, sigma, fourier, zeta, jacobian=True, eps=1e-5):
+def step(score_fn, sde, X, t, dt, z, x0, m, sigma, fourier, zeta, jacobian=True, vjp_fn=None):
+    """One guided reverse step from X at t with predictor noise z."""
+    g, rn2, score = guidance(score_fn, sde, X, float(t), x0, m, sigma, fourier, jacobian, vjp_fn=vjp_fn)
+    nr = np.sqrt(rn2)
+    c = np.where(nr > 0, zeta / np.where(nr > 0, nr, 1.0), 0.0)
+    return O.sde_step(sde, score, float(t), X, z, float(dt)) + c[:, None, None] * g
+
+
+def trajectory(score_fn, sde, z_prior, z_steps, x0, m, sigma, fourier, zeta, jacobian=True, eps=1e-5, vjp_fn=None):
     """impute(conditioning="dps") for one batch from injected prior / predictor noise; x0 (B,T,C) per state row."""
     N = len(z_steps)
     ts, dt = O.timesteps(N, eps)
     X = O.prior_sampling(sde, z_prior)
     for i, t in enumerate(ts):
-        g, rn2, score = guidance(score_fn, sde, X, float(t), x0, m, sigma, fourier, jacobian)
-        nr = np.sqrt(rn2)
-        c = np.where(nr > 0, zeta / np.where(nr > 0, nr, 1.0), 0.0)
-        X = O.sde_step(sde, score, float(t), X, z_steps[i], float(dt)) + c[:, None, None] * g
+        X = step(score_fn, sde, X, t, dt, z_steps[i], x0, m, sigma, fourier, zeta, jacobian, vjp_fn)
     return X
 
 

@@ -45,7 +45,13 @@ def report_err(tag, got, ref):
     got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
     err = float(np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30))
     rms = float(np.sqrt(((got - ref) ** 2).mean()) / max(np.sqrt((ref ** 2).mean()), 1e-30))
-    line = f"[parity] {tag}: max err / scale = {err:.3e}, relative rms = {rms:.3e}"
+    log_line(f"[parity] {tag}: max err / scale = {err:.3e}, relative rms = {rms:.3e}")
+    return err, rms
+
+
+def log_line(line):
+    """Prints a line and appends it to report_err's file."""
+    import os
     print(line)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     try:
@@ -54,4 +60,3 @@ def report_err(tag, got, ref):
             f.write(line + "\n")
     except OSError:
         pass
-    return err, rms
