@@ -7,7 +7,9 @@ num_samples_per_series=K > 1 draws an ensemble of K samples per series instead: 
 holds the ensemble scores of sampling/forecast.py (CRPS, quantile CRPS and CRPS-sum, median errors, 90 % interval coverage) in
 place of the MSE / MAE.  conditioning=dps (guidance.scale, guidance.jacobian) replaces the projection by gradient guidance; the three
 keys are then recorded in the `impute` block.  labels=data|<int> (class-conditional models) conditions every series on its test label
-(`datamodule.y_test`) or on one class, cfg_scale=w sets the classifier-free guidance scale; both are recorded only when set.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+(`datamodule.y_test`) or on one class, cfg_scale=w sets the classifier-free guidance scale; both are recorded only when set.
+resample=r jump_length=j (conditioning=replace) turn on RePaint resampling: every block of j steps runs r times with a forward re-noise
+between two runs, r * num_diffusion_steps score evaluations; both are recorded when they are not 1.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -90,6 +92,8 @@ class ImputationRunner:
         self.guidance_jacobian = bool(guidance.get("jacobian", True))
         self.labels = cfg.get("labels", None)
         self.cfg_scale = float(cfg.get("cfg_scale", 1.0))
+        self.resample = int(cfg.get("resample", 1))
+        self.jump_length = int(cfg.get("jump_length", 1))
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
         self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path,
@@ -112,6 +116,7 @@ class ImputationRunner:
         lo, hi = shard_range(int(truth.shape[0]), self.dist.rank, self.dist.world)  # independent rows: no exchange
         y = series_labels(self.labels, self.datamodule, int(truth.shape[0]), int(getattr(self.score_model, "n_classes", 0)))
         guided = {} if (y is None and self.cfg_scale == 1.0) else dict(y=None if y is None else y[lo:hi], cfg_scale=self.cfg_scale)
+        repaint = {k: v for k, v in (("resample", self.resample), ("jump_length", self.jump_length)) if v != 1}
         mean = std = None
         if self.datamodule.standardize:
             mean, std = self.datamodule.feature_mean_and_std
@@ -120,7 +125,7 @@ class ImputationRunner:
             X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
                                     feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K,
                                     conditioning=self.conditioning, guidance_scale=self.guidance_scale,
-                                    guidance_jacobian=self.guidance_jacobian, **guided)
+                                    guidance_jacobian=self.guidance_jacobian, **guided, **repaint)
             shape = X.shape
             X = X.reshape(-1, *shape[-2:])                                          # (rows, T, C) for the maps back
             if std is not None:
@@ -144,6 +149,7 @@ class ImputationRunner:
                                          guidance_jacobian=self.guidance_jacobian)
             if guided:
                 results["impute"].update(labels=None if y is None else str(self.labels), cfg_scale=self.cfg_scale)
+            results["impute"].update(repaint)
             logging.info(f"Saving imputations and errors to {self.save_dir}.\n{dict_to_str(results['impute'])}")
             yaml.dump(data=results, stream=open(results_path, "w"))
             torch.save(X, self.save_dir / "imputations.pt")

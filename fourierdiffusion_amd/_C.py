@@ -115,6 +115,11 @@ _PROTOS = {
     "fd_sampler_run_impute_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                             _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp,
                                             C.c_float, _vp]),
+    "fd_impute_project_renoise": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_float, _vp, C.c_uint64,
+                                            C.c_uint64, C.c_float, C.c_float, _vp, C.c_uint64, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_impute_repaint": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                                _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp,
+                                                C.c_float, _vp, C.c_int, C.c_int, _vp]),
     "fd_impute_guidance": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp,
                                      _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_impute_dps": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,

@@ -19,6 +19,12 @@
 // Phase 2: V = F^T U (v_mfma_f32_16x16x4_f32, 16 time rows x 16 channels per tile), masked into the LDS image W.  Phase 3:
 // Y = F W, out += Y / sigma.  Both LDS images are Tp x 16 floats in k-quad order, [(k / 4)][channel][k % 4], so that the
 // B operand of four consecutive MFMAs is one conflict-free ds_read_b128 per lane; LDS = 128 Tp bytes (128 KiB at T = 1024).
+//
+// RePaint resampling (Lugmayr et al. 2022; fd_sampler_run_impute_repaint): the steps are cut into blocks of jump_length, each block
+// runs `resample` times, and between two runs the state is diffused forward from the block's last level to its first by the
+// transition kernel, x <- ra x + rb G z_r.  The projector P = A^-1 m A is linear, so
+//   ra (x_s + P(x_obs - x_s)) + rb G z_r = xt + P(ra d),   xt = ra x_s + rb G z_r,
+// and the re-noise folds into phase 1 of the block's last step (RENOISE): one more Philox group, xt to `out`, ra sigma d / r to U.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -51,6 +57,10 @@ struct ImpArgs {
     SdeCoef cf;
     float alpha, s;
     uint64_t seed, off_step, off_obs;
+    // RENOISE only
+    const float* zre;        // (B,T,C) injected re-noise or nullptr (Philox at off_re)
+    float ra, rb;            // the forward transition kernel between the two levels: x <- ra x + rb G z_r
+    uint64_t off_re;
 };
 // PAIR (classifier-free guidance, fd_loop.h): x, score and out are (2B,T,C), rows [B, 2B) the null-token twin of rows [0, B)
 struct ImpArgsPair : ImpArgs {
@@ -70,7 +80,8 @@ __device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB +
 // PAIR: the workgroup of (b, channel block) reads x[b], steps with the guided score fd_guided(score[b], score[B + b]) and writes
 // every final value to rows b and B + b, so the two halves stay bit-equal; the Philox counters and lanes are those of the unpaired
 // launch over n = B T C (the second half draws nothing).
-template <bool STEP, bool FOURIER, bool PAIR = false>
+// RENOISE: the projected state is diffused forward in the same pass, out = ra (projected x) + rb G z_r (see the head of the file).
+template <bool STEP, bool FOURIER, bool PAIR = false, bool RENOISE = false>
 __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::type a) {
     extern __shared__ float lds[];
     float* U = lds;                            // sigma d / r, frequency rows
@@ -123,6 +134,16 @@ __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::t
                 fd_randn4(a.off_obs + g, a.seed, zo);
             }
         }
+        [[maybe_unused]] float zr[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (RENOISE) {
+            if (a.zre) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (own[j]) zr[j] = a.zre[base + loc[j]];
+            } else {
+                fd_randn4(a.off_re + g, a.seed, zr);
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (!own[j]) continue;
@@ -136,7 +157,19 @@ __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::t
                 xv = fd_sde_apply(xv, sc, zs[j], Gt, a.cf);
             }
             const float xo = a.alpha * a.x0[obase + loc[j]] + a.s * (Gt * zo[j]);
-            if (FOURIER) {
+            if constexpr (RENOISE) {
+                const float nz = a.rb * (Gt * zr[j]);
+                const float xt = a.ra * xv + nz;
+                if (FOURIER) {
+                    a.out[e] = xt;
+                    const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
+                    U[quad_idx(t, c - c0)] = sd * (a.ra * (xo - xv)) * inv_r(t, T);
+                } else {
+                    const float o = mrow[(size_t)t * C + c] ? a.ra * xo + nz : xt;
+                    a.out[e] = o;
+                    if constexpr (PAIR) a.out[half + e] = o;
+                }
+            } else if (FOURIER) {
                 a.out[e] = xv;
                 const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
                 U[quad_idx(t, c - c0)] = sd * (xo - xv) * inv_r(t, T);
@@ -229,13 +262,13 @@ __global__ __launch_bounds__(256) void k_impute_basis(float* __restrict__ Fm, fl
     }
 }
 
-template <bool STEP, bool FOURIER, bool PAIR = false>
+template <bool STEP, bool FOURIER, bool PAIR = false, bool RENOISE = false>
 int launch_variant(fd_ctx* ctx, const typename ImpArgsOf<PAIR>::type& a, size_t lds, hipStream_t s) {
     static unsigned long long attr_set = 0;
     if (FOURIER && fd_first_on_device(attr_set, ctx->device))
-        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_impute<STEP, FOURIER, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_impute<STEP, FOURIER, PAIR, RENOISE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         160 * 1024));
-    hipLaunchKernelGGL((k_impute<STEP, FOURIER, PAIR>), dim3((unsigned)(a.B * a.ncb)), dim3(kThreads), FOURIER ? lds : 0, s, a);
+    hipLaunchKernelGGL((k_impute<STEP, FOURIER, PAIR, RENOISE>), dim3((unsigned)(a.B * a.ncb)), dim3(kThreads), FOURIER ? lds : 0, s, a);
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
 }
@@ -262,33 +295,55 @@ int prepare(fd_ctx* ctx, ImpArgs& a, const float* x0, const uint8_t* mask, int m
     return FD_OK;
 }
 
-int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s) {
+// renoise: the RENOISE variants (a.ra, a.rb, a.zre, a.off_re set): the loop's fused step, or the step-wise projection
+int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s, bool renoise = false) {
     const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
+    if (renoise) {
+        if (step) return fourier ? launch_variant<true, true, false, true>(ctx, a, lds, s)
+                                 : launch_variant<true, false, false, true>(ctx, a, lds, s);
+        return fourier ? launch_variant<false, true, false, true>(ctx, a, lds, s)
+                       : launch_variant<false, false, false, true>(ctx, a, lds, s);
+    }
     if (step) return fourier ? launch_variant<true, true>(ctx, a, lds, s) : launch_variant<true, false>(ctx, a, lds, s);
     return fourier ? launch_variant<false, true>(ctx, a, lds, s) : launch_variant<false, false>(ctx, a, lds, s);
 }
 
 // the guided step + projection on the paired state (a.B series, 2 a.B rows)
-int launch_pair(fd_ctx* ctx, const ImpArgs& a, const fd_guide& g, bool fourier, hipStream_t s) {
+int launch_pair(fd_ctx* ctx, const ImpArgs& a, const fd_guide& g, bool fourier, hipStream_t s, bool renoise = false) {
     const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
     ImpArgsPair ap{};
     static_cast<ImpArgs&>(ap) = a;
     ap.w = g.w;
     ap.omw = g.omw;
+    if (renoise)
+        return fourier ? launch_variant<true, true, true, true>(ctx, ap, lds, s) : launch_variant<true, false, true, true>(ctx, ap, lds, s);
     return fourier ? launch_variant<true, true, true>(ctx, ap, lds, s) : launch_variant<true, false, true>(ctx, ap, lds, s);
 }
 
-// The loop behind fd_sampler_run_impute_rep (g == null) and fd_sampler_run_impute_cfg: the arguments of the former, checked under
-// the name `who`; a paired guide runs on x (2B,T,C) with its labels (2B) behind the score
+// (alpha, s) of level i of an n-step grid: the perturbation kernel at timesteps[i], the clean level (1, 0) at i = n
+void level_coef(const fd_sde_params& sde, const float* timesteps, int n_steps, int i, double* alpha, double* sdev) {
+    *alpha = 1.0;
+    *sdev = 0.0;
+    if (i < n_steps) fd_marginal_coef(sde, (double)timesteps[i], alpha, sdev);
+}
+
+// The loop behind fd_sampler_run_impute_rep (g == null), fd_sampler_run_impute_cfg and fd_sampler_run_impute_repaint: the arguments of
+// the first, checked under the name `who`; a paired guide runs on x (2B,T,C) with its labels (2B) behind the score.  resample = r,
+// jump_length = j: the steps are cut into blocks [i0, min(i0 + j, n_steps)), each block runs r times, and the last step of every run
+// but the r-th re-noises from level i1 back to level i0 (RENOISE); r = 1 is the plain loop for every j.  E = r n_steps evaluations, K =
+// (r - 1) ceil(n_steps / j) re-noises; z_steps, zobs_steps (E,B,T,C) and zre_steps (K,B,T,C) in execution order.
 int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
                 const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
                 const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
-                hipStream_t s, const fd_guide* g, const char* who) {
+                hipStream_t s, const fd_guide* g, const char* who, const float* zre_steps = nullptr, int resample = 1,
+                int jump_length = 1) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, G && timesteps && x, "%s: null pointer", who);
     FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
     FD_REQUIRE(ctx, dt > 0.f, "%s: step size must be > 0 (sde.py:158)", who);
     FD_REQUIRE(ctx, obs_replicas > 0 && B % obs_replicas == 0, "%s: B=%d is not a multiple of obs_replicas=%d", who, B, obs_replicas);
+    FD_REQUIRE(ctx, resample >= 1 && jump_length >= 1, "%s: resample=%d jump_length=%d must be >= 1", who, resample, jump_length);
+    FD_REQUIRE(ctx, (long long)resample * n_steps < (1ll << 31), "%s: resample=%d x n_steps=%d evaluations", who, resample, n_steps);
     const int T = m->d.max_len, C = m->d.n_channels;
     ImpArgs a{};
     if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, who)) return rc;
@@ -299,34 +354,68 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
     std::vector<float> al(n_steps), sd(n_steps);
     for (int i = 0; i < n_steps; ++i) {
         cf[i] = fd_sde_coef(*sde, (double)timesteps[i], dt);
-        double aa = 1.0, ss = 0.0;
-        if (i + 1 < n_steps) fd_marginal_coef(*sde, (double)timesteps[i + 1], &aa, &ss);
+        double aa, ss;
+        level_coef(*sde, timesteps, n_steps, i + 1, &aa, &ss);
         al[i] = (float)aa;
         sd[i] = (float)ss;
+    }
+    // the executed steps in order (the evaluation-time table follows them), and the transition kernel of every block, in double:
+    // ra = alpha(i0) / alpha(i1), rb^2 = s(i0)^2 - ra^2 s(i1)^2 (the variance the forward process adds between the two levels)
+    const int E = resample * n_steps;
+    std::vector<int> step_of(E);
+    std::vector<float> te(E), ra((size_t)n_steps, 1.f), rb((size_t)n_steps, 0.f);      // ra, rb indexed by the block's last step
+    for (int i0 = 0, e = 0; i0 < n_steps; i0 += jump_length) {
+        const int i1 = std::min(i0 + jump_length, n_steps);
+        for (int r = 0; r < resample; ++r)
+            for (int i = i0; i < i1; ++i, ++e) {
+                step_of[e] = i;
+                te[e] = timesteps[i];
+            }
+        if (resample > 1) {
+            double a0, s0, a1, s1;
+            level_coef(*sde, timesteps, n_steps, i0, &a0, &s0);
+            level_coef(*sde, timesteps, n_steps, i1, &a1, &s1);
+            const double q = a0 / a1, rad = s0 * s0 - q * q * s1 * s1;
+            FD_REQUIRE(ctx, rad >= -1e-12, "%s: levels %d -> %d: the transition variance %g is negative (timesteps must decrease)", who,
+                       i1, i0, rad);
+            ra[i1 - 1] = (float)q;
+            rb[i1 - 1] = (float)std::sqrt(std::max(rad, 0.0));
+        }
     }
     const size_t n = (size_t)B * T * C;
     const int R = fd_guide_rows(g, B);
     const bool pair = g && g->pair;
     fd_step_loop lp;
-    if (int rc = fd_step_loop_open(&lp, m, R, mode, fd_guide_bytes(g, B), timesteps, n_steps, s)) return rc;
+    if (int rc = fd_step_loop_open(&lp, m, R, mode, fd_guide_bytes(g, B), te.data(), E, s)) return rc;
     int* lab = (int*)lp.own;
     if (int rc = fd_guide_begin(m, g, lab, x, B, s)) return rc;
     fd_guide_scope scope(m, g, lab, R);
 
-    // Philox counters: predictor noise of step i at offset + i*per_step (as fd_sampler_run), observation noise behind them
+    // Philox counters: predictor noise of executed step e at offset + e*per_step (as fd_sampler_run), observation noise behind them
+    // at offset + (E + e)*per_step, re-noise k behind those at offset + (2E + k)*per_step
     const uint64_t per_step = (uint64_t)((n + 3) / 4);
     a.x = x; a.out = x; a.score = lp.score;
     a.seed = seed;
-    for (int i = 0; i < n_steps; ++i) {
-        if (int rc = fd_step_loop_eval(&lp, i, x)) return rc;
-        a.zstep = z_steps ? z_steps + (size_t)i * n : nullptr;
-        a.zobs = zobs_steps ? zobs_steps + (size_t)i * n : nullptr;
+    for (int e = 0, k = 0; e < E; ++e) {
+        const int i = step_of[e];
+        // the last step of a block's run, unless the run is the block's last: e + 1 then restarts the block
+        const bool renoise = e + 1 < E && step_of[e + 1] <= i;
+        if (int rc = fd_step_loop_eval(&lp, e, x)) return rc;
+        a.zstep = z_steps ? z_steps + (size_t)e * n : nullptr;
+        a.zobs = zobs_steps ? zobs_steps + (size_t)e * n : nullptr;
         a.cf = cf[i];
         a.alpha = al[i];
         a.s = sd[i];
-        a.off_step = offset + (uint64_t)i * per_step;
-        a.off_obs = offset + (uint64_t)(n_steps + i) * per_step;
-        if (int rc = pair ? launch_pair(ctx, a, *g, fourier != 0, s) : launch(ctx, a, true, fourier != 0, s)) return rc;
+        a.off_step = offset + (uint64_t)e * per_step;
+        a.off_obs = offset + (uint64_t)(E + e) * per_step;
+        if (renoise) {
+            a.zre = zre_steps ? zre_steps + (size_t)k * n : nullptr;
+            a.ra = ra[i];
+            a.rb = rb[i];
+            a.off_re = offset + ((uint64_t)2 * E + (uint64_t)k) * per_step;
+            ++k;
+        }
+        if (int rc = pair ? launch_pair(ctx, a, *g, fourier != 0, s, renoise) : launch(ctx, a, true, fourier != 0, s, renoise)) return rc;
     }
     return FD_OK;
 }
@@ -380,6 +469,28 @@ extern "C" int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_ob
     return launch(ctx, a, false, fourier != 0, hs);
 }
 
+extern "C" int fd_impute_project_renoise(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                         const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
+                                         uint64_t seed, uint64_t offset, float a, float b, const float* z_re, uint64_t offset_re,
+                                         float* out, int B, int T, int C, void* stream) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, x && out, "fd_impute_project_renoise: null pointer");
+    FD_REQUIRE(ctx, std::isfinite(a) && std::isfinite(b) && b >= 0.f, "fd_impute_project_renoise: a=%g b=%g (finite, b >= 0)", (double)a,
+               (double)b);
+    hipStream_t hs = (hipStream_t)stream;
+    ImpArgs ia{};
+    if (int rc = prepare(ctx, ia, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, hs, "fd_impute_project_renoise"))
+        return rc;
+    ia.x = x; ia.out = out;
+    ia.zobs = z;
+    ia.alpha = alpha; ia.s = s;
+    ia.seed = seed; ia.off_obs = offset;
+    ia.zre = z_re;
+    ia.ra = a; ia.rb = b;
+    ia.off_re = offset_re;
+    return launch(ctx, ia, false, fourier != 0, hs, true);
+}
+
 extern "C" int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
                                          int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
                                          int mask_per_series, const float* feat_std, int fourier, const float* z_steps,
@@ -404,6 +515,26 @@ extern "C" int fd_sampler_run_impute_cfg(fd_score* m, const fd_sde_params* sde, 
     const fd_guide g = fd_guide_plan(y, cfg_scale);
     return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
                        seed, offset, B, obs_replicas, mode, (hipStream_t)stream, &g, "fd_sampler_run_impute_cfg");
+}
+
+// fd_sampler_run_impute_cfg with RePaint resampling (see impute_loop); y null and cfg_scale = 1: the unguided loop, on any model
+extern "C" int fd_sampler_run_impute_repaint(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                             int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                             int mask_per_series, const float* feat_std, int fourier, const float* z_steps,
+                                             const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
+                                             const int32_t* y, float cfg_scale, const float* zre_steps, int resample, int jump_length,
+                                             void* stream) {
+    const char* who = "fd_sampler_run_impute_repaint";
+    if (int rc = fd_loop_check(m, sde, B, mode, who)) return rc;
+    const bool guided = y || cfg_scale != 1.0f;
+    fd_guide g{};
+    if (guided) {
+        if (int rc = fd_guide_check(m, cfg_scale, who)) return rc;
+        g = fd_guide_plan(y, cfg_scale);
+    }
+    return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
+                       seed, offset, B, obs_replicas, mode, (hipStream_t)stream, guided ? &g : nullptr, who, zre_steps, resample,
+                       jump_length);
 }
 
 extern "C" int fd_sampler_run_impute(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,

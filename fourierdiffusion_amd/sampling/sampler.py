@@ -466,7 +466,8 @@ class DiffusionSampler:
                fourier_transform: bool, feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
                obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None,
-               conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True, y=None,
+               conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True,
+               resample: int = 1, jump_length: int = 1, renoise_noise: Optional[Sequence[torch.Tensor]] = None, y=None,
                cfg_scale: float = 1.0) -> torch.Tensor:
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
         it back with the caller's destandardise / idft), one series per row of ``observed``.  ``num_samples`` = K >= 1: an
@@ -496,8 +497,23 @@ class DiffusionSampler:
         with one evaluation per step, w = 0 ignores the labels; otherwise the two evaluations of a step run as one forward on
         twice the rows, and a launch holds max(1, sample_batch_size // (2 K)) series, so that the forward workspace stays that of
         ``sample_batch_size`` rows (the injected noise of a launch is shaped accordingly).  y=None, cfg_scale=1.0: the call
-        without the two arguments, to the bit, on labelled and unlabelled models alike."""
+        without the two arguments, to the bit, on labelled and unlabelled models alike.
+
+        resample = r, jump_length = j (conditioning="replace" only; RePaint, Lugmayr et al. 2022): the N steps are cut into blocks of
+        j, every block is executed r times, and between two executions the state is diffused forward again from the block's last
+        level to its first (``repaint_schedule``), so that the hidden part can harmonise with what the projection pasted in.
+        E = r N score evaluations and K = (r - 1) ceil(N / j) re-noises, each fused into the kernel of the step before it
+        (fd_sampler_run_impute_repaint).  With r > 1, step_noise[b] / obs_noise[b] are (E,nb,T,C) in execution order and
+        renoise_noise[b] is (K,nb,T,C); the Philox stream is used only when all of them are absent.  r = 1 is the call without the
+        arguments for every j, to the bit (renoise_noise is an error there)."""
         guided, pair = self._guided(y, cfg_scale)
+        for name, v in (("resample", resample), ("jump_length", jump_length)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"impute: {name} must be an int >= 1, got {v!r}")
+        if resample > 1 and conditioning == "dps":
+            raise ValueError("impute: resample > 1 is not supported with conditioning='dps' (the state is never projected)")
+        if resample == 1 and renoise_noise is not None:
+            raise ValueError("impute: renoise_noise is only read with resample > 1 (no state is re-noised)")
         if self.corrector_steps > 0:
             raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
         if num_samples is not None and (isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1):
@@ -520,17 +536,31 @@ class DiffusionSampler:
         reps = 1 if num_samples is None else int(num_samples)
         n, bs = obs.shape[0], max(1, self.sample_batch_size // ((2 if pair else 1) * reps))
         labels = self._series_labels(y, n, "impute") if guided else None
+        # executed steps and re-noises (resample = 1: N and 0, today's loop)
+        sched = self.repaint_schedule(N, resample, jump_length) if resample > 1 else []
+        K = sum(1 for op in sched if op[0] == "renoise")
+        E = len(sched) - K if resample > 1 else N
         out: List[torch.Tensor] = []
         for b, lo in enumerate(range(0, n, bs)):
             nb = min(bs, n - lo)
             rows = nb * reps
             X = self.sample_prior(rows, noise=None if prior_noise is None else prior_noise[b])
-            z = None if step_noise is None else self._noise(step_noise[b], (N, rows), "step_noise")
-            zo = None if obs_noise is None else self._noise(obs_noise[b], (N, rows), "obs_noise")
-            key, off = (0, 0) if (z is not None and (zo is not None or dps)) else _rng.stream()
+            z = None if step_noise is None else self._noise(step_noise[b], (E, rows), "step_noise")
+            zo = None if obs_noise is None else self._noise(obs_noise[b], (E, rows), "obs_noise")
+            zr = None if renoise_noise is None else self._noise(renoise_noise[b], (K, rows), "renoise_noise")
+            key, off = (0, 0) if (z is not None and (zo is not None or dps) and (zr is not None or K == 0)) else _rng.stream()
             m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
             x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
-            if guided:
+            if resample > 1:
+                yb = None if labels is None else labels[lo:lo + nb].repeat_interleave(reps).contiguous()
+                X = self._cfg_state(X, pair)
+                rc = _C.lib().fd_sampler_run_impute_repaint(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                            m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                            int(bool(fourier_transform)), _C.ptr(z), _C.ptr(zo), key, off, rows, reps,
+                                                            mode, _C.ptr(yb), float(cfg_scale) if guided else 1.0, _C.ptr(zr),
+                                                            int(resample), int(jump_length), _C.stream_of(X))
+                X = X[:rows]
+            elif guided:
                 yb = None if labels is None else labels[lo:lo + nb].repeat_interleave(reps).contiguous()
                 X = self._cfg_state(X, pair)
                 if dps:
@@ -562,13 +592,35 @@ class DiffusionSampler:
             out.append(X if num_samples is None else X.view(nb, reps, *X.shape[1:]))
         return torch.cat([x.cpu() for x in out], dim=0)
 
+    @staticmethod
+    def repaint_schedule(N: int, resample: int = 1, jump_length: int = 1) -> list:
+        """The execution order of ``impute(resample=r, jump_length=j)`` over an N-step grid: ("step", i) for reverse step i with
+        its projection at level i + 1, and ("renoise", i1, i0) for the forward transition from level i1 back to level i0 (level N
+        is the clean one).  The steps are cut into blocks [i0, min(i0 + j, N)); a block runs r times, with a re-noise between two
+        runs.  r N steps and (r - 1) ceil(N / j) re-noises; r = 1: the steps 0 .. N-1 alone."""
+        for name, v in (("N", N), ("resample", resample), ("jump_length", jump_length)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"repaint_schedule: {name} must be an int >= 1, got {v!r}")
+        ops = []
+        for i0 in range(0, N, jump_length):
+            i1 = min(i0 + jump_length, N)
+            for rep in range(resample):
+                ops += [("step", i) for i in range(i0, i1)]
+                if rep + 1 < resample:
+                    ops.append(("renoise", i1, i0))
+        return ops
+
     def impute_project(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: Optional[float] = None, *,
                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None,
-                       noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       noise: Optional[torch.Tensor] = None, renoise_to: Optional[float] = None,
+                       renoise_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The projection of ``impute`` alone (its step-wise twin, as ``reverse_diffusion_step`` is ``sample``'s): X (B,T,C) in
         sample space -> A^-1(m A(x_obs) + (1 - m) A(X)), x_obs = alpha x0_obs + s G z with (alpha, s) the perturbation kernel at
         ``timestep`` (None: alpha = 1, s = 0, the exact projection).  x0_obs from ``observed_to_sample_space``; noise: injected
-        z (B,T,C) or None (Philox).  Returns a new device tensor."""
+        z (B,T,C) or None (Philox).  renoise_to = t' (>= ``timestep``): the projected state is then diffused forward from the level
+        of ``timestep`` (None: the clean level) to t' in the same kernel (fd_impute_project_renoise), x <- a x + b G z_r with the
+        transition kernel a = alpha(t') / alpha, b = sqrt(s(t')^2 - a^2 s^2); renoise_noise: injected z_r (B,T,C) or None (Philox,
+        its own stream).  Returns a new device tensor."""
         xd = _C.dev_f32(X.to(self.score_model.device), "X")
         x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
         if x0.shape != xd.shape or xd.dim() != 3:
@@ -583,9 +635,29 @@ class DiffusionSampler:
         sch = self.noise_scheduler
         alpha, sdev = (1.0, 0.0) if timestep is None else sch.marginal_coef(timestep)
         z = None if noise is None else self._noise(noise, (), "noise", B)
-        key, off = (0, 0) if (z is not None or sdev == 0.0) else _rng.stream()
+        zr = None if renoise_noise is None else self._noise(renoise_noise, (), "renoise_noise", B)
+        # one Philox key per call, drawn only when a stream is needed; the re-noise counters lie behind the observation noise's
+        key, off = (0, 0) if ((z is not None or sdev == 0.0) and (zr is not None or renoise_to is None)) else _rng.stream()
         out = torch.empty_like(xd)
         h = _C.ctx(xd.device)
+        if renoise_to is None:
+            if renoise_noise is not None:
+                raise ValueError("impute_project: renoise_noise is only read with renoise_to")
+        else:
+            if isinstance(renoise_to, bool) or not isinstance(renoise_to, (int, float)) or not math.isfinite(renoise_to):
+                raise ValueError(f"impute_project: renoise_to must be a finite number, got {renoise_to!r}")
+            a_hi, s_hi = sch.marginal_coef(renoise_to)
+            ra = a_hi / alpha
+            rad = s_hi * s_hi - ra * ra * sdev * sdev
+            if rad < -1e-12:
+                raise ValueError(f"impute_project: renoise_to={renoise_to!r} lies below the level of timestep={timestep!r}")
+            off_r = off + (xd.numel() + 3) // 4
+            rc = _C.lib().fd_impute_project_renoise(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
+                                                    int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha),
+                                                    float(sdev), _C.ptr(z), key, off, float(ra), math.sqrt(max(rad, 0.0)),
+                                                    _C.ptr(zr), off_r, out.data_ptr(), B, T, Cn, _C.stream_of(xd))
+            _C.check(rc, h)
+            return out
         rc = _C.lib().fd_impute_project(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
                                         int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha), float(sdev),
                                         _C.ptr(z), key, off, out.data_ptr(), B, T, Cn, _C.stream_of(xd))

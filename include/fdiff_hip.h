@@ -391,6 +391,31 @@ int fd_sampler_run_impute_cfg(fd_score* m, const fd_sde_params* sde, const float
                               float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                               const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
                               uint64_t offset, int B, int obs_replicas, int mode, const int32_t* y, float cfg_scale, void* stream);
+/* RePaint resampling of the replacement loop (Lugmayr et al. 2022): the n_steps steps are cut into consecutive blocks [i0, i1),
+ * i1 = min(i0 + jump_length, n_steps); every block is executed `resample` times before the next one starts, and between two
+ * executions the state is diffused forward from level i1 back to level i0 by the transition kernel x <- a x + b G z, with (alpha, s)
+ * of marginal_prob at timesteps[i] (level n_steps: the clean one, alpha = 1, s = 0), a = alpha(i0) / alpha(i1) and
+ * b = sqrt(s(i0)^2 - a^2 s(i1)^2), in double on the host.  The re-noise is fused into the last step's kernel of the execution (no
+ * launch and no pass over the state is added).  E = resample * n_steps score evaluations, K = (resample - 1) * ceil(n_steps /
+ * jump_length) re-noises; resample = 1 is fd_sampler_run_impute_cfg for every jump_length, to the bit.
+ *   fd_sampler_run_impute_repaint: the arguments of fd_sampler_run_impute_cfg and zre_steps, resample, jump_length.  y == NULL and
+ *                          cfg_scale == 1: the unguided loop (fd_sampler_run_impute_rep; any model), otherwise the rules of
+ *                          fd_sampler_run_impute_cfg (a paired call takes x (2B,T,C)).  Philox (seed), per = ceil(BTC/4): predictor
+ *                          noise of executed step e at offset + e*per + el/4, observation noise at offset + (E + e)*per + el/4,
+ *                          re-noise k at offset + (2E + k)*per + el/4.  z_steps, zobs_steps (E,B,T,C) and zre_steps (K,B,T,C): injected
+ *                          noise in execution order, or NULL (each on its own).
+ *   fd_impute_project_renoise: fd_impute_project followed by out <- a out + b G z_re in the same kernel (the loop's fused kernel
+ *                          without the step); z_re == NULL -> Philox (seed; element e at offset_re + e/4).  a, b finite, b >= 0;
+ *                          a = 1, b = 0 gives fd_impute_project to the bit. */
+int fd_impute_project_renoise(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                              const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
+                              uint64_t seed, uint64_t offset, float a, float b, const float* z_re, uint64_t offset_re, float* out,
+                              int B, int T, int C, void* stream);
+int fd_sampler_run_impute_repaint(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                  float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                  const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
+                                  uint64_t offset, int B, int obs_replicas, int mode, const int32_t* y, float cfg_scale,
+                                  const float* zre_steps, int resample, int jump_length, void* stream);
 
 /* Gradient-guided conditional sampling extension (NOT in the reference; diffusion posterior sampling, Chung et al. 2023, and
  * TSDiff's observation self-guidance, Kollovieh et al. 2023).  The state is never overwritten; every reverse step is nudged along
