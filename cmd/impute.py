@@ -9,7 +9,10 @@ place of the MSE / MAE.  conditioning=dps (guidance.scale, guidance.jacobian) re
 keys are then recorded in the `impute` block.  labels=data|<int> (class-conditional models) conditions every series on its test label
 (`datamodule.y_test`) or on one class, cfg_scale=w sets the classifier-free guidance scale; both are recorded only when set.
 resample=r jump_length=j (conditioning=replace) turn on RePaint resampling: every block of j steps runs r times with a forward re-noise
-between two runs, r * num_diffusion_steps score evaluations; both are recorded when they are not 1.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+between two runs, r * num_diffusion_steps score evaluations; both are recorded when they are not 1.  aggregate=w > 1 conditions on
+WINDOW MEANS instead (temporal super-resolution): mask.* is read in windows of w time steps (mask.horizon counts windows), the
+observation is the window means of the test split, every full-resolution entry counts as hidden in the scores, and results.yaml records
+`aggregate` and `max_abs_err_window_means`, the largest deviation of the result's window means over the observed windows.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -26,7 +29,7 @@ from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
 from fourierdiffusion_amd.sampling.forecast import ensemble_scores  # noqa: E402
-from fourierdiffusion_amd.sampling.masks import observation_mask  # noqa: E402
+from fourierdiffusion_amd.sampling.masks import observation_mask, window_means  # noqa: E402
 from fourierdiffusion_amd.sampling.sampler import series_labels  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
@@ -94,6 +97,7 @@ class ImputationRunner:
         self.cfg_scale = float(cfg.get("cfg_scale", 1.0))
         self.resample = int(cfg.get("resample", 1))
         self.jump_length = int(cfg.get("jump_length", 1))
+        self.aggregate = int(cfg.get("aggregate", 1))
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
         self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path,
@@ -110,9 +114,14 @@ class ImputationRunner:
         K = self.num_samples
         # the mask from its own generator: every rank builds the same one, and torch's global generator (the Philox keys) is untouched
         gen = torch.Generator().manual_seed(self.random_seed)
-        mask = observation_mask(self.mask_cfg.kind, tuple(truth.shape), p=float(self.mask_cfg.get("p", 0.5)),
+        w = self.aggregate
+        if not 1 <= w <= int(truth.shape[1]):
+            raise ValueError(f"aggregate must lie in [1, {int(truth.shape[1])}], got {w}")
+        coarse = truth if w == 1 else window_means(truth, w)                        # (n, J, C): what is observed, and its mask
+        mask = observation_mask(self.mask_cfg.kind, tuple(coarse.shape), p=float(self.mask_cfg.get("p", 0.5)),
                                 horizon=int(self.mask_cfg.get("horizon", 1)), generator=gen)
-        observed = truth.masked_fill(~mask, float("nan"))                          # the sampler never sees a hidden entry
+        observed = coarse.masked_fill(~mask, float("nan"))                         # the sampler never sees a hidden entry
+        agg = {} if w == 1 else dict(aggregate=w)
         lo, hi = shard_range(int(truth.shape[0]), self.dist.rank, self.dist.world)  # independent rows: no exchange
         y = series_labels(self.labels, self.datamodule, int(truth.shape[0]), int(getattr(self.score_model, "n_classes", 0)))
         guided = {} if (y is None and self.cfg_scale == 1.0) else dict(y=None if y is None else y[lo:hi], cfg_scale=self.cfg_scale)
@@ -125,7 +134,7 @@ class ImputationRunner:
             X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
                                     feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K,
                                     conditioning=self.conditioning, guidance_scale=self.guidance_scale,
-                                    guidance_jacobian=self.guidance_jacobian, **guided, **repaint)
+                                    guidance_jacobian=self.guidance_jacobian, **guided, **repaint, **agg)
             shape = X.shape
             X = X.reshape(-1, *shape[-2:])                                          # (rows, T, C) for the maps back
             if std is not None:
@@ -142,8 +151,15 @@ class ImputationRunner:
             results_path = self.save_dir / "results.yaml"
             results = yaml.safe_load(open(results_path)) if results_path.exists() else None
             results = results if isinstance(results, dict) else {}
-            scores = hidden_errors(X, truth, mask) if K == 1 else ensemble_results(X, truth, mask)
+            # window means: no full-resolution entry was observed, so the scores run over all of them
+            fine = mask if w == 1 else torch.zeros(truth.shape, dtype=torch.bool)
+            scores = hidden_errors(X, truth, fine) if K == 1 else ensemble_results(X, truth, fine)
             results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **scores}
+            if w > 1:
+                results["impute"]["aggregate"] = w
+                if mask.any():
+                    dev = (window_means(X.double(), w) - (coarse.double() if K == 1 else coarse.double()[:, None])).abs()
+                    results["impute"]["max_abs_err_window_means"] = float(dev[(mask if K == 1 else mask[:, None]).expand_as(dev)].max())
             if self.conditioning != "replace":
                 results["impute"].update(conditioning=self.conditioning, guidance_scale=self.guidance_scale,
                                          guidance_jacobian=self.guidance_jacobian)

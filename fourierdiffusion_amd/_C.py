@@ -130,6 +130,15 @@ _PROTOS = {
     "fd_sampler_run_impute_dps_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                                 _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                                 C.c_int, _vp, C.c_float, _vp]),
+    "fd_impute_project_agg": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_float, _vp, C.c_uint64,
+                                        C.c_uint64, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_impute_agg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                            _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_impute_guidance_agg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int,
+                                         _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_impute_dps_agg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                                _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, _vp]),
     "fd_pf_ode_drift": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_dpm": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),

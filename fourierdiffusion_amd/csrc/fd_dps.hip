@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "fd_aggregate.h"
 #include "fd_common.h"
 #include "fd_engine.h"
 #include "fd_loop.h"
@@ -351,7 +352,7 @@ int launch_step(fd_ctx* ctx, const StepArgs& a, const fd_guide* g, hipStream_t s
 // Jacobian, else the sampler's forward), the residual of the B state rows, and the VJP; leaves score, u, dx and the block sums in
 // the buffers
 int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, int R, const fd_guide* g, bool jac, bool fourier,
-             int mode, hipStream_t s) {
+             int mode, hipStream_t s, const fd_agg_plan* ag = nullptr) {
     fd_ctx* ctx = m->ctx;
     if (jac) {
         if (int rc = fd_score_forward_train(m, x, bf.tvec, bf.score, R, 0.f, 0, 0, s)) return rc;
@@ -360,7 +361,15 @@ int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, 
     }
     r.x = x;
     r.score = bf.score;
-    if (g) {
+    if (ag) {        // window means (fd_aggregate.hip): r.mask is (B/obs_rep,J,C) or (J,C)
+        fd_agg_res_args ra{};
+        ra.x = r.x; ra.score = r.score; ra.x0 = r.x0; ra.mask = r.mask; ra.stdv = r.stdv; ra.G = r.G;
+        ra.u = r.u; ra.dout = r.dout; ra.part = r.part;
+        ra.T = r.T; ra.C = r.C; ra.Tp = r.Tp; ra.ncb = r.ncb; ra.mask_per_series = r.mask_per_series; ra.obs_rep = r.obs_rep;
+        ra.alpha = r.alpha; ra.s2 = r.s2;
+        ra.p = *ag;
+        if (int rc = fd_agg_launch_residual(ctx, ra, B, fourier, s)) return rc;
+    } else if (g) {
         ResArgsPair rp{};
         static_cast<ResArgs&>(rp) = r;
         rp.half = (size_t)B * r.T * r.C;
@@ -378,12 +387,18 @@ int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, 
 // the body of fd_impute_guidance (g == null) and fd_impute_guidance_cfg, the arguments checked under the name `who`
 int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
                  const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian, float* g_out,
-                 double* rnorm2_out, int B, int obs_replicas, int mode, hipStream_t s, const fd_guide* g, const char* who) {
+                 double* rnorm2_out, int B, int obs_replicas, int mode, hipStream_t s, const fd_guide* g, const char* who,
+                 int window = 1) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, g_out && rnorm2_out, "%s: null pointer", who);
     FD_REQUIRE(ctx, std::isfinite(t) && t > 0.f, "%s: t=%g must be finite and > 0", who, (double)t);
     ResArgs r{};
     if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
+    fd_agg_plan agg{};
+    if (window > 1) {
+        FD_REQUIRE(ctx, !g, "%s: window=%d goes with no guide", who, window);
+        if (int rc = fd_agg_prepare(ctx, r.T, r.Tp, window, fourier, s, &agg, who)) return rc;
+    }
     const bool jac = jacobian != 0, pair = g && g->pair;
     const size_t n = (size_t)B * r.T * r.C;
     const int R = fd_guide_rows(g, B);
@@ -403,7 +418,7 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
     fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
     fd_label_dropout_scope ld(m, 0.f);
     fd_fill(bf.tvec, R, t, s);
-    if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s)) return rc;
+    if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
     StepArgs a{};
     a.G = G; a.u = bf.u; a.dx = bf.dx; a.part = bf.part; a.gout = g_out; a.rn2_out = rnorm2_out;
     a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
@@ -415,7 +430,7 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
 int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
              const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
              float guidance_scale, int jacobian, const float* z_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
-             hipStream_t s, const fd_guide* g, const char* who) {
+             hipStream_t s, const fd_guide* g, const char* who, int window = 1) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, timesteps, "%s: null pointer", who);
     FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
@@ -424,6 +439,11 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
                (double)guidance_scale);
     ResArgs r{};
     if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
+    fd_agg_plan agg{};
+    if (window > 1) {
+        FD_REQUIRE(ctx, !g, "%s: window=%d goes with no guide", who, window);
+        if (int rc = fd_agg_prepare(ctx, r.T, r.Tp, window, fourier, s, &agg, who)) return rc;
+    }
     const bool jac = jacobian != 0, pair = g && g->pair;
     const size_t n = (size_t)B * r.T * r.C;
     const int R = fd_guide_rows(g, B);
@@ -455,7 +475,7 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
         fd_fill(bf.tvec, R, timesteps[i], s);
         r.alpha = al[i];
         r.s2 = s2[i];
-        if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s)) return rc;
+        if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
         a.zin = z_steps ? z_steps + (size_t)i * n : nullptr;
         a.cf = cf[i];
         a.alpha = al[i];
@@ -473,6 +493,37 @@ extern "C" int fd_impute_guidance(fd_score* m, const fd_sde_params* sde, const f
     if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance")) return rc;
     return dps_guidance(m, sde, G, t, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, jacobian, g_out, rnorm2_out, B,
                         obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_impute_guidance");
+}
+
+// fd_impute_guidance and fd_sampler_run_impute_dps on window means: mask_u8 (B/obs_replicas,J,C) or (J,C), J = ceil(T / window), the
+// residual r (J,C) per row; window = 1 is the call without it
+extern "C" int fd_impute_guidance_agg(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x,
+                                      const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
+                                      int fourier, int jacobian, float* g_out, double* rnorm2_out, int B, int obs_replicas, int window,
+                                      int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance_agg")) return rc;
+    FD_REQUIRE(m->ctx, window >= 1 && window <= m->d.max_len, "fd_impute_guidance_agg: window=%d must lie in [1, max_len=%d]", window,
+               m->d.max_len);
+    if (window == 1)
+        return fd_impute_guidance(m, sde, G, t, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, jacobian, g_out, rnorm2_out, B,
+                                  obs_replicas, mode, stream);
+    return dps_guidance(m, sde, G, t, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, jacobian, g_out, rnorm2_out, B,
+                        obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_impute_guidance_agg", window);
+}
+
+extern "C" int fd_sampler_run_impute_dps_agg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                             int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                             int mask_per_series, const float* feat_std, int fourier, float guidance_scale,
+                                             int jacobian, const float* z_steps, uint64_t seed, uint64_t offset, int B,
+                                             int obs_replicas, int window, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_dps_agg")) return rc;
+    FD_REQUIRE(m->ctx, window >= 1 && window <= m->d.max_len, "fd_sampler_run_impute_dps_agg: window=%d must lie in [1, max_len=%d]",
+               window, m->d.max_len);
+    if (window == 1)
+        return fd_sampler_run_impute_dps(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier,
+                                         guidance_scale, jacobian, z_steps, seed, offset, B, obs_replicas, mode, stream);
+    return dps_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, guidance_scale, jacobian,
+                    z_steps, seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_dps_agg", window);
 }
 
 // fd_impute_guidance on a class-conditional model under classifier-free guidance: y (B) one label per row or null, w the scale;

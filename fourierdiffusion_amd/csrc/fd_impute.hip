@@ -29,6 +29,7 @@
 #include <cmath>
 #include <vector>
 
+#include "fd_aggregate.h"
 #include "fd_common.h"
 #include "fd_engine.h"
 #include "fd_loop.h"
@@ -320,6 +321,20 @@ int launch_pair(fd_ctx* ctx, const ImpArgs& a, const fd_guide& g, bool fourier, 
     return fourier ? launch_variant<true, true, true>(ctx, ap, lds, s) : launch_variant<true, false, true>(ctx, ap, lds, s);
 }
 
+// window means (fd_aggregate.hip): the fields of `a` under the window geometry p; a.mask is (B/obs_rep,J,C) or (J,C), stdv is read in
+// both domains
+int launch_agg(fd_ctx* ctx, const ImpArgs& a, const fd_agg_plan& p, const float* stdv, bool step, bool fourier, hipStream_t s) {
+    fd_agg_imp_args g{};
+    g.x = a.x; g.score = a.score; g.zstep = a.zstep; g.x0 = a.x0; g.mask = a.mask; g.stdv = stdv; g.G = a.G; g.zobs = a.zobs;
+    g.out = a.out;
+    g.B = a.B; g.T = a.T; g.C = a.C; g.Tp = a.Tp; g.ncb = a.ncb; g.mask_per_series = a.mask_per_series; g.obs_rep = a.obs_rep;
+    g.cf = a.cf;
+    g.alpha = a.alpha; g.s = a.s;
+    g.seed = a.seed; g.off_step = a.off_step; g.off_obs = a.off_obs;
+    g.p = p;
+    return fd_agg_launch_impute(ctx, g, step, fourier, s);
+}
+
 // (alpha, s) of level i of an n-step grid: the perturbation kernel at timesteps[i], the clean level (1, 0) at i = n
 void level_coef(const fd_sde_params& sde, const float* timesteps, int n_steps, int i, double* alpha, double* sdev) {
     *alpha = 1.0;
@@ -336,7 +351,7 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
                 const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
                 const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
                 hipStream_t s, const fd_guide* g, const char* who, const float* zre_steps = nullptr, int resample = 1,
-                int jump_length = 1) {
+                int jump_length = 1, int window = 1) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, G && timesteps && x, "%s: null pointer", who);
     FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
@@ -348,6 +363,12 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
     ImpArgs a{};
     if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, who)) return rc;
     a.obs_rep = obs_replicas;
+    // window > 1: the mask holds windows and fd_aggregate.hip's kernel takes the place of k_impute (no guide and no RePaint there)
+    fd_agg_plan agg{};
+    if (window > 1) {
+        FD_REQUIRE(ctx, !g && resample == 1, "%s: window=%d goes with neither a guide nor resample > 1", who, window);
+        if (int rc = fd_agg_prepare(ctx, T, a.Tp, window, fourier, s, &agg, who)) return rc;
+    }
     // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
     // at the next grid point; the last step projects hard (alpha = 1, s = 0)
     std::vector<SdeCoef> cf(n_steps);
@@ -415,6 +436,10 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
             a.off_re = offset + ((uint64_t)2 * E + (uint64_t)k) * per_step;
             ++k;
         }
+        if (window > 1) {
+            if (int rc = launch_agg(ctx, a, agg, feat_std, true, fourier != 0, s)) return rc;
+            continue;
+        }
         if (int rc = pair ? launch_pair(ctx, a, *g, fourier != 0, s, renoise) : launch(ctx, a, true, fourier != 0, s, renoise)) return rc;
     }
     return FD_OK;
@@ -469,6 +494,27 @@ extern "C" int fd_impute_project(fd_ctx* ctx, const float* x, const float* x0_ob
     return launch(ctx, a, false, fourier != 0, hs);
 }
 
+extern "C" int fd_impute_project_agg(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                     const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
+                                     uint64_t seed, uint64_t offset, float* out, int B, int T, int C, int window, void* stream) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, window >= 1 && window <= T, "fd_impute_project_agg: window=%d must lie in [1, T=%d]", window, T);
+    if (window == 1)
+        return fd_impute_project(ctx, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, alpha, s, z, seed, offset, out, B, T, C,
+                                 stream);
+    FD_REQUIRE(ctx, x && out, "fd_impute_project_agg: null pointer");
+    hipStream_t hs = (hipStream_t)stream;
+    ImpArgs a{};
+    if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, hs, "fd_impute_project_agg")) return rc;
+    fd_agg_plan agg{};
+    if (int rc = fd_agg_prepare(ctx, T, a.Tp, window, fourier, hs, &agg, "fd_impute_project_agg")) return rc;
+    a.x = x; a.out = out;
+    a.zobs = z;
+    a.alpha = alpha; a.s = s;
+    a.seed = seed; a.off_obs = offset;
+    return launch_agg(ctx, a, agg, feat_std, false, fourier != 0, hs);
+}
+
 extern "C" int fd_impute_project_renoise(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                                          const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
                                          uint64_t seed, uint64_t offset, float a, float b, const float* z_re, uint64_t offset_re,
@@ -499,6 +545,23 @@ extern "C" int fd_sampler_run_impute_rep(fd_score* m, const fd_sde_params* sde, 
     if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute")) return rc;
     return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
                        seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute");
+}
+
+// fd_sampler_run_impute_rep on window means: mask_u8 (B/obs_replicas,J,C) or (J,C), J = ceil(T / window); window = 1 is that call
+extern "C" int fd_sampler_run_impute_agg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                         int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                         int mask_per_series, const float* feat_std, int fourier, const float* z_steps,
+                                         const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int window,
+                                         int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_agg")) return rc;
+    FD_REQUIRE(m->ctx, window >= 1 && window <= m->d.max_len, "fd_sampler_run_impute_agg: window=%d must lie in [1, max_len=%d]", window,
+               m->d.max_len);
+    if (window == 1)
+        return fd_sampler_run_impute_rep(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier,
+                                         z_steps, zobs_steps, seed, offset, B, obs_replicas, mode, stream);
+    return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
+                       seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_agg", nullptr, 1, 1,
+                       window);
 }
 
 // fd_sampler_run_impute_rep on a class-conditional model under classifier-free guidance: y (B) one label per state row or null,

@@ -467,8 +467,8 @@ class DiffusionSampler:
                prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
                obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None,
                conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True,
-               resample: int = 1, jump_length: int = 1, renoise_noise: Optional[Sequence[torch.Tensor]] = None, y=None,
-               cfg_scale: float = 1.0) -> torch.Tensor:
+               resample: int = 1, jump_length: int = 1, renoise_noise: Optional[Sequence[torch.Tensor]] = None,
+               aggregate: int = 1, y=None, cfg_scale: float = 1.0) -> torch.Tensor:
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
         it back with the caller's destandardise / idft), one series per row of ``observed``.  ``num_samples`` = K >= 1: an
         ensemble of K samples per series instead, (n, K, max_len, n_channels); a launch holds max(1, sample_batch_size // K)
@@ -505,7 +505,22 @@ class DiffusionSampler:
         E = r N score evaluations and K = (r - 1) ceil(N / j) re-noises, each fused into the kernel of the step before it
         (fd_sampler_run_impute_repaint).  With r > 1, step_noise[b] / obs_noise[b] are (E,nb,T,C) in execution order and
         renoise_noise[b] is (K,nb,T,C); the Philox stream is used only when all of them are absent.  r = 1 is the call without the
-        arguments for every j, to the bit (renoise_noise is an error there)."""
+        arguments for every j, to the bit (renoise_noise is an error there).
+
+        aggregate = w > 1 (1 <= w <= max_len): the observations are WINDOW MEANS, a series reported at a w times coarser rate
+        (temporal super-resolution, disaggregation; forecasting from a coarse history with a mask over windows).  With
+        J = ceil(T / w) windows, window j = [j w, min((j + 1) w, T)) (the last one may be shorter), ``observed`` is (n, J, C), the
+        window means at data scale (``masks.window_means``), and ``mask`` is bool (n, J, C) or (J, C): True = the mean of that
+        window is observed.  Under "replace" the projection becomes the one onto {x : P A(x) = y} (P the window-mean operator), and
+        the window means of the result reproduce ``observed`` on the observed windows up to f32 rounding; under "dps" the residual
+        is the one of the window means (fd_sampler_run_impute_agg, fd_sampler_run_impute_dps_agg).  ``feature_std`` is read in both
+        domains (it varies inside a window).  Ensembles and both Jacobian modes work; y / cfg_scale and resample > 1 do not
+        (ValueError), and max_len <= 1024.  aggregate=1: the call without the argument, to the bit."""
+        self._check_aggregate(aggregate, "impute")
+        if aggregate > 1 and (y is not None or cfg_scale != 1.0):
+            raise ValueError("impute: aggregate > 1 is not supported with y / cfg_scale (classifier-free guidance)")
+        if aggregate > 1 and isinstance(resample, int) and resample > 1:
+            raise ValueError("impute: aggregate > 1 is not supported with resample > 1 (RePaint)")
         guided, pair = self._guided(y, cfg_scale)
         for name, v in (("resample", resample), ("jump_length", jump_length)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
@@ -528,11 +543,12 @@ class DiffusionSampler:
         dps = conditioning == "dps"
         if dps and obs_noise is not None:
             raise ValueError("impute: obs_noise is not used by conditioning='dps' (no observation is noised)")
-        obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
+        obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, aggregate)
         self.score_model.eval()
         N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
         ctx, h, p, G, mode = self._engine_args()
-        fstd = std if (fourier_transform or dps) else None      # (the guidance weighs the residual by sigma in both domains)
+        # (the guidance weighs the residual by sigma in both domains, and sigma varies inside a window)
+        fstd = std if (fourier_transform or dps or aggregate > 1) else None
         reps = 1 if num_samples is None else int(num_samples)
         n, bs = obs.shape[0], max(1, self.sample_batch_size // ((2 if pair else 1) * reps))
         labels = self._series_labels(y, n, "impute") if guided else None
@@ -550,8 +566,20 @@ class DiffusionSampler:
             zr = None if renoise_noise is None else self._noise(renoise_noise[b], (K, rows), "renoise_noise")
             key, off = (0, 0) if (z is not None and (zo is not None or dps) and (zr is not None or K == 0)) else _rng.stream()
             m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
-            x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
-            if resample > 1:
+            x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std, aggregate, self.max_len)
+            if aggregate > 1:
+                if dps:
+                    rc = _C.lib().fd_sampler_run_impute_dps_agg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(),
+                                                                x0.data_ptr(), m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                                int(bool(fourier_transform)), float(guidance_scale),
+                                                                int(guidance_jacobian), _C.ptr(z), key, off, rows, reps,
+                                                                int(aggregate), mode, _C.stream_of(X))
+                else:
+                    rc = _C.lib().fd_sampler_run_impute_agg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                            m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                            int(bool(fourier_transform)), _C.ptr(z), _C.ptr(zo), key, off, rows, reps,
+                                                            int(aggregate), mode, _C.stream_of(X))
+            elif resample > 1:
                 yb = None if labels is None else labels[lo:lo + nb].repeat_interleave(reps).contiguous()
                 X = self._cfg_state(X, pair)
                 rc = _C.lib().fd_sampler_run_impute_repaint(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
@@ -613,22 +641,27 @@ class DiffusionSampler:
     def impute_project(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: Optional[float] = None, *,
                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None,
                        noise: Optional[torch.Tensor] = None, renoise_to: Optional[float] = None,
-                       renoise_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       renoise_noise: Optional[torch.Tensor] = None, aggregate: int = 1) -> torch.Tensor:
         """The projection of ``impute`` alone (its step-wise twin, as ``reverse_diffusion_step`` is ``sample``'s): X (B,T,C) in
         sample space -> A^-1(m A(x_obs) + (1 - m) A(X)), x_obs = alpha x0_obs + s G z with (alpha, s) the perturbation kernel at
         ``timestep`` (None: alpha = 1, s = 0, the exact projection).  x0_obs from ``observed_to_sample_space``; noise: injected
         z (B,T,C) or None (Philox).  renoise_to = t' (>= ``timestep``): the projected state is then diffused forward from the level
         of ``timestep`` (None: the clean level) to t' in the same kernel (fd_impute_project_renoise), x <- a x + b G z_r with the
         transition kernel a = alpha(t') / alpha, b = sqrt(s(t')^2 - a^2 s^2); renoise_noise: injected z_r (B,T,C) or None (Philox,
-        its own stream).  Returns a new device tensor."""
+        its own stream).  aggregate = w > 1: the projection on window means (fd_impute_project_agg), mask (B, J, C) or (J, C) over
+        the J = ceil(T / w) windows, x0_obs from ``observed_to_sample_space(aggregate=w)``, feature_std read in both domains; not
+        with renoise_to.  Returns a new device tensor."""
+        self._check_aggregate(aggregate, "impute_project", int(X.shape[1]) if isinstance(X, torch.Tensor) and X.dim() == 3 else None)
+        if aggregate > 1 and (renoise_to is not None or renoise_noise is not None):
+            raise ValueError("impute_project: aggregate > 1 is not supported with renoise_to (RePaint)")
         xd = _C.dev_f32(X.to(self.score_model.device), "X")
         x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
         if x0.shape != xd.shape or xd.dim() != 3:
             raise ValueError(f"impute_project: X {tuple(xd.shape)} and x0_obs {tuple(x0.shape)} must be the same (B,T,C) shape")
         B, T, Cn = xd.shape
-        m_u8, per_series = self._mask_u8(mask, B, T, Cn, xd.device)
+        m_u8, per_series = self._mask_u8(mask, B, -(-T // aggregate), Cn, xd.device)
         std = None
-        if fourier_transform and feature_std is not None:
+        if (fourier_transform or aggregate > 1) and feature_std is not None:
             std = _C.dev_f32(feature_std.to(xd.device), "feature_std")
             if tuple(std.shape) != (T, Cn):
                 raise ValueError(f"impute_project: feature_std must have shape {(T, Cn)}, got {tuple(std.shape)}")
@@ -658,6 +691,13 @@ class DiffusionSampler:
                                                     _C.ptr(zr), off_r, out.data_ptr(), B, T, Cn, _C.stream_of(xd))
             _C.check(rc, h)
             return out
+        if aggregate > 1:
+            rc = _C.lib().fd_impute_project_agg(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
+                                                int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha),
+                                                float(sdev), _C.ptr(z), key, off, out.data_ptr(), B, T, Cn, int(aggregate),
+                                                _C.stream_of(xd))
+            _C.check(rc, h)
+            return out
         rc = _C.lib().fd_impute_project(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
                                         int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha), float(sdev),
                                         _C.ptr(z), key, off, out.data_ptr(), B, T, Cn, _C.stream_of(xd))
@@ -665,15 +705,21 @@ class DiffusionSampler:
         return out
 
     def impute_guidance(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: float, *,
-                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None, jacobian: bool = True, y=None,
-                        cfg_scale: float = 1.0) -> tuple:
+                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None, jacobian: bool = True,
+                        aggregate: int = 1, y=None, cfg_scale: float = 1.0) -> tuple:
         """One guidance evaluation of ``impute(conditioning="dps")`` alone (fd_impute_guidance): X (B,T,C) in sample space at
         ``timestep`` -> (g, rnorm2), g = -grad_X ||r||^2 (B,T,C) float32 and rnorm2 = ||r||^2 per row (B,) float64, both on the
         device.  x0_obs from ``observed_to_sample_space``; feature_std: the datamodule's std when it standardises (used in both
         domains), else None.  jacobian=False: the Jacobian-free gradient (the score from the sampler's forward).
         y, cfg_scale (class-conditional models only; ValueError otherwise): one label per row (an int, or an integer tensor (B,)) and
         the classifier-free guidance scale w -- the guidance of the guided score w s(x, t, y) + (1 - w) s(x, t, null), its Jacobian
-        w J_c + (1 - w) J_u (fd_impute_guidance_cfg); g and rnorm2 for the B rows."""
+        w J_c + (1 - w) J_u (fd_impute_guidance_cfg); g and rnorm2 for the B rows.
+        aggregate = w > 1: the residual of the window means (fd_impute_guidance_agg), mask (B, J, C) or (J, C) over the
+        J = ceil(T / w) windows, x0_obs from ``observed_to_sample_space(aggregate=w)``, rnorm2 the sum over windows; not with y /
+        cfg_scale."""
+        self._check_aggregate(aggregate, "impute_guidance")
+        if aggregate > 1 and (y is not None or cfg_scale != 1.0):
+            raise ValueError("impute_guidance: aggregate > 1 is not supported with y / cfg_scale (classifier-free guidance)")
         guided, _pair = self._guided(y, cfg_scale)
         T, Cn = self.max_len, self.n_channels
         if not (isinstance(X, torch.Tensor) and isinstance(x0_obs, torch.Tensor)) or x0_obs.shape != X.shape or X.dim() != 3 \
@@ -684,7 +730,7 @@ class DiffusionSampler:
         if feature_std is not None and tuple(feature_std.shape) != (T, Cn):
             raise ValueError(f"impute_guidance: feature_std must have shape {(T, Cn)}, got {tuple(feature_std.shape)}")
         B = X.shape[0]
-        m_u8, per_series = self._mask_u8(mask, B, T, Cn, self.score_model.device)
+        m_u8, per_series = self._mask_u8(mask, B, -(-T // aggregate), Cn, self.score_model.device)
         xd = _C.dev_f32(X.to(self.score_model.device), "X")
         x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
         std = None if feature_std is None else _C.dev_f32(feature_std.to(xd.device), "feature_std")
@@ -700,6 +746,13 @@ class DiffusionSampler:
                                                  float(cfg_scale), _C.stream_of(xd))
             _C.check(rc, ctx)
             return g, rn2
+        if aggregate > 1:
+            rc = _C.lib().fd_impute_guidance_agg(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(),
+                                                 m_u8.data_ptr(), int(per_series), _C.ptr(std), int(bool(fourier_transform)),
+                                                 int(bool(jacobian)), g.data_ptr(), rn2.data_ptr(), B, 1, int(aggregate), mode,
+                                                 _C.stream_of(xd))
+            _C.check(rc, ctx)
+            return g, rn2
         rc = _C.lib().fd_impute_guidance(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(),
                                          int(per_series), _C.ptr(std), int(bool(fourier_transform)), int(bool(jacobian)),
                                          g.data_ptr(), rn2.data_ptr(), B, 1, mode, _C.stream_of(xd))
@@ -708,21 +761,32 @@ class DiffusionSampler:
 
     def observed_to_sample_space(self, observed: torch.Tensor, mask: torch.Tensor, *, fourier_transform: bool,
                                  feature_mean: Optional[torch.Tensor] = None,
-                                 feature_std: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x0_obs = A^-1(where(mask, observed, 0)) on the device (what ``impute`` conditions on; the input of ``impute_project``)."""
-        obs, mask_u8, _, mean, std = self._conditioning(observed, mask, feature_mean, feature_std)
-        return self._x0_obs(obs, mask_u8, fourier_transform, mean, std)
+                                 feature_std: Optional[torch.Tensor] = None, aggregate: int = 1) -> torch.Tensor:
+        """x0_obs = A^-1(where(mask, observed, 0)) on the device (what ``impute`` conditions on; the input of ``impute_project``).
+        aggregate = w > 1: observed and mask over the J = ceil(T / w) windows, x0_obs = A^-1(P^+ where(mask, observed, 0)) (n, T, C),
+        P^+ the piecewise-constant lift."""
+        self._check_aggregate(aggregate, "observed_to_sample_space")
+        obs, mask_u8, _, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, aggregate)
+        return self._x0_obs(obs, mask_u8, fourier_transform, mean, std, aggregate, self.max_len)
 
-    def _conditioning(self, observed, mask, feature_mean, feature_std):
-        """Validated device copies: observed (n,T,C) f32, mask as uint8 (n,T,C) or (T,C), per-series flag, mean, std."""
+    def _check_aggregate(self, aggregate, who: str, T="max_len") -> None:
+        """ValueError unless aggregate is an int in [1, T] (T: this sampler's max_len, or None to leave the upper end open)."""
+        T = self.max_len if T == "max_len" else T
+        if isinstance(aggregate, bool) or not isinstance(aggregate, int) or aggregate < 1 or (T is not None and aggregate > T):
+            raise ValueError(f"{who}: aggregate must be an int in [1, {'T' if T is None else T}], got {aggregate!r}")
+
+    def _conditioning(self, observed, mask, feature_mean, feature_std, aggregate: int = 1):
+        """Validated device copies: observed (n,T,C) f32, mask as uint8 (n,T,C) or (T,C), per-series flag, mean, std.  aggregate = w
+        > 1: observed and mask over the J = ceil(T / w) windows, (n,J,C) and (n,J,C) or (J,C); mean and std stay (T,C)."""
         if not isinstance(mask, torch.Tensor):
             raise ValueError("observed and mask must be torch tensors")
-        n = self._check_series(observed, "observed")
+        J = -(-self.max_len // aggregate)
+        n = self._check_series(observed, "observed", J)
         if not observed.is_floating_point():
             raise ValueError(f"observed must be a floating-point tensor, got {observed.dtype}")
         T, Cn = self.max_len, self.n_channels
         dev = self.score_model.device
-        m_u8, per_series = self._mask_u8(mask, n, T, Cn, dev)
+        m_u8, per_series = self._mask_u8(mask, n, J, Cn, dev)
         if (feature_mean is None) != (feature_std is None):
             raise ValueError("feature_mean and feature_std go together (both or neither)")
         mean = std = None
@@ -753,8 +817,11 @@ class DiffusionSampler:
         return zd
 
     @staticmethod
-    def _x0_obs(obs: torch.Tensor, m_u8: torch.Tensor, fourier_transform: bool, mean, std) -> torch.Tensor:
+    def _x0_obs(obs: torch.Tensor, m_u8: torch.Tensor, fourier_transform: bool, mean, std, aggregate: int = 1,
+                T: Optional[int] = None) -> torch.Tensor:
         y0 = torch.where(m_u8.bool(), obs, torch.zeros((), dtype=obs.dtype, device=obs.device))   # NaN at unobserved entries: gone
+        if aggregate > 1:      # P^+: every entry takes its window's value
+            y0 = y0.repeat_interleave(aggregate, dim=1)[:, :T].contiguous()
         if fourier_transform:
             return dft_standardize(y0, mean, std) if std is not None else dft(y0)
         return ((y0 - mean) / std).contiguous() if std is not None else y0.contiguous()
@@ -818,9 +885,9 @@ class DiffusionSampler:
         sch.set_timesteps(N)
         return N, (C.c_float * N)(*sch.timesteps.to(torch.float32).tolist()), float(sch.step_size)
 
-    def _check_series(self, X, name: str) -> int:
-        """Raises ValueError unless X is a non-empty tensor (n, max_len, n_channels); returns n."""
-        T, Cn = self.max_len, self.n_channels
+    def _check_series(self, X, name: str, rows: Optional[int] = None) -> int:
+        """Raises ValueError unless X is a non-empty tensor (n, max_len, n_channels); returns n.  rows: in the place of max_len."""
+        T, Cn = self.max_len if rows is None else rows, self.n_channels
         if not isinstance(X, torch.Tensor) or X.dim() != 3 or tuple(X.shape[1:]) != (T, Cn):
             raise ValueError(f"{name} must be a tensor of shape (n, {T}, {Cn}), got "
                              f"{tuple(X.shape) if isinstance(X, torch.Tensor) else type(X)}")

@@ -462,6 +462,33 @@ int fd_sampler_run_impute_dps_cfg(fd_score* m, const fd_sde_params* sde, const f
                                   uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode, const int32_t* y,
                                   float cfg_scale, void* stream);
 
+/* Conditioning on window means (NOT in the reference): the observation is a series reported at a coarser rate than the model's.
+ * window = w in [1, T], J = ceil(T / w) windows, window j = [j w, min((j + 1) w, T)) of length l_j (the last may be short); per
+ * channel (P v)_j = mean of v over window j, (P^+ r)_t = r_{j(t)}, (P^T r)_t = r_{j(t)} / l_{j(t)}.  mask_u8 is (B / obs_replicas,J,C)
+ * when mask_per_series, else (J,C): 1 = the mean of that window is observed.  x0_obs stays (B / obs_replicas,T,C): A^-1(P^+ where(m,
+ * y, 0)) for the window means y (J,C).  Replacement, d as above:
+ *   x' = x + dft(P^+ (m . P idft(sigma . d))) / sigma      (fourier == 0: x' = x + P^+ (m . P (sigma . d)) / sigma)
+ * guidance: r = m . P idft(sigma . (x0_obs - x0_hat)) (J,C), u = sigma . diag(1/rho) F P^T r (fourier == 0: P in the place of P idft,
+ * u = sigma . P^T r); everything else as in the entries they extend.  feat_std is read in BOTH domains (sigma varies inside a window).
+ * window == 1 forwards to the entry without the argument (bit-identical); window < 1 or > T: FD_ERR_ARG; window > 1 needs T <= 1024
+ * in both domains.  No labels, no classifier-free guidance and no RePaint.  The first call for a (T, window) builds two rectangular
+ * bases (Jp x Tp and Tp x Jp floats, Jp = 16 ceil(J/16)) and waits for them.  Philox layouts, noise tensors and obs_replicas as
+ * fd_impute_project, fd_sampler_run_impute_rep, fd_impute_guidance and fd_sampler_run_impute_dps. */
+int fd_impute_project_agg(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                          const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z, uint64_t seed,
+                          uint64_t offset, float* out, int B, int T, int C, int window, void* stream);
+int fd_sampler_run_impute_agg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                              float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                              const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
+                              uint64_t offset, int B, int obs_replicas, int window, int mode, void* stream);
+int fd_impute_guidance_agg(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                           const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian,
+                           float* g_out, double* rnorm2_out, int B, int obs_replicas, int window, int mode, void* stream);
+int fd_sampler_run_impute_dps_agg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                  float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                  const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
+                                  uint64_t seed, uint64_t offset, int B, int obs_replicas, int window, int mode, void* stream);
+
 /* Probability-flow ODE extension (NOT in the reference, whose only sampler is Euler-Maruyama over the reverse SDE; Song et al. 2021,
  * Sec. 4.3): the deterministic ODE with the reverse SDE's marginals.  With a = a_x(t), g = g(t) of the SDE (VP: a = beta/2,
  * g = sqrt(beta); VE: a = 0, g = sigma_min sqrt(2 ln(sigma_max/sigma_min)) (sigma_max/sigma_min)^t) and s the score:
