@@ -256,7 +256,8 @@ def score_layout(dims: ModelDims, backbone: int = 0, d_mlp: int = 0, n_classes: 
             return lib().fd_score_layout_ex(C.byref(dims), backbone, d_mlp, arr, C.byref(n))
     rc = layout(None)
     if rc != 0:
-        raise FdError(f"fd_score_layout failed ({rc}): bad model dims")
+        raise FdError(f"fd_score_layout failed ({rc}): bad model dims (positive sizes, d_model % n_head == 0; MLP backbone: d_mlp > 0 "
+                      "and d_model <= 1024; LSTM backbone: d_model <= 100, the widest the backward through time holds in the LDS)")
     arr = (ParamEntry * n.value)()
     rc = layout(arr)
     if rc != 0:

@@ -185,7 +185,8 @@ extern "C" int fd_score_create_ex(fd_ctx* ctx, const fd_model_dims* dims, int ba
     FD_REQUIRE(ctx, out != nullptr, "fd_score_create: null out");
     FD_REQUIRE(ctx, dims_ok(dims), "fd_score_create: bad dims (need positive sizes and d_model %% n_head == 0)");
     FD_REQUIRE(ctx, bb_ok(dims, backbone, d_mlp), "fd_score_create_ex: backbone %d unsupported at d_model=%d d_mlp=%d (MLP: d_mlp > 0; "
-               "LSTM: d_model <= 128)", backbone, dims->d_model, d_mlp);
+               "LSTM: d_model <= 100, the widest W_hh the backward through time holds in the 160 KiB LDS)", backbone, dims->d_model,
+               d_mlp);
     FD_REQUIRE(ctx, backbone != FD_BACKBONE_TRANSFORMER || dims->d_model / dims->n_head <= 64,
                "fd_score_create: head_dim %d > 64 unsupported", dims->d_model / dims->n_head);
     FD_REQUIRE(ctx, dims->d_model <= 1024, "fd_score_create: d_model %d > 1024 unsupported", dims->d_model);

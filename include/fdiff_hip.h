@@ -207,6 +207,8 @@ int fd_score_create(fd_ctx* ctx, const fd_model_dims* dims, fd_score** out);
  *   FD_BACKBONE_LSTM  replaces fdiff.models.score_models.LSTMScoreModule (score_models.py:249-317): Linear embed, + time
  *                     embedding, num_layers x { h += nn.LSTM(d_model, d_model, batch_first)(h) }, Linear unembed.
  * Both run exact-f32 kernels in either mode (no positional table: pos_encoder is None in the reference).
+ * Limits, refused by the three calls below: MLP d_mlp > 0 and d_model <= 1024; LSTM d_model <= 100 (the backward through time
+ * keeps W_hh, 4 d_model^2 floats, and 8 d_model more in the 160 KiB LDS).
  * State-dict names: backbone.{i}.0.weight|bias, backbone.{i}.3.weight|bias (MLP); backbone.{i}.weight_ih_l0,
  * weight_hh_l0, bias_ih_l0, bias_hh_l0 (LSTM, gate order i|f|g|o). */
 #define FD_BACKBONE_TRANSFORMER 0
