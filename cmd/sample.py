@@ -60,7 +60,10 @@ class SamplingRunner:
         # metrics against the training set, on the main rank only (reference cmd/sample.py:62-65)
         self.metrics = None
         if "metrics" in cfg and cfg.metrics is not None and self.dist.is_main:
-            self.metrics = instantiate(cfg.metrics)(original_samples=self.datamodule.X_train)
+            # a metrics config with `holdout: true` (metrics=neighbours) also gets the held-out split, for the memorisation metrics
+            node = {k: v for k, v in cfg.metrics.items() if k != "holdout"}
+            bound = {"holdout_samples": self.datamodule.X_test} if cfg.metrics.get("holdout", False) else {}
+            self.metrics = instantiate(node)(original_samples=self.datamodule.X_train, **bound)
 
     def sample(self) -> None:
         bs = self.sampler.sample_batch_size

@@ -8,7 +8,7 @@ import fourierdiffusion_amd as _pkg
 
 _SUBMODULES = [
     "utils", "utils.dataclasses", "utils.fourier", "utils.losses", "utils.extraction", "utils.callbacks", "utils.tensors",
-    "utils.wasserstein",
+    "utils.wasserstein", "utils.neighbours",
     "schedulers", "schedulers.sde",
     "models", "models.score_models", "models.transformer",
     "sampling", "sampling.sampler", "sampling.metrics",

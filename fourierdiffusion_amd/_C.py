@@ -170,6 +170,9 @@ _PROTOS = {
     "fd_sort_rows": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "fd_w2_sorted_rows": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_ensemble_scores": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "fd_knn_rows_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_knn_rows": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fd_ball_counts": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -1,8 +1,12 @@
 """Evaluation metrics -- same surface as fdiff.sampling.metrics (reference: src/fdiff/sampling/metrics.py:13-217):
 `Metric`, `MetricCollection`, `SlicedWasserstein`, `MarginalWasserstein`, same constructor arguments, same result keys.
-The distances run on the HIP engine (utils/wasserstein.py); results are plain Python floats / lists as in the reference."""
+The distances run on the HIP engine (utils/wasserstein.py); results are plain Python floats / lists as in the reference.
+
+Not in the reference: `PrecisionRecall` and `Memorisation`, nearest-neighbour metrics in sample space (utils/neighbours.py), which
+see what a projection-based distance cannot -- a generator that replays its training set, or one that covers a single mode."""
 from __future__ import annotations
 
+import inspect
 from abc import ABC, abstractmethod
 from functools import partial
 from typing import Any, Optional
@@ -11,6 +15,7 @@ import numpy as np
 import torch
 
 from ..utils.fourier import dft, spectral_density
+from ..utils.neighbours import MAX_K, ball_counts, knn
 from ..utils.tensors import check_flat_array
 from ..utils.wasserstein import WassersteinDistances
 
@@ -33,6 +38,15 @@ class Metric(ABC):
 
 def _as_tensor(x) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+
+
+def _takes_holdout(make: partial) -> bool:
+    return "holdout_samples" in inspect.signature(make.func).parameters
+
+
+def subsample_indices(n: int, size: int, seed: int) -> np.ndarray:
+    """`size` of the n row indices, drawn without replacement from numpy's Generator(seed), ascending."""
+    return np.sort(np.random.default_rng(seed).choice(n, size=size, replace=False))
 
 
 class _View:
@@ -59,19 +73,29 @@ class MetricCollection:
     """Same surface and result keys as the reference's collection (metrics.py:28-99): every partially instantiated metric is bound
     to the original samples once per view -- `time` (the samples as they are) and `freq` (their dft) -- and, on request, a marginal
     Wasserstein on the spectral densities forms a third view (`spectral`, seed 42, all distances kept, no baselines).  A call
-    returns the union of the views' results (+ the time / freq baselines) sorted by key."""
+    returns the union of the views' results (+ the time / freq baselines) sorted by key.
+
+    `holdout_samples` (not in the reference): real samples the model was not trained on, mapped into each view like the original
+    samples and handed to the metrics whose class takes them (`Memorisation`); without it nothing changes."""
 
     def __init__(self, metrics: list, original_samples: Optional[np.ndarray | torch.Tensor] = None,
-                 include_baselines: bool = True, include_spectral_density: bool = False) -> None:
+                 include_baselines: bool = True, include_spectral_density: bool = False,
+                 holdout_samples: Optional[np.ndarray | torch.Tensor] = None) -> None:
         factories = [m for m in metrics if isinstance(m, partial)]      # (like the reference, only partials are taken up)
         if factories and original_samples is None:
             raise AssertionError("Original samples must be provided for the metrics to be instantiated.")
         original = _as_tensor(original_samples) if original_samples is not None else None
+        holdout = _as_tensor(holdout_samples) if holdout_samples is not None and len(holdout_samples) > 0 else None
         self._views = [_View("time", lambda x: x, []), _View("freq", dft, [])]
         for view in self._views:
             if factories:
                 bound_to = view.transform(original)
-                view.metrics = [make(original_samples=bound_to) for make in factories]
+                if holdout is None:
+                    view.metrics = [make(original_samples=bound_to) for make in factories]
+                else:
+                    held = view.transform(holdout)
+                    view.metrics = [make(original_samples=bound_to, holdout_samples=held) if _takes_holdout(make)
+                                    else make(original_samples=bound_to) for make in factories]
         self.include_baselines = include_baselines
         self.metric_spectral = None
         self._spectral_view = None
@@ -168,3 +192,104 @@ class MarginalWasserstein(_WassersteinMetric):
 
     def _distances(self, original, other):
         return WassersteinDistances(original_data=original, other_data=other, seed=self.random_seed).marginal_distances()
+
+
+class PrecisionRecall(Metric):
+    """Improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) of generated samples G
+    against the real samples R in sample space.  NND_k(x) is the distance from x to its k-th nearest neighbour in its OWN set:
+      precision  mean_i 1[count_i > 0], count_i = #{j : d(g_i, r_j) <= NND_k(r_j)}    density  sum_i count_i / (k |G|)
+      recall     the same with the roles of R and G swapped                           coverage mean_j 1[min_i d(r_j, g_i) <= NND_k(r_j)]
+    `max_original` evaluates against a seeded subsample of the real set."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, k: int = 5, max_original: Optional[int] = None,
+                 random_seed: int = 0) -> None:
+        if int(k) != k or not 1 <= k <= MAX_K:
+            raise ValueError(f"k={k} must be an integer in [1, {MAX_K}]")
+        if max_original is not None and (int(max_original) != max_original or max_original <= k):
+            raise ValueError(f"max_original={max_original} must be an integer above k={k}")
+        if len(original_samples) <= k:
+            raise ValueError(f"{len(original_samples)} original samples cannot supply k={k} neighbours of a sample in its own set")
+        super().__init__(original_samples=original_samples)
+        self.k, self.max_original, self.random_seed = int(k), max_original, random_seed
+        n = self.original_samples.shape[0]
+        if max_original is not None and n > max_original:
+            keep = torch.from_numpy(subsample_indices(n, int(max_original), random_seed)).to(self.original_samples.device)
+            self.original_samples = self.original_samples[keep].contiguous()
+
+    def _radii(self, samples: torch.Tensor) -> torch.Tensor:
+        return knn(samples, samples, self.k, exclude_self=True)[0][:, self.k - 1].contiguous()
+
+    def _evaluate(self, real: torch.Tensor, generated: torch.Tensor) -> dict[str, float]:
+        if generated.shape[0] <= self.k:
+            raise ValueError(f"{generated.shape[0]} samples cannot supply k={self.k} neighbours of a sample in its own set")
+        radii_real, radii_gen = self._radii(real), self._radii(generated)
+        in_real = ball_counts(generated, real, radii_real)            # per generated sample: real balls it falls in
+        in_gen = ball_counts(real, generated, radii_gen)
+        nearest_gen = knn(real, generated, 1)[0][:, 0]
+        return {"precision": float((in_real > 0).double().mean()),
+                "recall": float((in_gen > 0).double().mean()),
+                "density": float(in_real.sum()) / (self.k * generated.shape[0]),
+                "coverage": float((nearest_gen <= radii_real).double().mean())}
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        return self._evaluate(self.original_samples, check_flat_array(other_samples))
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        n_samples = self.original_samples.shape[0]                    # two folds of the original samples, as the Wasserstein metrics
+        if n_samples // 2 <= self.k:
+            return {}
+        folds = self._evaluate(self.original_samples[: n_samples // 2].contiguous(),
+                               self.original_samples[n_samples // 2:].contiguous())
+        return {f"{key}_self": val for key, val in folds.items()}
+
+    @property
+    def name(self) -> str:
+        return "precision_recall"
+
+
+class Memorisation(Metric):
+    """Does the generator copy its training set?  With d_i the distance from sample g_i to its nearest training row r_j*:
+      authenticity        share of samples with d_i > NND_1(r_j*) (Alaa et al. 2022): a copy sits nearer to a training row than that
+                          row's own nearest training neighbour does
+      nn_distance_min / nn_distance_median   of the d_i
+      train_closer_share  (with `holdout_samples`) share of samples strictly nearer to the training set than to the held-out set,
+                          ties one half; the training set is subsampled (seeded) to the held-out set's size when it is larger.
+                          About 0.5: nothing memorised; towards 1: samples sit on training rows."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 random_seed: int = 0) -> None:
+        if len(original_samples) < 2:
+            raise ValueError("Memorisation needs at least two original samples")
+        if holdout_samples is not None and len(holdout_samples) < 1:
+            raise ValueError("holdout_samples is empty")
+        super().__init__(original_samples=original_samples)
+        self.random_seed = random_seed
+        self.holdout_samples = self.train_subset = None
+        if holdout_samples is not None:
+            self.holdout_samples = check_flat_array(holdout_samples)
+            if self.holdout_samples.shape[1] != self.original_samples.shape[1]:
+                raise ValueError("original and held-out samples must have the same number of features")
+            n, h = self.original_samples.shape[0], self.holdout_samples.shape[0]
+            self.train_subset = self.original_samples
+            if n > h:
+                keep = torch.from_numpy(subsample_indices(n, h, random_seed)).to(self.original_samples.device)
+                self.train_subset = self.original_samples[keep].contiguous()
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = check_flat_array(other_samples)
+        dist, nearest = knn(samples, self.original_samples, 1)
+        dist, nearest = dist[:, 0], nearest[:, 0]
+        own = knn(self.original_samples, self.original_samples, 1, exclude_self=True)[0][:, 0]
+        host = dist.double().cpu().numpy()
+        out = {"authenticity": float((dist > own[nearest]).double().mean()),
+               "nn_distance_min": float(host.min()), "nn_distance_median": float(np.median(host))}
+        if self.holdout_samples is not None:
+            to_train = knn(samples, self.train_subset, 1)[0][:, 0]
+            to_held = knn(samples, self.holdout_samples, 1)[0][:, 0]
+            out["train_closer_share"] = float((to_train < to_held).double().mean() + 0.5 * (to_train == to_held).double().mean())
+        return out
+
+    @property
+    def name(self) -> str:
+        return "memorisation"

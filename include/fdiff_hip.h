@@ -644,6 +644,32 @@ int fd_w2_sorted_rows(fd_ctx* ctx, const float* a, const float* b, float* out, i
 int fd_ensemble_scores(fd_ctx* ctx, const float* samples, const float* truth, int n, int K, int T, int C, const double* levels,
                        int n_levels, float* out_crps, float* out_quantiles, float* out_mean, void* stream);
 
+/* Nearest-neighbour primitives of the sample-space metrics (NOT in the reference: improved precision / recall, density / coverage,
+ * authenticity and the train-versus-held-out nearest-neighbour share are built on them in sampling/metrics.py).  q (n, d) and
+ * r (m, d) are dense row-major fp32 device arrays with finite entries; distances are SQUARED Euclidean.
+ *   fd_knn_rows     for every query row the k nearest reference rows: dist2 (n, k) and idx (n, k), each row ascending in
+ *                   (distance, index), no index repeated.  1 <= k <= 16 and k <= m - exclude_self.  exclude_self = 1 needs q == r
+ *                   and n == m and never returns j == i (the k-NN radii of a set in itself).  Selection runs on the fp32-MFMA
+ *                   expansion ||q||^2 + ||r||^2 - 2 q.r of both sets centred by the column mean of r (double, fixed order), the
+ *                   n x m matrix never exists; the k selected pairs are then recomputed as sum (q - r)^2 (f32 differences, double
+ *                   sum in ascending feature order) and re-sorted.  So a returned distance is the distance of the returned index
+ *                   to f32 rounding, a bit-copy of a reference row returns that row at rank 0 with distance exactly 0, and a row
+ *                   can lose its place to another only when their distances differ by less than the expansion's error,
+ *                   2 (d + 3) 2^-24 (||q - mean||^2 + ||r - mean||^2).  Ties go to the lower index.  work: caller-owned device
+ *                   bytes, at least fd_knn_rows_workspace_bytes(n, m, d, k).  Deterministic, independent of how the reference
+ *                   rows are split over workgroups (the environment variable FDIFF_KNN_SPLITS forces a split count, read by
+ *                   both calls).
+ *   fd_ball_counts  counts[i] = #{ j : d2(q_i, r_j) <= radius2[j] }, radius2 (m) device fp32, on the same centred expansion
+ *                   (so a pair within that error of its radius may fall on either side); scratch from the context's arena.  No
+ *                   atomics: two runs are bit-identical.
+ * FD_ERR_ARG: null pointer, a shape < 1, k out of range, exclude_self with q != r or n != m, a workspace that is too small,
+ * n * k, n * d or m * d >= 2^31. */
+int fd_knn_rows_workspace_bytes(fd_ctx* ctx, int n, int m, int d, int k, size_t* bytes);
+int fd_knn_rows(fd_ctx* ctx, const float* q, int n, const float* r, int m, int d, int k, int exclude_self, float* dist2 /* (n, k) */,
+                int32_t* idx /* (n, k) */, void* work, size_t work_bytes, void* stream);
+int fd_ball_counts(fd_ctx* ctx, const float* q, int n, const float* r, int m, int d, const float* radius2 /* (m) */,
+                   int32_t* counts /* (n) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
