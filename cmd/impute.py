@@ -12,7 +12,9 @@ resample=r jump_length=j (conditioning=replace) turn on RePaint resampling: ever
 between two runs, r * num_diffusion_steps score evaluations; both are recorded when they are not 1.  aggregate=w > 1 conditions on
 WINDOW MEANS instead (temporal super-resolution): mask.* is read in windows of w time steps (mask.horizon counts windows), the
 observation is the window means of the test split, every full-resolution entry counts as hidden in the scores, and results.yaml records
-`aggregate` and `max_abs_err_window_means`, the largest deviation of the result's window means over the observed windows.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+`aggregate` and `max_abs_err_window_means`, the largest deviation of the result's window means over the observed windows.
+multivariate_scores=true (K > 1) adds the scores that see the joint draw (energy score, variogram score with the `variogram` block's
+order / max_lag / weights, rank histogram and its reliability index), on channels divided by their standard deviation.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -28,7 +30,7 @@ import yaml  # noqa: E402
 from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
-from fourierdiffusion_amd.sampling.forecast import ensemble_scores  # noqa: E402
+from fourierdiffusion_amd.sampling.forecast import ensemble_scores, multivariate_scores  # noqa: E402
 from fourierdiffusion_amd.sampling.masks import observation_mask, window_means  # noqa: E402
 from fourierdiffusion_amd.sampling.sampler import series_labels  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
@@ -60,6 +62,22 @@ def ensemble_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor) -
     if (~mask).any():
         out.update(ensemble_scores(X, truth, mask).metrics)
     return out
+
+
+def multivariate_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor, opts=None) -> dict:
+    """The multivariate scores of an ensemble X (n, K, T, C), K > 1 (sampling.forecast.multivariate_scores: energy score, variogram
+    score, rank histogram), with every channel divided by the standard deviation of the scored truth split (float64; 1 where it
+    is 0), since the energy score mixes channels.  opts: the `variogram` block of the config (order, max_lag, weights)."""
+    if X.dim() != 4 or int(X.shape[1]) < 2:
+        raise ValueError("multivariate_scores=true needs an ensemble: set num_samples_per_series=K > 1, got samples of shape "
+                         f"{tuple(X.shape)}")
+    opts = opts or {}
+    std = truth.double().reshape(-1, truth.shape[-1]).std(0, unbiased=False)
+    std = torch.where(std > 0, std, torch.ones_like(std))
+    max_lag = opts.get("max_lag", None)
+    m = multivariate_scores(X, truth, mask, order=float(opts.get("order", 0.5)), max_lag=None if max_lag is None else int(max_lag),
+                            weights=str(opts.get("weights", "inverse_lag")), scale=std).metrics
+    return {**m, "multivariate_scale": "channel_std"}
 
 
 class ImputationRunner:
@@ -98,6 +116,10 @@ class ImputationRunner:
         self.resample = int(cfg.get("resample", 1))
         self.jump_length = int(cfg.get("jump_length", 1))
         self.aggregate = int(cfg.get("aggregate", 1))
+        self.multivariate: bool = bool(cfg.get("multivariate_scores", False))
+        self.variogram = dict(cfg.get("variogram", None) or {})
+        if self.multivariate and self.num_samples < 2:
+            raise ValueError("multivariate_scores=true needs an ensemble: set num_samples_per_series=K > 1")
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
         self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path,
@@ -155,6 +177,8 @@ class ImputationRunner:
             fine = mask if w == 1 else torch.zeros(truth.shape, dtype=torch.bool)
             scores = hidden_errors(X, truth, fine) if K == 1 else ensemble_results(X, truth, fine)
             results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **scores}
+            if self.multivariate and (~fine).any():
+                results["impute"].update(multivariate_results(X, truth, fine, self.variogram))
             if w > 1:
                 results["impute"]["aggregate"] = w
                 if mask.any():

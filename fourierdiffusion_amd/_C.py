@@ -20,6 +20,7 @@ FD_MODE_F32 = 0
 FD_MODE_BF16 = 1
 FD_COMM_ID_BYTES = 128
 FD_BACKBONE_TRANSFORMER, FD_BACKBONE_MLP, FD_BACKBONE_LSTM = 0, 1, 2
+FD_VARIOGRAM_HALF, FD_VARIOGRAM_ONE, FD_VARIOGRAM_TWO = 0, 1, 2
 
 
 class FdError(RuntimeError):
@@ -173,6 +174,13 @@ _PROTOS = {
     "fd_knn_rows_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_knn_rows": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fd_ball_counts": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "fd_energy_score_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_energy_score": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
+                                  C.c_size_t, _vp]),
+    "fd_variogram_score_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_variogram_score": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fd_ensemble_ranks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -670,6 +670,40 @@ int fd_knn_rows(fd_ctx* ctx, const float* q, int n, const float* r, int m, int d
 int fd_ball_counts(fd_ctx* ctx, const float* q, int n, const float* r, int m, int d, const float* radius2 /* (m) */,
                    int32_t* counts /* (n) */, void* stream);
 
+/* Multivariate scores of a sample ensemble, per series (NOT in the reference; Gneiting and Raftery 2007, Scheuerer and Hamill
+ * 2015): the per-entry scores of fd_ensemble_scores cannot tell a coherent ensemble from one whose members were permuted
+ * independently at every entry, these can.  samples (n, K, T, C) fp32, truth (n, T, C), 1 <= K <= 1024; mask_u8 as in
+ * fd_impute_*: 1 = observed, (n, T, C) when mask_per_series, else one (T, C) mask.  H: the hidden entries of a series (mask 0).
+ *   fd_energy_score     out_score[s] = (1/K) sum_k ||x_k - y||_H - 1/(2 K^2) sum_{j,k} ||x_j - x_k||_H, Euclidean norms over H;
+ *                       fair != 0: 1/(2 K (K - 1)) in the second term, needs K >= 2.  NaN when H is empty.  out_hidden[s] = |H|.
+ *   fd_variogram_score  out_num[s] = sum_{a<b in H} w_ab (|y_a - y_b|^p - (1/K) sum_k |x_ka - x_kb|^p)^2, out_den[s] = sum w_ab,
+ *                       over the pairs of hidden entries a = (t_a, c_a), b = (t_b, c_b) (every channel pair) with
+ *                       |t_a - t_b| <= max_lag (max_lag < 0: no limit); p = 0.5, 1, 2 for order = FD_VARIOGRAM_HALF, _ONE, _TWO;
+ *                       w_ab = 1 / (1 + |t_a - t_b|) when inverse_lag, else 1.  The score is num / den.  A series with no such
+ *                       pair: num NaN, den 0.  out_hidden (n) may be NULL.
+ *   fd_ensemble_ranks   below[e] = #{k : x_k < y}, equal[e] = #{k : x_k == y}, int32 (n, T, C), for EVERY entry (no mask); an
+ *                       entry with a NaN sample or truth gets -1 in both.
+ * Observed entries are skipped by select: whatever they hold, NaN included, has no effect.  A NaN at a hidden entry, in the truth
+ * or in any member, makes out_score / out_num of that series NaN and leaves the other series alone (out_den depends on the mask
+ * only).  One tile kernel serves both scores (csrc/fd_multivariate.hip): differences in fp32 (never the Gram expansion), at most
+ * 64 terms summed in fp32, then double; one partial per 64 x 64 tile of row pairs in work, added per series in fixed order by a
+ * second kernel.  No atomics: two runs are bit-identical, and a series' outputs do not depend on n or on its position.  work:
+ * caller-owned device bytes, at least *_workspace_bytes of the same shape (and max_lag).
+ * FD_ERR_ARG: null pointer, a shape < 1, K outside [1, 1024], fair with K = 1, an unknown order, a workspace that is too small,
+ * T*C or n times the tiles of a series >= 2^31 (fd_ensemble_ranks: n > 65535). */
+enum { FD_VARIOGRAM_HALF = 0, FD_VARIOGRAM_ONE = 1, FD_VARIOGRAM_TWO = 2 };
+int fd_energy_score_workspace_bytes(fd_ctx* ctx, int n, int K, int T, int C, size_t* bytes);
+int fd_energy_score(fd_ctx* ctx, const float* samples, const float* truth, const uint8_t* mask_u8, int mask_per_series, int n, int K,
+                    int T, int C, int fair, double* out_score /* (n) */, int32_t* out_hidden /* (n) */, void* work,
+                    size_t work_bytes, void* stream);
+int fd_variogram_score_workspace_bytes(fd_ctx* ctx, int n, int K, int T, int C, int max_lag, size_t* bytes);
+int fd_variogram_score(fd_ctx* ctx, const float* samples, const float* truth, const uint8_t* mask_u8, int mask_per_series, int n,
+                       int K, int T, int C, int order, int max_lag, int inverse_lag, double* out_num /* (n) */,
+                       double* out_den /* (n) */, int32_t* out_hidden /* (n) or NULL */, void* work, size_t work_bytes,
+                       void* stream);
+int fd_ensemble_ranks(fd_ctx* ctx, const float* samples, const float* truth, int n, int K, int T, int C, int32_t* below,
+                      int32_t* equal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
