@@ -6,7 +6,10 @@ split's shape) next to the checkpoint, with the MSE / MAE over the hidden entrie
 num_samples_per_series=K > 1 draws an ensemble of K samples per series instead: imputations.pt is (n, K, T, C) and results.yaml
 holds the ensemble scores of sampling/forecast.py (CRPS, quantile CRPS and CRPS-sum, median errors, 90 % interval coverage) in
 place of the MSE / MAE.  conditioning=dps (guidance.scale, guidance.jacobian) replaces the projection by gradient guidance; the three
-keys are then recorded in the `impute` block.  labels=data|<int> (class-conditional models) conditions every series on its test label
+keys are then recorded in the `impute` block.  conditioning=smc (smc.obs_std, smc.twist_scale, smc.ess_threshold, guidance.jacobian;
+num_samples_per_series = K >= 2 particles) runs the twisted particle filter instead and adds `smc_log_evidence_mean`,
+`smc_ess_final_mean` (final ESS / K), `smc_resamples_mean` (resamples per series) and `smc_unique_final_mean` (distinct final
+ancestors / K).  labels=data|<int> (class-conditional models) conditions every series on its test label
 (`datamodule.y_test`) or on one class, cfg_scale=w sets the classifier-free guidance scale; both are recorded only when set.
 resample=r jump_length=j (conditioning=replace) turn on RePaint resampling: every block of j steps runs r times with a forward re-noise
 between two runs, r * num_diffusion_steps score evaluations; both are recorded when they are not 1.  aggregate=w > 1 conditions on
@@ -111,6 +114,9 @@ class ImputationRunner:
         guidance = cfg.get("guidance", None) or {}
         self.guidance_scale = float(guidance.get("scale", 1.0))
         self.guidance_jacobian = bool(guidance.get("jacobian", True))
+        smc = cfg.get("smc", None) or {}
+        self.smc = dict(obs_std=float(smc.get("obs_std", 0.1)), twist_scale=float(smc.get("twist_scale", 1.0)),
+                        ess_threshold=float(smc.get("ess_threshold", 0.5)))
         self.labels = cfg.get("labels", None)
         self.cfg_scale = float(cfg.get("cfg_scale", 1.0))
         self.resample = int(cfg.get("resample", 1))
@@ -152,8 +158,17 @@ class ImputationRunner:
         if self.datamodule.standardize:
             mean, std = self.datamodule.feature_mean_and_std
         X = None
+        smc_stats = None
+        if hi > lo and self.conditioning == "smc":
+            X, info = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps,
+                                          fourier_transform=self.fourier_transform, feature_mean=mean, feature_std=std,
+                                          num_samples=K, conditioning="smc", guidance_jacobian=self.guidance_jacobian,
+                                          return_info=True, **self.smc, **guided, **repaint, **agg)
+            unique = torch.tensor([[len(set(a.tolist())) for a in info.ancestors[-1]]], dtype=torch.float64) / K
+            # per-series rows: evidence, final ESS / K, resamples, distinct final ancestors / K
+            smc_stats = torch.stack([info.log_evidence, info.ess[-1] / K, info.resampled.double().sum(0), unique[0]], dim=1)
         if hi > lo:
-            X = self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
+            X = X if smc_stats is not None else self.sampler.impute(observed[lo:hi], mask[lo:hi], self.num_diffusion_steps, fourier_transform=self.fourier_transform,
                                     feature_mean=mean, feature_std=std, num_samples=None if K == 1 else K,
                                     conditioning=self.conditioning, guidance_scale=self.guidance_scale,
                                     guidance_jacobian=self.guidance_jacobian, **guided, **repaint, **agg)
@@ -169,6 +184,10 @@ class ImputationRunner:
             parts = [None] * self.dist.world
             dist.all_gather_object(parts, X)                                        # host-side gather of the results
             X = torch.cat([p for p in parts if p is not None], dim=0)
+            if self.conditioning == "smc":
+                stats = [None] * self.dist.world
+                dist.all_gather_object(stats, smc_stats)
+                smc_stats = torch.cat([p for p in stats if p is not None], dim=0)
         if self.dist.is_main:
             results_path = self.save_dir / "results.yaml"
             results = yaml.safe_load(open(results_path)) if results_path.exists() else None
@@ -184,7 +203,13 @@ class ImputationRunner:
                 if mask.any():
                     dev = (window_means(X.double(), w) - (coarse.double() if K == 1 else coarse.double()[:, None])).abs()
                     results["impute"]["max_abs_err_window_means"] = float(dev[(mask if K == 1 else mask[:, None]).expand_as(dev)].max())
-            if self.conditioning != "replace":
+            if self.conditioning == "smc":
+                st = smc_stats.mean(0)
+                results["impute"].update(conditioning="smc", guidance_jacobian=self.guidance_jacobian,
+                                         **{f"smc_{k}": v for k, v in self.smc.items()}, smc_log_evidence_mean=float(st[0]),
+                                         smc_ess_final_mean=float(st[1]), smc_resamples_mean=float(st[2]),
+                                         smc_unique_final_mean=float(st[3]))
+            elif self.conditioning != "replace":
                 results["impute"].update(conditioning=self.conditioning, guidance_scale=self.guidance_scale,
                                          guidance_jacobian=self.guidance_jacobian)
             if guided:

@@ -140,6 +140,12 @@ _PROTOS = {
     "fd_sampler_run_impute_dps_agg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                                 _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_impute_smc": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                            _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp,
+                                            C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fd_smc_resample": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "fd_smc_step": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                              C.c_uint64, C.c_double, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_pf_ode_drift": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_dpm": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),

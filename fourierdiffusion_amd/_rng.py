@@ -10,6 +10,9 @@ data-parallel ranks (same seed) get disjoint counter ranges through ``set_rank``
 
 Counter ranges under one key (offsets relative to the rank's base, ``rank << 56``):
   perturbation / prior / step noise   [0, n / 4) of the call's own key (one key per call)
+  resampling uniforms (conditioning="smc")  behind the predictor noise of the same call: with N steps of B rows (n = B / K series)
+                                      the uniform of (stage j, series q), j = 0 .. N, is ((word >> 8) + 0.5) / 2^24 of word
+                                      (j n + q) % 4 of counter N ceil(B T C / 4) + (j n + q) / 4 (fd_sampler_run_impute_smc)
   dropout site s of encoder layer l   [(4 l + s) << 40, (4 l + s + 1) << 40) of the training call's key (fd_dropout_site_offset)
   label dropout (class conditioning)  [0xFFFF << 40, 0xFFFF << 40 + B / 4] of the same training call's key: the window of "layer
                                       16383, site 3", which no encoder layer reaches; label b is lane b % 4 of counter b / 4

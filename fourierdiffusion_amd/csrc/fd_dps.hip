@@ -32,6 +32,7 @@
 
 #include "fd_aggregate.h"
 #include "fd_common.h"
+#include "fd_dps.h"
 #include "fd_engine.h"
 #include "fd_loop.h"
 #include "fd_philox.h"
@@ -45,20 +46,7 @@ constexpr int kStepBlock = 256;
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-struct ResArgs {
-    const float* x;          // (B,T,C) state x_i
-    const float* score;      // (B,T,C) s_theta(x_i, t_i)
-    const float* x0;         // (B/obs_rep,T,C) A^-1(where(m, y, 0))
-    const uint8_t* mask;     // (B/obs_rep,T,C) or (T,C), 1 = observed, time domain
-    const float* stdv;       // (T,C) feature std or nullptr (= 1)
-    const float* G;          // (T)
-    const float* basis;      // F (Tp x Tp) then F^T (Tp x Tp); FOURIER only
-    float* u;                // (B,T,C)
-    float* dout;             // (B,T,C) s^2 G^2 u, or nullptr (no Jacobian)
-    double* part;            // (B, ncb) sum r^2 of each channel block
-    int T, C, Tp, ncb, mask_per_series, obs_rep;
-    float alpha, s2;
-};
+typedef fd_dps_res ResArgs;      // fd_dps.h
 // PAIR: x and score are (2B,T,C), dout too (w v in the conditional half, (1 - w) v in the null half); u and part stay B rows
 struct ResArgsPair : ResArgs {
     size_t half;             // B T C: where the null half starts
@@ -271,31 +259,17 @@ __global__ __launch_bounds__(kStepBlock) void k_dps_step(typename StepArgsOf<PAI
     }
 }
 
-// the stage buffers of one run (fd_ll_carve: outside the arena).  R: the rows of a forward (B, or 2B for a paired guide, whose label
-// vector lab and -- fd_impute_guidance_cfg, whose x is the caller's -- state copy xpair follow the unpaired layout)
-struct DpsBufs {
-    float *tvec, *score, *u, *dout, *dx;
-    double* part;
-    int* lab;
-    float* xpair;
-};
-int dps_buffers(fd_ctx* ctx, int B, int R, size_t n, int ncb, bool jac, bool xpair, DpsBufs* o) {
-    const size_t nR = n / B * R;
-    return fd_ll_carve(ctx, [&](auto take) {
-        o->tvec = (float*)take(R * sizeof(float));
-        o->score = (float*)take(nR * sizeof(float));
-        o->u = (float*)take(n * sizeof(float));
-        o->dout = jac ? (float*)take(nR * sizeof(float)) : nullptr;
-        o->dx = jac ? (float*)take(nR * sizeof(float)) : nullptr;
-        o->part = (double*)take((size_t)B * ncb * sizeof(double));
-        o->lab = R != B ? (int*)take((size_t)R * sizeof(int)) : nullptr;
-        o->xpair = xpair ? (float*)take(nR * sizeof(float)) : nullptr;
-    });
+typedef fd_dps_bufs DpsBufs;     // fd_dps.h
+
+}  // namespace
+
+int fd_dps_buffers(fd_ctx* ctx, int B, int R, size_t n, int ncb, bool jac, bool xpair, fd_dps_bufs* o) {
+    return fd_ll_carve(ctx, [&](auto take) { fd_dps_take(take, B, R, n, ncb, jac, xpair, o); });
 }
 
 // checks and fills the conditioning / geometry fields shared by both entries
-int dps_prepare(fd_score* m, ResArgs& r, const float* G, const float* x, const float* x0, const uint8_t* mask, int mask_per_series,
-                const float* stdv, int fourier, int B, int obs_replicas, hipStream_t s, const char* who) {
+int fd_dps_prepare(fd_score* m, fd_dps_res& r, const float* G, const float* x, const float* x0, const uint8_t* mask,
+                   int mask_per_series, const float* stdv, int fourier, int B, int obs_replicas, hipStream_t s, const char* who) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, G && x && x0 && mask, "%s: null pointer", who);
     FD_REQUIRE(ctx, obs_replicas > 0 && B % obs_replicas == 0, "%s: B=%d is not a multiple of obs_replicas=%d", who, B, obs_replicas);
@@ -316,6 +290,8 @@ int dps_prepare(fd_score* m, ResArgs& r, const float* G, const float* x, const f
     }
     return FD_OK;
 }
+
+namespace {
 
 template <bool FOURIER, bool PAIR>
 int launch_residual(fd_ctx* ctx, const typename ResArgsOf<PAIR>::type& r, int B, hipStream_t s) {
@@ -348,11 +324,13 @@ int launch_step(fd_ctx* ctx, const StepArgs& a, const fd_guide* g, hipStream_t s
     return FD_OK;
 }
 
+}  // namespace
+
 // One guidance evaluation at (x, tvec) on R network rows (B, or 2B under a paired guide g): the score (training forward with the
 // Jacobian, else the sampler's forward), the residual of the B state rows, and the VJP; leaves score, u, dx and the block sums in
 // the buffers
-int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, int R, const fd_guide* g, bool jac, bool fourier,
-             int mode, hipStream_t s, const fd_agg_plan* ag = nullptr) {
+int fd_dps_eval(fd_score* m, fd_dps_res& r, const fd_dps_bufs& bf, const float* x, int B, int R, const fd_guide* g, bool jac,
+                bool fourier, int mode, hipStream_t s, const fd_agg_plan* ag) {
     fd_ctx* ctx = m->ctx;
     if (jac) {
         if (int rc = fd_score_forward_train(m, x, bf.tvec, bf.score, R, 0.f, 0, 0, s)) return rc;
@@ -384,6 +362,13 @@ int dps_eval(fd_score* m, ResArgs& r, const DpsBufs& bf, const float* x, int B, 
     return FD_OK;
 }
 
+// the residual of the B state rows alone, from the x and score r points at (no network evaluation)
+int fd_dps_residual(fd_ctx* ctx, const fd_dps_res& r, int B, bool fourier, hipStream_t s) {
+    return fourier ? launch_residual<true, false>(ctx, r, B, s) : launch_residual<false, false>(ctx, r, B, s);
+}
+
+namespace {
+
 // the body of fd_impute_guidance (g == null) and fd_impute_guidance_cfg, the arguments checked under the name `who`
 int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
                  const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian, float* g_out,
@@ -393,7 +378,7 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
     FD_REQUIRE(ctx, g_out && rnorm2_out, "%s: null pointer", who);
     FD_REQUIRE(ctx, std::isfinite(t) && t > 0.f, "%s: t=%g must be finite and > 0", who, (double)t);
     ResArgs r{};
-    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
+    if (int rc = fd_dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
     fd_agg_plan agg{};
     if (window > 1) {
         FD_REQUIRE(ctx, !g, "%s: window=%d goes with no guide", who, window);
@@ -403,7 +388,7 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
     const size_t n = (size_t)B * r.T * r.C;
     const int R = fd_guide_rows(g, B);
     DpsBufs bf;
-    if (int rc = dps_buffers(ctx, B, R, n, r.ncb, jac, pair, &bf)) return rc;
+    if (int rc = fd_dps_buffers(ctx, B, R, n, r.ncb, jac, pair, &bf)) return rc;
     double al = 1.0, sd = 0.0;
     fd_marginal_coef(*sde, (double)t, &al, &sd);
     r.alpha = (float)al;
@@ -418,7 +403,7 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
     fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
     fd_label_dropout_scope ld(m, 0.f);
     fd_fill(bf.tvec, R, t, s);
-    if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
+    if (int rc = fd_dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
     StepArgs a{};
     a.G = G; a.u = bf.u; a.dx = bf.dx; a.part = bf.part; a.gout = g_out; a.rn2_out = rnorm2_out;
     a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
@@ -438,7 +423,7 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
     FD_REQUIRE(ctx, std::isfinite(guidance_scale) && guidance_scale >= 0.f, "%s: guidance_scale=%g must be finite and >= 0", who,
                (double)guidance_scale);
     ResArgs r{};
-    if (int rc = dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
+    if (int rc = fd_dps_prepare(m, r, G, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, B, obs_replicas, s, who)) return rc;
     fd_agg_plan agg{};
     if (window > 1) {
         FD_REQUIRE(ctx, !g, "%s: window=%d goes with no guide", who, window);
@@ -448,7 +433,7 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
     const size_t n = (size_t)B * r.T * r.C;
     const int R = fd_guide_rows(g, B);
     DpsBufs bf;
-    if (int rc = dps_buffers(ctx, B, R, n, r.ncb, jac, false, &bf)) return rc;
+    if (int rc = fd_dps_buffers(ctx, B, R, n, r.ncb, jac, false, &bf)) return rc;
     r.u = bf.u; r.dout = bf.dout; r.part = bf.part;
     // per-step coefficients on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and Tweedie's (alpha, s) at t_i
     std::vector<SdeCoef> cf(n_steps);
@@ -475,7 +460,7 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
         fd_fill(bf.tvec, R, timesteps[i], s);
         r.alpha = al[i];
         r.s2 = s2[i];
-        if (int rc = dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
+        if (int rc = fd_dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
         a.zin = z_steps ? z_steps + (size_t)i * n : nullptr;
         a.cf = cf[i];
         a.alpha = al[i];

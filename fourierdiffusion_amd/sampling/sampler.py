@@ -45,6 +45,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import torch
@@ -55,6 +56,21 @@ from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
 from ..utils.fourier import dft, dft_standardize
 from .likelihood import ESTIMATORS, EXACT_MAX_DIMS, RK45_MAX_EVALS, LikelihoodResult, drift_divergence, drift_integral
+
+
+@dataclass
+class SMCInfo:
+    """What ``impute(conditioning="smc", return_info=True)`` reports next to its samples, for n series, K particles and N steps (CPU
+    tensors).  log_evidence (n,) float64: the estimate of log p(y), the Gaussian constant included, -inf for a degenerate series;
+    log_weights (n, K) float64: the final log weights (0 after a final resample); ess (N + 1, n) float64, resampled (N + 1, n) bool
+    and ancestors (N + 1, n, K) int32 (index inside the series) of every stage; degenerate (n,) bool: every particle of the series
+    lost its weight (no resampling from then on)."""
+    log_evidence: torch.Tensor
+    log_weights: torch.Tensor
+    ess: torch.Tensor
+    resampled: torch.Tensor
+    ancestors: torch.Tensor
+    degenerate: torch.Tensor
 
 
 class DiffusionSampler:
@@ -468,7 +484,9 @@ class DiffusionSampler:
                obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None,
                conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True,
                resample: int = 1, jump_length: int = 1, renoise_noise: Optional[Sequence[torch.Tensor]] = None,
-               aggregate: int = 1, y=None, cfg_scale: float = 1.0) -> torch.Tensor:
+               aggregate: int = 1, obs_std: Optional[float] = None, twist_scale: float = 1.0, ess_threshold: float = 0.5,
+               final_resample: bool = True, resample_noise: Optional[Sequence[torch.Tensor]] = None, return_info: bool = False,
+               y=None, cfg_scale: float = 1.0):
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
         it back with the caller's destandardise / idft), one series per row of ``observed``.  ``num_samples`` = K >= 1: an
         ensemble of K samples per series instead, (n, K, max_len, n_channels); a launch holds max(1, sample_batch_size // K)
@@ -515,8 +533,28 @@ class DiffusionSampler:
         the window means of the result reproduce ``observed`` on the observed windows up to f32 rounding; under "dps" the residual
         is the one of the window means (fd_sampler_run_impute_agg, fd_sampler_run_impute_dps_agg).  ``feature_std`` is read in both
         domains (it varies inside a window).  Ensembles and both Jacobian modes work; y / cfg_scale and resample > 1 do not
-        (ValueError), and max_len <= 1024.  aggregate=1: the call without the argument, to the bit."""
+        (ValueError), and max_len <= 1024.  aggregate=1: the call without the argument, to the bit.
+
+        conditioning="smc" (num_samples = K in [2, 1024]): twisted sequential Monte Carlo, the Twisted Diffusion Sampler of Wu et
+        al. 2023 (fd_sampler_run_impute_smc).  The observation model is y = A(x_0) + obs_std eps at the observed entries (obs_std
+        > 0, data scale).  The K rows of a series are particles: the "dps" gradient, scaled by 1 / (2 v_i), v_i = obs_std^2 +
+        twist_scale (s_i / alpha_i)^2, is the proposal; importance weights correct for what it gets wrong (exactly, with or
+        without ``guidance_jacobian``); whenever the effective sample size of a series falls below ess_threshold K its particles
+        are resampled on the device (systematic resampling).  final_resample=True resamples once more at the end, so the K
+        returned samples are equally weighted and ``ensemble_scores`` / ``multivariate_scores`` apply unchanged; False never
+        resamples at the end and returns the weighted particles (weights in ``SMCInfo.log_weights``).  resample_noise[b] (N + 1, nb): injected uniforms in [0, 1),
+        one per (stage, series), else the call's Philox stream behind the predictor noise.  return_info=True: returns
+        ``(samples, SMCInfo)``, the info holding the log evidence log p(y) per series (an unbiased estimate of p(y) under the
+        discretised model), the final log weights, and the ESS, resample flags and ancestors of all N + 1 stages.  y / cfg_scale,
+        aggregate > 1, resample > 1, obs_noise and guidance_scale do not apply (ValueError for the first four).  The other
+        conditionings ignore these arguments (obs_std, resample_noise and return_info are errors there)."""
         self._check_aggregate(aggregate, "impute")
+        if conditioning == "smc":
+            return self._impute_smc(observed, mask, num_diffusion_steps, fourier_transform, feature_mean, feature_std, prior_noise,
+                                    step_noise, obs_noise, num_samples, guidance_jacobian, resample, renoise_noise, aggregate, y,
+                                    cfg_scale, obs_std, twist_scale, ess_threshold, final_resample, resample_noise, return_info)
+        if obs_std is not None or resample_noise is not None or return_info:
+            raise ValueError("impute: obs_std, resample_noise and return_info go with conditioning='smc'")
         if aggregate > 1 and (y is not None or cfg_scale != 1.0):
             raise ValueError("impute: aggregate > 1 is not supported with y / cfg_scale (classifier-free guidance)")
         if aggregate > 1 and isinstance(resample, int) and resample > 1:
@@ -534,7 +572,7 @@ class DiffusionSampler:
         if num_samples is not None and (isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1):
             raise ValueError(f"impute: num_samples must be None or an int >= 1, got {num_samples!r}")
         if conditioning not in ("replace", "dps"):
-            raise ValueError(f"impute: conditioning must be 'replace' or 'dps', got {conditioning!r}")
+            raise ValueError(f"impute: conditioning must be 'replace', 'dps' or 'smc', got {conditioning!r}")
         if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)) or not math.isfinite(guidance_scale) \
                 or guidance_scale < 0:
             raise ValueError(f"impute: guidance_scale must be a finite number >= 0, got {guidance_scale!r}")
@@ -619,6 +657,82 @@ class DiffusionSampler:
             _C.check(rc, ctx)
             out.append(X if num_samples is None else X.view(nb, reps, *X.shape[1:]))
         return torch.cat([x.cpu() for x in out], dim=0)
+
+    def _impute_smc(self, observed, mask, num_diffusion_steps, fourier_transform, feature_mean, feature_std, prior_noise, step_noise,
+                    obs_noise, num_samples, guidance_jacobian, resample, renoise_noise, aggregate, y, cfg_scale, obs_std, twist_scale,
+                    ess_threshold, final_resample, resample_noise, return_info):
+        """``impute(conditioning="smc")``: the argument checks, then one fd_sampler_run_impute_smc per launch."""
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or not 2 <= num_samples <= 1024:
+            raise ValueError(f"impute: conditioning='smc' needs num_samples (particles per series) in [2, 1024], got {num_samples!r}")
+        if y is not None or cfg_scale != 1.0:
+            raise ValueError("impute: y / cfg_scale are not supported with conditioning='smc'")
+        if aggregate > 1:
+            raise ValueError("impute: aggregate > 1 is not supported with conditioning='smc'")
+        if resample != 1 or renoise_noise is not None:
+            raise ValueError("impute: resample > 1 (RePaint) is not supported with conditioning='smc'")
+        if obs_noise is not None:
+            raise ValueError("impute: obs_noise is not used by conditioning='smc' (no observation is noised)")
+        if self.corrector_steps > 0:
+            raise ValueError("impute: the predictor-corrector sampler is not supported with conditioning (corrector_steps=0)")
+        if not number(obs_std) or obs_std <= 0:
+            raise ValueError(f"impute: conditioning='smc' needs obs_std, a finite number > 0, got {obs_std!r}")
+        if not number(twist_scale) or twist_scale < 0:
+            raise ValueError(f"impute: twist_scale must be a finite number >= 0, got {twist_scale!r}")
+        if not number(ess_threshold) or not 0 <= ess_threshold <= 1:
+            raise ValueError(f"impute: ess_threshold must lie in [0, 1], got {ess_threshold!r}")
+        for name, v in (("final_resample", final_resample), ("guidance_jacobian", guidance_jacobian), ("return_info", return_info)):
+            if not isinstance(v, bool):
+                raise ValueError(f"impute: {name} must be a bool, got {v!r}")
+        obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, 1)
+        self.score_model.eval()
+        N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
+        ctx, h, p, G, mode = self._engine_args()
+        K = int(num_samples)
+        n, bs = obs.shape[0], max(1, self.sample_batch_size // K)
+        dev = self.score_model.device
+        out: List[torch.Tensor] = []
+        info = {k: [] for k in ("log_evidence", "log_weights", "ess", "resampled", "ancestors")}
+        for b, lo in enumerate(range(0, n, bs)):
+            nb = min(bs, n - lo)
+            rows = nb * K
+            X = self.sample_prior(rows, noise=None if prior_noise is None else prior_noise[b])
+            z = None if step_noise is None else self._noise(step_noise[b], (N, rows), "step_noise")
+            u = None
+            if resample_noise is not None:
+                u = resample_noise[b].to(device=dev, dtype=torch.float64).contiguous()
+                if tuple(u.shape) != (N + 1, nb) or not bool(((u >= 0) & (u < 1)).all()):
+                    raise ValueError(f"resample_noise must have shape {(N + 1, nb)} and lie in [0, 1), got {tuple(u.shape)}")
+            key, off = (0, 0) if (z is not None and u is not None) else _rng.stream()
+            m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
+            x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std)
+            lz = torch.empty(nb, dtype=torch.float64, device=dev)
+            lw = torch.empty(rows, dtype=torch.float64, device=dev)
+            es = torch.empty(N + 1, nb, dtype=torch.float64, device=dev)
+            rs = torch.empty(N + 1, nb, dtype=torch.uint8, device=dev)
+            an = torch.empty(N + 1, rows, dtype=torch.int32, device=dev)
+            rc = _C.lib().fd_sampler_run_impute_smc(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                    m_b.data_ptr(), int(per_series), _C.ptr(std), int(bool(fourier_transform)),
+                                                    int(guidance_jacobian), float(obs_std), float(twist_scale),
+                                                    float(ess_threshold), int(final_resample), _C.ptr(z), _C.ptr(u), key, off, rows,
+                                                    K, mode, lz.data_ptr(), lw.data_ptr(), es.data_ptr(), rs.data_ptr(),
+                                                    an.data_ptr(), _C.stream_of(X))
+            _C.check(rc, ctx)
+            out.append(X.view(nb, K, *X.shape[1:]).cpu())
+            n_obs = (m_b.reshape(nb, -1) if per_series else m_b.reshape(1, -1).expand(nb, -1)).sum(dim=1).to(torch.float64)
+            info["log_evidence"].append((lz - 0.5 * n_obs * math.log(2.0 * math.pi * float(obs_std) ** 2)).cpu())
+            info["log_weights"].append(lw.view(nb, K).cpu())
+            info["ess"].append(es.cpu())
+            info["resampled"].append(rs.bool().cpu())
+            info["ancestors"].append(an.view(N + 1, nb, K).cpu())
+        X = torch.cat(out, dim=0)
+        if not return_info:
+            return X
+        le = torch.cat(info["log_evidence"])
+        return X, SMCInfo(log_evidence=le, log_weights=torch.cat(info["log_weights"]), ess=torch.cat(info["ess"], dim=1),
+                          resampled=torch.cat(info["resampled"], dim=1), ancestors=torch.cat(info["ancestors"], dim=1),
+                          degenerate=torch.isinf(le) & (le < 0))
 
     @staticmethod
     def repaint_schedule(N: int, resample: int = 1, jump_length: int = 1) -> list:

@@ -446,6 +446,45 @@ int fd_sampler_run_impute_dps(fd_score* m, const fd_sde_params* sde, const float
                               float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
                               int fourier, float guidance_scale, int jacobian, const float* z_steps, uint64_t seed, uint64_t offset,
                               int B, int obs_replicas, int mode, void* stream);
+/* Twisted sequential Monte Carlo conditioning (NOT in the reference; the Twisted Diffusion Sampler, Wu et al. 2023) around the
+ * evaluation above.  A series is carried by `particles` = K adjacent state rows that read its observation in place (as obs_replicas);
+ * the observation model is y = A(x_0) + obs_std eps at the observed entries.  Per row and step i, with rho_i = ||r||^2 and g_i as
+ * above, n = sqrt(dt) g(t_i) G_k z the noise term of fd_sde_apply per element and S = dt g(t_i)^2 G_k^2 its variance:
+ *   v_i      = obs_std^2 + twist_scale (s_i / alpha_i)^2
+ *   ltw_i(x) = -rho_i(x) / (2 v_i),   h_i = g_i / (2 v_i)
+ *   x_{i+1}  = fd_sde_apply(x_i, score_i, z_i) + S . h_i                  (term skipped where h == 0)
+ *   c1 = sum_e n_e h_e,  c2 = sum_e S_e h_e^2                             (per row, double, fixed order)
+ *   logw    += -c1 - c2 / 2 + ltw_{i+1}(x_{i+1}) - ltw_i(x_i)             (logw = ltw_0(x_0) at the prior)
+ * After step N-1 the twist is the likelihood: rho_N is the residual of x_N with alpha = 1, s = 0 (no network evaluation), v_N =
+ * obs_std^2.  Stage j = 0 .. N (after evaluation j, before step j; stage N is the final one), per series over its K rows, in double:
+ * W = softmax(logw), a NaN or infinite logw counting as weight 0; ESS = 1 / sum W^2; if ESS < ess_threshold K (always at stage N
+ * when final_resample != 0): the evidence grows by logsumexp(logw) - log K, the rows are resampled systematically from ONE uniform
+ * u, a[k] = min{j : cumW[j] > (u + k) / K} clamped to K - 1, and logw = 0; else logw is kept.  Stage N resamples under
+ * final_resample alone (final_resample == 0: never, the weighted rows are returned and logsumexp - log K still goes to the evidence).  A series whose rows all have weight 0 is not resampled and its evidence becomes -inf.  The
+ * constant -(n_obs / 2) log(2 pi obs_std^2) of the likelihood is NOT added.  2 <= particles <= 1024, B % particles == 0,
+ * obs_std > 0, 0 <= ess_threshold <= 1, twist_scale finite and >= 0 (FD_ERR_ARG otherwise, before any device work).
+ *   fd_sampler_run_impute_smc: the whole loop; x (B,T,C) holds the prior sample and receives the particles of stage N (resampled
+ *       under final_resample).  Philox (seed): predictor noise as fd_sampler_run_impute_dps; the uniform of (stage j, series q) is
+ *       ((word >> 8) + 0.5) / 2^24 of word (j n + q) % 4 of counter offset + n_steps*ceil(BTC/4) + (j n + q) / 4, n = B / particles
+ *       (behind the last predictor group).  z_steps: injected (n_steps,B,T,C) or NULL; u_stages: injected double (n_steps+1, n) or
+ *       NULL.  Outputs, device, each nullable: log_evidence double (n), log_weights double (B) (0 after a final resample), ess
+ *       double (n_steps+1, n), resampled uint8 (n_steps+1, n), ancestors int32 (n_steps+1, B) (index inside the series).  No host
+ *       synchronisation in the loop: the decision to resample stays on the device.
+ *   fd_smc_resample: one stage alone on logw (n, particles), in place, with u (n): ancestors (n, particles), ess (n), resampled (n),
+ *       dlogz (n) the evidence increment (0 when nothing is added; final_stage != 0 adds it without a resample too).
+ *   fd_smc_step: one proposal alone: x_out row b from row (b / particles) particles + ancestors[b] of x, score, g (ancestors NULL:
+ *       the identity), h = g inv2v, noise z (B,T,C) or NULL (Philox at offset + e / 4); c1, c2 double (B).  x_out != x. */
+int fd_sampler_run_impute_smc(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt,
+                              float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
+                              int fourier, int jacobian, double obs_std, double twist_scale, double ess_threshold,
+                              int final_resample, const float* z_steps, const double* u_stages, uint64_t seed, uint64_t offset, int B,
+                              int particles, int mode, double* log_evidence, double* log_weights, double* ess, uint8_t* resampled,
+                              int32_t* ancestors, void* stream);
+int fd_smc_resample(fd_ctx* ctx, double* logw, const double* u, int n, int particles, double ess_threshold, int force,
+                    int final_stage, int32_t* ancestors, double* ess, uint8_t* resampled, double* dlogz, void* stream);
+int fd_smc_step(fd_ctx* ctx, const fd_sde_params* sde, const float* G, double t, float dt, const float* x, const float* score,
+                const float* g, const int32_t* ancestors, const float* z, uint64_t seed, uint64_t offset, double inv2v, float* x_out,
+                double* c1, double* c2, int B, int particles, int T, int C, void* stream);
 /* The two above under classifier-free guidance (class-conditional models; FD_ERR_ARG otherwise), y / cfg_scale and the pairing rule
  * as fd_sampler_run_impute_cfg.  The score in x0_hat and in the step is the guided one, and
  *   dx = w J_c^T v + (1 - w) J_u^T v,  v = s^2 G^2 . u:

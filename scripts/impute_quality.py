@@ -10,7 +10,10 @@ writes the table as JSON.
 
 `--conditioning replace dps` adds rows of gradient guidance (impute(conditioning="dps")) for every `--guidance-scale` and every
 `--jacobian` setting (on: with the network's Jacobian, off: Jacobian-free).  `--time-domain` trains the model on the time-domain
-representation instead (standardised all the same).  The defaults reproduce the table of the projection alone."""
+representation instead (standardised all the same).  `--conditioning ... smc` adds rows of the twisted particle filter
+(impute(conditioning="smc"), K particles per series) for every `--obs-std` and every `--jacobian` setting, with the mean log
+evidence, the final ESS / K and the resamples per series next to the scores.  The defaults reproduce the table of the projection
+alone."""
 from __future__ import annotations
 
 import argparse
@@ -38,7 +41,8 @@ def main() -> None:
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--C", type=int, default=4)
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--conditioning", nargs="+", choices=["replace", "dps"], default=["replace"])
+    ap.add_argument("--conditioning", nargs="+", choices=["replace", "dps", "smc"], default=["replace"])
+    ap.add_argument("--obs-std", type=float, nargs="+", default=[0.1])
     ap.add_argument("--guidance-scale", type=float, nargs="+", default=[1.0])
     ap.add_argument("--jacobian", nargs="+", choices=["on", "off"], default=["on"])
     ap.add_argument("--time-domain", action="store_true")
@@ -86,6 +90,12 @@ def main() -> None:
         if cond == "replace":
             variants.append(({}, {}))
             continue
+        if cond == "smc":
+            for jac in args.jacobian:
+                for sd in args.obs_std:
+                    variants.append((dict(conditioning="smc", obs_std=sd, guidance_jacobian=jac == "on", return_info=True),
+                                     {"conditioning": "smc", "obs_std": sd, "guidance_jacobian": jac == "on"}))
+            continue
         for jac in args.jacobian:
             for zeta in args.guidance_scale:
                 variants.append((dict(conditioning="dps", guidance_scale=zeta, guidance_jacobian=jac == "on"),
@@ -100,6 +110,12 @@ def main() -> None:
                 t0 = time.perf_counter()
                 X = sampler.impute(observed, mask, N, fourier_transform=fourier, feature_mean=mean, feature_std=std, num_samples=K,
                                    **kw)
+                if kw.get("return_info"):
+                    X, info = X
+                    extra = {**extra, "log_evidence_mean": float(info.log_evidence.mean()),
+                             "ess_final_over_K": float(info.ess[-1].mean()) / K,
+                             "resamples_per_series": float(info.resampled.double().sum(0).mean()),
+                             "degenerate": int(info.degenerate.sum())}
                 torch.cuda.synchronize()
                 sec = time.perf_counter() - t0
                 if fourier:
