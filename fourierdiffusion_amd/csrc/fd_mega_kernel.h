@@ -76,6 +76,12 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 #ifndef FD_STATIC_UNITS
 #define FD_STATIC_UNITS 1
 #endif
+#ifndef FD_RAGGED_MERGE
+#define FD_RAGGED_MERGE 1   // static odd tile counts with a ragged last tile of <= 8 tokens: both heads of a pair share that tile (keys; queries in the single-tile units)
+#endif
+#ifndef FD_RAGGED_HANDOUT
+#define FD_RAGGED_HANDOUT 1 // with FD_RAGGED_MERGE: the (light) single-tile units go to the SIMDs that got no extra two-tile unit
+#endif
 #ifndef FD_PROF_UNITS
 #define FD_PROF_UNITS 0
 #endif
@@ -100,6 +106,70 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 FD_MEGA_NS_BEGIN
 
 constexpr float kNegBig = -1.0e30f;
+
+// Lane masks of the merged ragged key tile (RAGGED_MERGE in k_mega; lane = 16 g + tok).  They are compile-time constants, so a select
+// on them (lane_in<M>) is one v_cndmask on an SGPR pair and no compare: the units are VALU-issue bound.
+//   K: row tok keeps its K words where row and k-slot group g name the same head (rows [0, RH) even head, [RH, 2 RH) odd head)
+//   V: V^T row tok (rows 0-7 even head, 8-15 odd head) keeps its words where the score rows 4g .. 4g+3 belong to that head
+//   C(r): score row 4g + r is dead (beyond 2 RH) or a key beyond the R real ones
+template <unsigned long long M>
+__device__ __forceinline__ bool lane_in(int lane) {
+#if __has_builtin(__builtin_amdgcn_inverse_ballot_w64) && !defined(FD_NO_INVERSE_BALLOT)
+    (void)lane;
+    return __builtin_amdgcn_inverse_ballot_w64(M);
+#else                       // compilers without the builtin (older hiprtc images): a shift and a test per select
+    return ((M >> lane) & 1ull) != 0ull;
+#endif
+}
+constexpr unsigned long long ragged_kmask(int RH) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int tok = l & 15, g = l >> 4;
+        if (tok < 2 * RH && (tok < RH) == (g < 2)) m |= 1ull << l;
+    }
+    return m;
+}
+constexpr unsigned long long ragged_vmask(int RH) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int tok = l & 15, g = l >> 4;
+        const bool row_even = RH == 4 ? g == 0 : g < 2, row_odd = RH == 4 ? g == 1 : g >= 2;
+        if (tok < 8 ? row_even : row_odd) m |= 1ull << l;
+    }
+    return m;
+}
+// Merged ragged QUERY tile (the single-tile units): column tok < RH is query tok of the even head, column RH + tok the same query of
+// the odd head.  Q(own): lanes whose own Q words stay (even head's k-slot groups of the even columns); C(r): as ragged_cmask, plus the
+// rows of the merged KEY tile that belong to the other head than the column (they would score 0, i.e. P = 1, or overflow in the
+// exact form); V: the lanes whose row sums are real (after the odd head's columns moved back: every lane group, columns < RH)
+constexpr unsigned long long ragged_qmask(int RH) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l)
+        if ((l & 15) < RH && (l >> 4) < 2) m |= 1ull << l;
+    return m;
+}
+constexpr unsigned long long ragged_qcmask(int RH, int R, int r) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int row = 4 * (l >> 4) + r, tok = l & 15;
+        if (row >= 2 * RH || (row & (RH - 1)) >= R || (tok < 2 * RH && (row < RH) != (tok < RH))) m |= 1ull << l;
+    }
+    return m;
+}
+constexpr unsigned long long ragged_qvalid(int RH) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l)
+        if ((l & 15) < RH) m |= 1ull << l;
+    return m;
+}
+constexpr unsigned long long ragged_cmask(int RH, int R, int r) {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int row = 4 * (l >> 4) + r;
+        if (row >= 2 * RH || (row & (RH - 1)) >= R) m |= 1ull << l;
+    }
+    return m;
+}
 
 __device__ __forceinline__ float relu_bits(float x) {
     int i = __builtin_bit_cast(int, x);
@@ -262,6 +332,23 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
     // take the softmax denominators from one more P V-shaped MFMA per key block whose A operand is all ones (the matrix pipe has
     // slack in the units, the VALU has none)
     constexpr bool HD8 = (KS1 == 3 && DT == 5 && KSO == 2) || (KS1 == 2 && DT == 3 && KSO == 1);   // (d_model 64 / 8 heads, 32 / 4 heads)
+    // Ragged last key tile (T mod 16 = R real keys, R <= 8, odd tile count): the tile is less than half full, so ONE score tile
+    // serves both heads of a pair -- rows [0, RH) carry the even head's keys, rows [RH, 2 RH) the same keys for the odd head (RH = 4
+    // when R <= 4, else 8).  The head is selected in the K operand (the other head's k-slots zeroed), Q keeps both heads live.  Its
+    // P V product (V^T rows 0-7 against the even head's keys, rows 8-15 against the odd head's) is the initial accumulator of both
+    // heads' P V chains: the rows it spoils in each are the ones the epilogue discards anyway.  kbf / vbf keep their layout.
+    // The single-tile units, whose QUERY tile is that ragged tile, also run one chain of score tiles for both heads (QMERGE in do_unit).
+    // T = 100 per (pair, series): 85 score tiles / 340 exponentials instead of 98 / 392; instantiations with RAGGED_MERGE false compile
+    // to the same ISA as without this code (profiles/mega_ragged_merge_resources.txt).
+    constexpr bool RAGGED_MERGE = FD_RAGGED_MERGE && SH::KT > 0 && !FD_ROLLED_ATTN && !HD8 && (SH::KT & 1) && (SH::T & 15) >= 1 &&
+                                  (SH::T & 15) <= 8;
+    constexpr int RH = (SH::T & 15) <= 4 ? 4 : 8;
+    constexpr unsigned long long RKM = ragged_kmask(RH), RVM = ragged_vmask(RH);
+    constexpr unsigned long long RCM[4] = {ragged_cmask(RH, SH::T & 15, 0), ragged_cmask(RH, SH::T & 15, 1), ragged_cmask(RH, SH::T & 15, 2),
+                                           ragged_cmask(RH, SH::T & 15, 3)};
+    constexpr unsigned long long RQM = ragged_qmask(RH), RQV = ragged_qvalid(RH);
+    constexpr unsigned long long RQC[4] = {ragged_qcmask(RH, SH::T & 15, 0), ragged_qcmask(RH, SH::T & 15, 1), ragged_qcmask(RH, SH::T & 15, 2),
+                                           ragged_qcmask(RH, SH::T & 15, 3)};
     constexpr bool F32 = SH::FFN32 != 0;         // pair form of the FFN (see ShapeStatic)
     constexpr int KS32 = DT;                     // pair form: k-steps of 16 (D + 1 <= 16 DT)
     static_assert(!F32 || (NW == 8 && DT == 2 * KS1 - 1 &&
@@ -712,6 +799,22 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                         const u32x2 w = {mine ? qraw[q][0] : 0u, mine ? qraw[q][1] : 0u};
                         return __builtin_bit_cast(s16x4, w);
                     };
+                    // Single-tile units under RAGGED_MERGE: their query tile is the ragged one, so both heads share ONE chain of score
+                    // tiles.  Column tok < RH keeps the even head's words of query tok; column RH + tok gets the odd head's words of
+                    // query tok (one DPP row shift per word inside lane groups 2-3); everything else is zero.  The K / V^T fragments
+                    // serve it unmodified, each column's output lies in the rows of its head, and the odd head's columns are shifted
+                    // back in front of the epilogue, which then runs as for every other unit.
+                    constexpr bool QMERGE = RAGGED_MERGE && NQ == 1;
+                    constexpr int NHS = QMERGE ? 1 : 2;     // chains per query tile
+                    auto merge_q = [&](const u32x2 w) -> s16x4 {
+                        u32x2 r;
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            const unsigned own = lane_in<RQM>(lane) ? w[i] : 0u;
+                            r[i] = (unsigned)__builtin_amdgcn_update_dpp((int)own, (int)w[i], 0x110 + RH, 0xc, RH == 4 ? 0x2 : 0xc, false);
+                        }
+                        return __builtin_bit_cast(s16x4, r);
+                    };
                     // keys beyond T in the ragged last tile: masked through the MFMA's C operand
                     f32x4 cmask;
 #pragma unroll
@@ -726,6 +829,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                     // operands are then two masked copies: 14 VALU instructions fewer per unit than masking first and
                     // patching each copy, and only the 4 raw words stay live for the exact path.
                     s16x4 qs[NQ][2];
+                    s16x4 qsb[RAGGED_MERGE ? NQ : 1];      // merged ragged key tile: both heads live, each with its own bound
                     {
                         const float k2 = reinterpret_cast<const float*>(kmax)[(pr * S + ser) * 2 + (g >> 1)];
                         const bool slot_here = (g & 1) == (hd >> 2);
@@ -745,7 +849,25 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             const u32x2 qo = {lo_grp ? 0u : w0, lo_grp ? 0u : w1};
                             qs[q][0] = __builtin_bit_cast(s16x4, qe);
                             qs[q][1] = __builtin_bit_cast(s16x4, qo);
+                            if constexpr (QMERGE) qs[q][0] = merge_q(u32x2{w0, w1});
+                            else if constexpr (RAGGED_MERGE) qsb[q] = __builtin_bit_cast(s16x4, u32x2{w0, w1});
                         }
+                    }
+                    // merged ragged key tile (see RAGGED_MERGE): C-operand mask of its rows 4g + r (dead rows and keys beyond T),
+                    // the head a row belongs to, and which lanes keep their K row / V^T words
+                    f32x4 cmaskm;
+                    const bool mrow_even = RH == 4 ? g == 0 : g < 2, mrow_odd = RH == 4 ? g == 1 : g >= 2;
+                    if constexpr (RAGGED_MERGE) {
+                        cmaskm[0] = lane_in<RCM[0]>(lane) ? kNegBig : 0.f;
+                        cmaskm[1] = lane_in<RCM[1]>(lane) ? kNegBig : 0.f;
+                        cmaskm[2] = lane_in<RCM[2]>(lane) ? kNegBig : 0.f;
+                        cmaskm[3] = lane_in<RCM[3]>(lane) ? kNegBig : 0.f;
+                    }
+                    if constexpr (QMERGE) {
+                        cmaskm[0] = lane_in<RQC[0]>(lane) ? kNegBig : 0.f;
+                        cmaskm[1] = lane_in<RQC[1]>(lane) ? kNegBig : 0.f;
+                        cmaskm[2] = lane_in<RQC[2]>(lane) ? kNegBig : 0.f;
+                        cmaskm[3] = lane_in<RQC[3]>(lane) ? kNegBig : 0.f;
                     }
                     float m2[NQ][2];
                     f32x4 o2[NQ][2];
@@ -758,7 +880,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                     for (int q = 0; q < NQ; ++q)
 #pragma unroll
                         for (int hs = 0; hs < 2; ++hs) {
-                            if (EXACT) qb[q][hs] = qmasked(q, hs);
+                            if constexpr (QMERGE) {
+                                if (EXACT && hs == 0) qb[q][0] = merge_q(qraw[q]);
+                            } else if (EXACT) qb[q][hs] = qmasked(q, hs);
                             m2[q][hs] = kNegBig;
                             o2[q][hs] = f4zero();
                             if (HD8) l2[HD8 ? q : 0][hs] = f4zero();
@@ -830,26 +954,71 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                     if (HD8) l2[HD8 ? q : 0][hs] = MFMA(ones8, pkj, l2[HD8 ? q : 0][hs]);
                                 }
                         }
-                    } else
-                    for (int kb = 0; kb < KT; kb += 8) {
+                    } else {
+                    // key tiles / V^T blocks of the pipelined loop: the merged ragged tile is not one of them
+                    const int KTL = RAGGED_MERGE ? KT - 1 : KT, NJL = RAGGED_MERGE ? NJ - 1 : NJ;
+                    if constexpr (RAGGED_MERGE) {
+                        // The merged ragged tile runs first: its P V tile becomes the initial accumulator of both heads.
+                        // K: lane (row rho = tok, g) takes the 8-byte row of key (KT-1)*16 + (rho & (RH-1)), kept where row and k-slot
+                        // group name the same head.  V^T: the last block's words of lane group g & (RH/4 - 1) (keys 4 (g & ..) + i of
+                        // the tile), kept where V^T row (tok) and score-row group name the same head; the block's upper 8 bytes (the
+                        // missing even tile) are zeros and meet the zero half of the packed P.
+                        const u32x2 kraw = *reinterpret_cast<const u32x2*>(
+                            kbf + ((size_t)(pr * NTOK + (ser * KT + KT - 1) * 16 + (tok & (RH - 1))) * 4 + g) * 8);
+                        const bool kkeep = lane_in<RKM>(lane);
+                        const s16x4 kfm = __builtin_bit_cast(s16x4, u32x2{kkeep ? kraw[0] : 0u, kkeep ? kraw[1] : 0u});
+                        const u32x2 vraw = *reinterpret_cast<const u32x2*>(
+                            vbf + ((size_t)(((pr * S + ser) * NJ + NJ - 1) * 4 + (g & (RH / 4 - 1))) * 16 + tok) * 16);
+                        const bool vkeep = lane_in<RVM>(lane);
+                        const bf16x8 vfm = __builtin_bit_cast(bf16x8, u32x4{vkeep ? vraw[0] : 0u, vkeep ? vraw[1] : 0u, 0u, 0u});
+                        f32x4 sc[NQ];
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q) {
+                            if constexpr (QMERGE) sc[q] = MFMA16(kfm, EXACT ? qb[q][0] : qs[q][0], cmaskm);
+                            else if (EXACT) sc[q] = MFMA16(kfm, __builtin_bit_cast(s16x4, qraw[q]), cmaskm);
+                            else sc[q] = MFMA16(kfm, qsb[q], cmaskm);
+                        }
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q) {
+                            if (EXACT) {
+                                // exact maxima per head over the tile's live rows; later blocks rescale as usual
+                                const float bb = fmaxf(fmaxf(sc[q][0], sc[q][1]), fmaxf(sc[q][2], sc[q][3]));
+                                if constexpr (QMERGE) {      // a column holds one head: the other head's rows are masked
+                                    m2[q][0] = group_max(bb);
+                                } else {
+                                    m2[q][0] = group_max(mrow_even ? bb : kNegBig);
+                                    m2[q][1] = group_max(mrow_odd ? bb : kNegBig);
+                                }
+                                const float mm = (!QMERGE && mrow_odd) ? m2[q][1] : m2[q][0];
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) sc[q][r] -= mm;
+                            }
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) sc[q][r] = FD_EXP2(sc[q][r]);
+                            const f32x4 rg = MFMA(vfm, pack8(sc[q], f4zero()), f4zero());
+                            o2[q][0] = rg;
+                            if constexpr (!QMERGE) o2[q][1] = rg;
+                        }
+                    }
+                    for (int kb = 0; kb < KTL; kb += 8) {
                         // K and V fragments of this 128-key block: one read serves both heads and all NQ query tiles
                         s16x4 kf[8];
                         bf16x8 vf[4];
 #pragma unroll
                         for (int j = 0; j < 8; ++j)
-                            if (kb + j < KT)
+                            if (kb + j < KTL)
                                 kf[j] = *reinterpret_cast<const s16x4*>(
                                     kbf + ((size_t)(pr * NTOK + (ser * KT + kb + j) * 16 + tok) * 4 + g) * 8);
 #pragma unroll
                         for (int jj = 0; jj < 4; ++jj)
-                            if ((kb >> 1) + jj < NJ)
+                            if ((kb >> 1) + jj < NJL)
                                 vf[jj] = *reinterpret_cast<const bf16x8*>(
                                     vbf + ((size_t)(((pr * S + ser) * NJ + (kb >> 1) + jj) * 4 + g) * 16 + tok) * 16);
                         // Both passes are software-pipelined by hand, a few MFMAs ahead of their consumers, and
                         // fenced per stage: left alone hipcc issues MFMA -> s_nop 7 -> 4 exps strictly in sequence.
                         // Tile index k = ((hs * 4 + jj) * NQ + q) * 2 + jl with key tile j = 2 jj + jl.
-                        const int nk = min(8, KT - kb);                 // key tiles in this block
-                        constexpr int NKT = 16 * NQ;                    // score tiles per block
+                        const int nk = min(8, KTL - kb);                // key tiles in this block
+                        constexpr int NKT = 8 * NHS * NQ;              // score tiles per block
                         umark(10, step);
                         if (EXACT) {
                             // pass 1 (exact path only): row maxima; the scores are recomputed in pass 2 with -max
@@ -882,7 +1051,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
 #pragma unroll
                             for (int q = 0; q < NQ; ++q)
 #pragma unroll
-                                for (int hs = 0; hs < 2; ++hs) {
+                                for (int hs = 0; hs < NHS; ++hs) {
                                     const float mnew = fmaxf(m2[q][hs], group_max(bm[q][hs]));
                                     const float alpha = __builtin_amdgcn_exp2f(m2[q][hs] - mnew);
                                     o2[q][hs] = o2[q][hs] * alpha;
@@ -945,6 +1114,16 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             }
                         }
                     }
+                    if constexpr (QMERGE) {
+                        // the odd head's columns [RH, 2 RH) back to the lanes of their queries: from here on lane groups 2-3 read
+                        // o2[.][1] as in every other unit (lanes that shift in nothing get zeros)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float v = o2[0][0][r];          // (a scalar copy: __builtin_bit_cast of a vector element reads element 0)
+                            o2[0][1][r] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x100 + RH, 0xf, 0xf, false));
+                        }
+                    }
+                    }
                     };
                     // row sums of P: O^T rows 8*hs + [0,8) live in lane groups 2hs, 2hs+1; row 8*hs + hd is the ones row.
                     // hd in [4,7]: register hd-4 of the odd lane group; hd < 4: register hd of the even one
@@ -964,6 +1143,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             float row_even, row_odd;
                             swap16(cand, row_even, row_odd);
                             lrow[q] = (hd >= 4) ? row_odd : row_even;
+                            // (columns >= RH of a merged query tile hold no query: they neither vote nor divide by their sum, which
+                            //  can be 0 -- their store, like every padded query's, only has to be finite)
+                            if constexpr (QMERGE) lrow[q] = lane_in<RQV>(lane) ? lrow[q] : 1.0f;
                             bad |= !(lrow[q] > 7.8e-31f);                 // 2^-100; also catches NaN
                         }
                         return bad;
@@ -1007,7 +1189,24 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                     // Static hand-out: wave w runs units w, w + NW, ...  (The dynamic LDS counter balanced the per-wave times
                     // but never changed the phase time -- a wave left alone on its SIMD runs at nearly the throughput of two --
                     // and cost an LDS atomic round trip, ~12 VALU instructions and a wait for the weight prefetch per unit.)
-                    for (int u = wave; u < NU; u += NW) {
+                    // Under RAGGED_MERGE a single-tile unit costs about a quarter of a two-tile one (28 against 104 exponentials at
+                    // T = 100), so the plain order -- the ND % NW left-over two-tile units to waves 0.., the singles to the waves
+                    // behind them -- loads the SIMDs (wave & 3) of the left-over two-tile units most.  With 1 .. 3 left-overs the
+                    // singles go round robin to the waves of the OTHER SIMDs only (T = 100, 3 pairs x 2 series: 520 | 520 | 500 | 500
+                    // exponentials per SIMD instead of 548 | 548 | 472 | 472).  Still static: slot i = wave + NW k maps to a unit.
+                    constexpr bool RHO = RAGGED_MERGE && FD_RAGGED_HANDOUT && NW == 8;
+                    const int RD = ND % NW, k0 = ND / NW, NE = 2 * (4 - RD);       // left-over two-tile units, their slot row, waves that take singles
+                    const bool spread = RHO && RD >= 1 && RD <= 3;
+                    const int NUX = spread ? NW * (k0 + (NU - ND + NE - 1) / NE) : NU;
+                    for (int i = wave; i < NUX; i += NW) {
+                        int u = i;
+                        if constexpr (RHO) {
+                            if (spread && i >= ND) {
+                                if ((wave & 3) < RD) break;
+                                u = ND + (i / NW - k0) * NE + (wave >> 2) * (4 - RD) + (wave & 3) - RD;
+                                if (u >= NU) break;
+                            }
+                        }
 #else
                     for (;;) {
                         int u = 0;
