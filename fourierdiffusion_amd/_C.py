@@ -187,6 +187,9 @@ _PROTOS = {
     "fd_variogram_score": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fd_ensemble_ranks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "fd_kernel_quadforms_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_kernel_quadforms": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, _vp, C.c_int, C.c_int,
+                                      _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

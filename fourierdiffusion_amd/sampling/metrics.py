@@ -3,7 +3,9 @@
 The distances run on the HIP engine (utils/wasserstein.py); results are plain Python floats / lists as in the reference.
 
 Not in the reference: `PrecisionRecall` and `Memorisation`, nearest-neighbour metrics in sample space (utils/neighbours.py), which
-see what a projection-based distance cannot -- a generator that replays its training set, or one that covers a single mode."""
+see what a projection-based distance cannot -- a generator that replays its training set, or one that covers a single mode; and
+`KernelTwoSample`, the kernel two-sample test (utils/two_sample.py), which puts a p-value on "can the samples be told apart from
+real data at this sample size"."""
 from __future__ import annotations
 
 import inspect
@@ -17,6 +19,7 @@ import torch
 from ..utils.fourier import dft, spectral_density
 from ..utils.neighbours import MAX_K, ball_counts, knn
 from ..utils.tensors import check_flat_array
+from ..utils.two_sample import DEFAULT_SCALES, MAX_COLUMNS, _check_scales, mmd_permutation_test
 from ..utils.wasserstein import WassersteinDistances
 
 
@@ -293,3 +296,60 @@ class Memorisation(Metric):
     @property
     def name(self) -> str:
         return "memorisation"
+
+
+class KernelTwoSample(Metric):
+    """Kernel two-sample test (Gretton et al. 2012) of the generated samples against real ones: the unbiased MMD^2 under a Gaussian
+    kernel mixture (bandwidths `scales` times the pooled mean squared pair distance) and the p-value of `n_permutations`
+    permutations of the pooled rows.
+      mmd2, mmd_p_value                  against the original samples
+      mmd2_holdout, mmd_p_value_holdout  (with `holdout_samples`) against real samples the model was not trained on
+      mmd2_self, mmd_p_value_self        (baseline) the two folds of the original samples against each other
+    A small p-value: the two sets can be told apart at this sample size.  `max_original` evaluates against a seeded subsample of the
+    real set."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 n_permutations: int = 200, scales=DEFAULT_SCALES, max_original: Optional[int] = None, random_seed: int = 0) -> None:
+        if isinstance(n_permutations, bool) or int(n_permutations) != n_permutations or not 1 <= n_permutations < MAX_COLUMNS:
+            raise ValueError(f"n_permutations={n_permutations} must be an integer in [1, {MAX_COLUMNS - 1}]")
+        if max_original is not None and (int(max_original) != max_original or max_original < 2):
+            raise ValueError(f"max_original={max_original} must be an integer >= 2")
+        if len(original_samples) < 2:
+            raise ValueError("KernelTwoSample needs at least two original samples")
+        if holdout_samples is not None and len(holdout_samples) < 2:
+            raise ValueError("KernelTwoSample needs at least two held-out samples")
+        self.scales = _check_scales(scales)
+        super().__init__(original_samples=original_samples)
+        self.n_permutations, self.max_original, self.random_seed = int(n_permutations), max_original, random_seed
+        n = self.original_samples.shape[0]
+        if max_original is not None and n > max_original:
+            keep = torch.from_numpy(subsample_indices(n, int(max_original), random_seed)).to(self.original_samples.device)
+            self.original_samples = self.original_samples[keep].contiguous()
+        self.holdout_samples = None
+        if holdout_samples is not None:
+            self.holdout_samples = check_flat_array(holdout_samples)
+            if self.holdout_samples.shape[1] != self.original_samples.shape[1]:
+                raise ValueError("original and held-out samples must have the same number of features")
+
+    def _test(self, samples: torch.Tensor, real: torch.Tensor, suffix: str) -> dict[str, float]:
+        res = mmd_permutation_test(samples, real, n_permutations=self.n_permutations, scales=self.scales, seed=self.random_seed)
+        return {f"mmd2{suffix}": float(res.mmd2), f"mmd_p_value{suffix}": float(res.p_value)}
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = check_flat_array(other_samples)
+        out = self._test(samples, self.original_samples, "")
+        if self.holdout_samples is not None:
+            out.update(self._test(samples, self.holdout_samples, "_holdout"))
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        n_samples = self.original_samples.shape[0]                    # two folds of the original samples, as the Wasserstein metrics
+        if n_samples // 2 < 2:
+            return {}
+        return self._test(self.original_samples[: n_samples // 2].contiguous(), self.original_samples[n_samples // 2:].contiguous(),
+                          "_self")
+
+    @property
+    def name(self) -> str:
+        return "kernel_two_sample"

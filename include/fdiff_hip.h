@@ -743,6 +743,43 @@ int fd_variogram_score(fd_ctx* ctx, const float* samples, const float* truth, co
 int fd_ensemble_ranks(fd_ctx* ctx, const float* samples, const float* truth, int n, int K, int T, int C, int32_t* below,
                       int32_t* equal, void* stream);
 
+/* Quadratic forms of the kernel two-sample test (NOT in the reference; Gretton et al. 2012: the unbiased MMD^2 with a permutation
+ * p-value is host arithmetic on them, utils/two_sample.py).  z (N, d) dense row-major fp32 device rows with finite entries, the two
+ * samples stacked; member (N, P) device bytes, 0 / non-zero = outside / inside the first group: column 0 the observed split, every
+ * other column a permutation of it.  scales: HOST doubles c_1..c_Q.
+ *   base2       bandwidth2 when > 0, else the mean squared distance over the pairs i != j in its closed form
+ *               2 sum_i ||z_i - mean||^2 / (N - 1), entirely in double (fixed order): pooled, the same under every permutation
+ *   k(a, b)     (1/Q) sum_q exp(-||a - b||^2 / (c_q base2)); base2 == 0 (all rows equal): k = 1
+ *   out_quad    (P) quad[p] = sum_{i != j} A[i,p] k(z_i, z_j) A[j,p]
+ *   out_rowsum  (N) rowsum[i] = sum_{j != i} k(z_i, z_j)
+ *   out_col0    (N) or NULL: col0[i] = sum_{j != i} k(z_i, z_j) A[j,0]
+ *   out_base2   (1) base2 as used
+ * One fused kernel (csrc/fd_mmd.hip): squared distances as in fd_knn_rows (rows centred by their column mean, fp32-MFMA expansion
+ * ||a||^2 + ||b||^2 - 2 a.b, clamped at 0), Q hardware exponentials per pair, the diagonal excluded by INDEX, and the product with
+ * the membership rows by a second fp32 MFMA fed from the first one's accumulator; the N x N matrix never exists.  The value of a
+ * pair does not depend on the tile it falls in nor on its orientation (i, j) / (j, i): every column's quad is the quadratic form of
+ * ONE symmetric matrix, so the permutation test is exactly level whatever the rounding.  P + 1 columns (one of ones, for rowsum)
+ * are accumulated 256 at a time; beyond that the column chunks go on a grid dimension and the distances are recomputed
+ * ceil((P + 1) / 256) times.
+ * Error.  A term passes at most c = 2048 fp32 additions (128 * min(16, max(1, tiles / 16)) streamed rows, tiles = ceil(N / 128))
+ * before it reaches double; everything after is double in a fixed order.  With u = 2^-24 and delta_ij the expansion error of
+ * fd_knn_rows, 2 (d + 3) u (||z_i - mean||^2 + ||z_j - mean||^2):
+ *   |quad~_p - quad_p| <= sum_{i != j} A_ip A_jp eps_ij + c u quad_p,   eps_ij = delta_ij / (min_q c_q base2) + 8 u
+ * (8 u: rounding of the exponent factor and of its product with d2, at most 0.74 u on a value <= 1; 2 u for v_exp_f32; under 4.4 u for
+ * the Q - 1 additions of the mixture); rowsum and col0 likewise with the sums over j.
+ * col_splits: 0 = automatic, else the number of workgroup columns the streamed rows are divided over (clipped to the number of
+ * row groups).  Partials go to work and are added in double in a fixed order by a second kernel; no atomics: results are
+ * bit-identical between runs and for every col_splits.  work: caller-owned device bytes, at least
+ * fd_kernel_quadforms_workspace_bytes of the same shape.
+ * FD_ERR_ARG: null pointer (out_col0 excepted), N < 2, d < 1, P outside [1, 1024], n_scales outside [1, 8], a scale that is not
+ * finite and > 0, a bandwidth2 that is not finite, col_splits < 0, N * d or N * P >= 2^31, a workspace that is too small. */
+int fd_kernel_quadforms_workspace_bytes(fd_ctx* ctx, int N, int d, int P, int col_splits, size_t* bytes);
+int fd_kernel_quadforms(fd_ctx* ctx, const float* z, int N, int d, const double* scales /* host */, int n_scales,
+                        double bandwidth2 /* <= 0: pooled mean pair distance */, const uint8_t* member /* (N, P) device */, int P,
+                        int col_splits /* 0: automatic */, double* out_quad /* (P) */, double* out_rowsum /* (N) */,
+                        double* out_col0 /* (N) or NULL */, double* out_base2 /* (1) device */, void* work, size_t work_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
