@@ -5,7 +5,8 @@ The distances run on the HIP engine (utils/wasserstein.py); results are plain Py
 Not in the reference: `PrecisionRecall` and `Memorisation`, nearest-neighbour metrics in sample space (utils/neighbours.py), which
 see what a projection-based distance cannot -- a generator that replays its training set, or one that covers a single mode; and
 `KernelTwoSample`, the kernel two-sample test (utils/two_sample.py), which puts a p-value on "can the samples be told apart from
-real data at this sample size"."""
+real data at this sample size"; and `DTWPrecisionRecall` / `DTWMemorisation`, the two nearest-neighbour metrics under banded dynamic
+time warping (utils/dtw.py), which see a training series replayed a few samples early or late as the copy it is."""
 from __future__ import annotations
 
 import inspect
@@ -16,6 +17,7 @@ from typing import Any, Optional
 import numpy as np
 import torch
 
+from ..utils.dtw import _series_shape, _window, dtw_ball_counts, dtw_knn
 from ..utils.fourier import dft, spectral_density
 from ..utils.neighbours import MAX_K, ball_counts, knn
 from ..utils.tensors import check_flat_array
@@ -24,6 +26,8 @@ from ..utils.wasserstein import WassersteinDistances
 
 
 class Metric(ABC):
+    views = ("time", "freq")          # the representations a MetricCollection binds the class in
+
     def __init__(self, original_samples: np.ndarray | torch.Tensor) -> None:
         self.original_samples = check_flat_array(original_samples)
 
@@ -74,7 +78,8 @@ class _View:
 
 class MetricCollection:
     """Same surface and result keys as the reference's collection (metrics.py:28-99): every partially instantiated metric is bound
-    to the original samples once per view -- `time` (the samples as they are) and `freq` (their dft) -- and, on request, a marginal
+    to the original samples once per view its class names in `views` (every class of the reference: both) -- `time` (the samples as
+    they are) and `freq` (their dft) -- and, on request, a marginal
     Wasserstein on the spectral densities forms a third view (`spectral`, seed 42, all distances kept, no baselines).  A call
     returns the union of the views' results (+ the time / freq baselines) sorted by key.
 
@@ -91,14 +96,15 @@ class MetricCollection:
         holdout = _as_tensor(holdout_samples) if holdout_samples is not None and len(holdout_samples) > 0 else None
         self._views = [_View("time", lambda x: x, []), _View("freq", dft, [])]
         for view in self._views:
-            if factories:
+            wanted = [make for make in factories if view.prefix in getattr(make.func, "views", Metric.views)]
+            if wanted:
                 bound_to = view.transform(original)
                 if holdout is None:
-                    view.metrics = [make(original_samples=bound_to) for make in factories]
+                    view.metrics = [make(original_samples=bound_to) for make in wanted]
                 else:
                     held = view.transform(holdout)
                     view.metrics = [make(original_samples=bound_to, holdout_samples=held) if _takes_holdout(make)
-                                    else make(original_samples=bound_to) for make in factories]
+                                    else make(original_samples=bound_to) for make in wanted]
         self.include_baselines = include_baselines
         self.metric_spectral = None
         self._spectral_view = None
@@ -219,16 +225,23 @@ class PrecisionRecall(Metric):
             keep = torch.from_numpy(subsample_indices(n, int(max_original), random_seed)).to(self.original_samples.device)
             self.original_samples = self.original_samples[keep].contiguous()
 
+    # the two distance primitives (flat (n, d) device rows in, as utils/neighbours.py): what a subclass under another distance swaps
+    def _knn(self, queries: torch.Tensor, references: torch.Tensor, k: int, exclude_self: bool = False):
+        return knn(queries, references, k, exclude_self=exclude_self)
+
+    def _ball_counts(self, queries: torch.Tensor, references: torch.Tensor, radii: torch.Tensor) -> torch.Tensor:
+        return ball_counts(queries, references, radii)
+
     def _radii(self, samples: torch.Tensor) -> torch.Tensor:
-        return knn(samples, samples, self.k, exclude_self=True)[0][:, self.k - 1].contiguous()
+        return self._knn(samples, samples, self.k, exclude_self=True)[0][:, self.k - 1].contiguous()
 
     def _evaluate(self, real: torch.Tensor, generated: torch.Tensor) -> dict[str, float]:
         if generated.shape[0] <= self.k:
             raise ValueError(f"{generated.shape[0]} samples cannot supply k={self.k} neighbours of a sample in its own set")
         radii_real, radii_gen = self._radii(real), self._radii(generated)
-        in_real = ball_counts(generated, real, radii_real)            # per generated sample: real balls it falls in
-        in_gen = ball_counts(real, generated, radii_gen)
-        nearest_gen = knn(real, generated, 1)[0][:, 0]
+        in_real = self._ball_counts(generated, real, radii_real)      # per generated sample: real balls it falls in
+        in_gen = self._ball_counts(real, generated, radii_gen)
+        nearest_gen = self._knn(real, generated, 1)[0][:, 0]
         return {"precision": float((in_real > 0).double().mean()),
                 "recall": float((in_gen > 0).double().mean()),
                 "density": float(in_real.sum()) / (self.k * generated.shape[0]),
@@ -279,23 +292,99 @@ class Memorisation(Metric):
                 keep = torch.from_numpy(subsample_indices(n, h, random_seed)).to(self.original_samples.device)
                 self.train_subset = self.original_samples[keep].contiguous()
 
+    def _knn(self, queries: torch.Tensor, references: torch.Tensor, k: int, exclude_self: bool = False):
+        """The distance primitive (flat (n, d) device rows in): what a subclass under another distance swaps."""
+        return knn(queries, references, k, exclude_self=exclude_self)
+
     def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
         samples = check_flat_array(other_samples)
-        dist, nearest = knn(samples, self.original_samples, 1)
+        dist, nearest = self._knn(samples, self.original_samples, 1)
         dist, nearest = dist[:, 0], nearest[:, 0]
-        own = knn(self.original_samples, self.original_samples, 1, exclude_self=True)[0][:, 0]
+        own = self._knn(self.original_samples, self.original_samples, 1, exclude_self=True)[0][:, 0]
         host = dist.double().cpu().numpy()
         out = {"authenticity": float((dist > own[nearest]).double().mean()),
                "nn_distance_min": float(host.min()), "nn_distance_median": float(np.median(host))}
         if self.holdout_samples is not None:
-            to_train = knn(samples, self.train_subset, 1)[0][:, 0]
-            to_held = knn(samples, self.holdout_samples, 1)[0][:, 0]
+            to_train = self._knn(samples, self.train_subset, 1)[0][:, 0]
+            to_held = self._knn(samples, self.holdout_samples, 1)[0][:, 0]
             out["train_closer_share"] = float((to_train < to_held).double().mean() + 0.5 * (to_train == to_held).double().mean())
         return out
 
     @property
     def name(self) -> str:
         return "memorisation"
+
+
+class _DTWDistance:
+    """Mixin of the two DTW metrics: takes the series shape (T, C) from the original samples BEFORE the base class flattens them,
+    resolves the window, and answers the base class's distance hooks with utils/dtw.py on the rows folded back to (n, T, C).  Result
+    keys get the prefix `dtw_`.  Warping a spectrum is meaningless: bound in the time view only."""
+    views = ("time",)
+
+    def _take_shape(self, original_samples, window) -> None:
+        if len(tuple(original_samples.shape)) != 3:
+            raise ValueError(f"{type(self).__name__} needs the original samples as (n, T, C) series, got shape "
+                             f"{tuple(original_samples.shape)}: a flat (n, d) array has lost its time axis")
+        _, T, C = _series_shape(original_samples, "original samples")
+        self.series_shape, self.window = (T, C), _window(window, T)
+
+    def _fold(self, rows: torch.Tensor) -> torch.Tensor:
+        T, C = self.series_shape
+        if rows.dim() != 2 or rows.shape[1] != T * C:
+            raise ValueError(f"samples of {tuple(rows.shape[1:])} features, the original samples are series of shape {(T, C)}")
+        return rows.view(rows.shape[0], T, C)
+
+    def _knn(self, queries, references, k, exclude_self=False):
+        q = self._fold(queries)
+        return dtw_knn(q, q if references is queries else self._fold(references), k, window=self.window, exclude_self=exclude_self)
+
+    def _ball_counts(self, queries, references, radii):
+        return dtw_ball_counts(self._fold(queries), self._fold(references), radii, window=self.window)
+
+
+def _dtw_keys(results: dict[str, Any]) -> dict[str, Any]:
+    return {f"dtw_{key}": val for key, val in results.items()}
+
+
+class DTWPrecisionRecall(_DTWDistance, PrecisionRecall):
+    """`PrecisionRecall` with every distance replaced by banded dynamic time warping (utils/dtw.py; `window`: an integer, None =
+    ceil(0.1 T), or "full"): small phase jitter no longer costs precision or recall.  Same formulas and arguments; keys
+    dtw_precision, dtw_recall, dtw_density, dtw_coverage and their `_self` baselines.  Needs (n, T, C) original samples."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, k: int = 5, max_original: Optional[int] = None,
+                 random_seed: int = 0, window=None) -> None:
+        self._take_shape(original_samples, window)
+        super().__init__(original_samples=original_samples, k=k, max_original=max_original, random_seed=random_seed)
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        return _dtw_keys(super().__call__(other_samples))
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        return _dtw_keys(super().baseline_metrics)
+
+    @property
+    def name(self) -> str:
+        return "dtw_precision_recall"
+
+
+class DTWMemorisation(_DTWDistance, Memorisation):
+    """`Memorisation` under banded dynamic time warping: a training series replayed a few samples early or late is found next to
+    its source row, where the Euclidean nearest neighbour is usually another row and the replay passes for authentic.  Same
+    formulas and arguments plus `window`; keys dtw_authenticity, dtw_nn_distance_min, dtw_nn_distance_median and (with a holdout)
+    dtw_train_closer_share.  Needs (n, T, C) original samples."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 random_seed: int = 0, window=None) -> None:
+        self._take_shape(original_samples, window)
+        super().__init__(original_samples=original_samples, holdout_samples=holdout_samples, random_seed=random_seed)
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        return _dtw_keys(super().__call__(other_samples))
+
+    @property
+    def name(self) -> str:
+        return "dtw_memorisation"
 
 
 class KernelTwoSample(Metric):

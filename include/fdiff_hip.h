@@ -709,6 +709,44 @@ int fd_knn_rows(fd_ctx* ctx, const float* q, int n, const float* r, int m, int d
 int fd_ball_counts(fd_ctx* ctx, const float* q, int n, const float* r, int m, int d, const float* radius2 /* (m) */,
                    int32_t* counts /* (n) */, void* stream);
 
+/* Dynamic time warping under a Sakoe-Chiba band, and the nearest-neighbour primitives under it (NOT in the reference; the
+ * time-warp-aware twins of fd_knn_rows / fd_ball_counts: DTWPrecisionRecall and DTWMemorisation in sampling/metrics.py are built on
+ * them).  Series a, b of shape (T, C), row-major as samples are stored, equal lengths, window w in [0, T - 1]:
+ *   c(i, j) = sum_c (a[i, c] - b[j, c])^2          D(0, 0) = c(0, 0)
+ *   D(i, j) = c(i, j) + min(D(i-1, j), D(i, j-1), D(i-1, j-1))   for |i - j| <= w, absent neighbours = +inf
+ *   dtw2(a, b; w) = D(T-1, T-1)                    (w = 0: squared Euclidean distance; w = T - 1: unconstrained; all channels warp
+ *                                                   together, "dependent" DTW)
+ * q (n, T, C) and r (m, T, C) are dense fp32 device arrays with finite entries; every distance is the SQUARED dtw2.
+ *   fd_dtw_pairs        dist2[i] = dtw2(a_i, b_i), a and b both (n, T, C); scratch from the context's arena.
+ *   fd_dtw_knn          for every query the k nearest reference series: dist2 (n, k) and idx (n, k), each row ascending in
+ *                       (distance, index), no index repeated.  1 <= k <= 16 and k <= m - exclude_self.  exclude_self = 1 needs
+ *                       q == r and n == m and never returns j == i.  Ties go to the lower index.
+ *   fd_dtw_ball_counts  counts[i] = #{ j : dtw2(q_i, r_j) <= radius2[j] }, radius2 (m) device fp32.
+ * One kernel serves all three (csrc/fd_dtw.hip): a (query, reference) pair per lane, the references read from an image transposed
+ * once into [tile of 64][t][c][lane], the query wave-uniform; the band is walked in blocks of 8 query rows held in registers, the
+ * row a block hands to the next lives in the LDS (min(T, 2 w + 8) words per lane); the n x m matrix never exists.  A cell is
+ *   D = fma(d_{C-1}, d_{C-1}, m + P),  m = the min of the three predecessors, d_c = a[i, c] - b[j, c] in fp32,
+ *   P = fma(d_{C-2}, d_{C-2}, ... fma(d_0, d_0, 0))  (C = 1: D = fma(d_0, d_0, m)),
+ * a pure function of the inputs: a value does not depend on the entry point, on the tiling or on the split, dtw2(a, b) ==
+ * dtw2(b, a) bit for bit, the distance fd_dtw_knn returns is bit for bit fd_dtw_pairs of the returned pair, and a bit-copy of a
+ * reference row returns that row at distance exactly 0.  All terms are non-negative and min is exact and monotone, so with D the
+ * float64 value |computed - D| <= 1.01 (C + 2) (2 T - 1) 2^-24 D: selection may exchange two references whose dtw2 differ by less
+ * than twice that, and a pair within it of its radius may be counted or not.
+ * Limits: 1 <= T <= 1024, C >= 1, a stored band column min(2 w + 1, T) <= 256; n * T * C, m * T * C and n * k below 2^31.
+ * work: caller-owned device bytes, at least the matching _workspace_bytes of the same shape (the image, and the per-split partial
+ * lists or counts).  The reference tiles are split over workgroups when the queries alone do not fill the device; partial lists
+ * are merged on (distance, index), partial counts are added in split order, no atomics: results are bit-identical between runs and
+ * for every split (the environment variable FDIFF_DTW_SPLITS forces a split count, read by the _workspace_bytes calls too).
+ * FD_ERR_ARG: null pointer, a shape < 1 or T > 1024, window outside [0, T - 1] or with a band column above 256, k out of range,
+ * exclude_self with q != r or n != m, a workspace that is too small, n * T * C, m * T * C or n * k >= 2^31. */
+int fd_dtw_pairs(fd_ctx* ctx, const float* a, const float* b, int n, int T, int C, int window, float* dist2 /* (n) */, void* stream);
+int fd_dtw_knn_workspace_bytes(fd_ctx* ctx, int n, int m, int T, int C, int window, int k, size_t* bytes);
+int fd_dtw_knn(fd_ctx* ctx, const float* q, int n, const float* r, int m, int T, int C, int window, int k, int exclude_self,
+               float* dist2 /* (n, k) */, int32_t* idx /* (n, k) */, void* work, size_t work_bytes, void* stream);
+int fd_dtw_ball_counts_workspace_bytes(fd_ctx* ctx, int n, int m, int T, int C, int window, size_t* bytes);
+int fd_dtw_ball_counts(fd_ctx* ctx, const float* q, int n, const float* r, int m, int T, int C, int window,
+                       const float* radius2 /* (m) */, int32_t* counts /* (n) */, void* work, size_t work_bytes, void* stream);
+
 /* Multivariate scores of a sample ensemble, per series (NOT in the reference; Gneiting and Raftery 2007, Scheuerer and Hamill
  * 2015): the per-entry scores of fd_ensemble_scores cannot tell a coherent ensemble from one whose members were permuted
  * independently at every entry, these can.  samples (n, K, T, C) fp32, truth (n, T, C), 1 <= K <= 1024; mask_u8 as in
