@@ -23,31 +23,26 @@
 //              d_0^2 .. d_{C-2}^2 started at 0 (C = 1: D = fma(d, d, m)): per channel one subtract and one FMA, one v_min3_f32, and for
 //              C > 1 one add.  A pure function of the inputs: the result does not depend on the entry point, the tiling or the split,
 //              and dtw2(a, b) == dtw2(b, a) bit for bit (x - y and y - x differ in sign only, min is exact).
-//   selection  per-lane k-best lists in registers over the tiles a wave visits ((distance, index) pairs, sorted), merged across the
-//              lanes by six rounds of lane exchange.  gridDim.y splits the reference tiles when the queries alone do not fill
-//              the device (FDIFF_DTW_SPLITS forces a count); every split writes its list and k_dtw_merge merges them.  Every
+//   selection  per-lane k-best lists in registers over the tiles a wave visits ((distance, index) pairs, sorted: KBest of
+//              fd_pairs.h, which also has the merge, the count sum and the split planning; fd_neighbours.hip uses the same), merged
+//              across the lanes by six rounds of lane exchange.  gridDim.y splits the reference tiles when the queries alone do not
+//              fill the device (FDIFF_DTW_SPLITS forces a count); every split writes its list and k_merge_lists (DtwTail) merges them.  Every
 //              comparison is on (distance, index), a strict total order: the result does not depend on the split.  Ball counts are
 //              integer partials added in split order.  No atomics anywhere: two runs are bit-identical.
 //   pairs      the same kernel with one useful lane per wave (the pair's row of b in its tile): n pairs cost what a search against
 //              64 references costs, and the value is by construction the one fd_dtw_knn returns for that pair.
-#include <hip/hip_runtime.h>
-
-#include <climits>
-#include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
-#include "fd_common.h"
+#include "fd_pairs.h"
 
 namespace {
+using namespace fdp;
 
 constexpr int LANES = 64;
 #ifndef FD_DTW_IB
 #define FD_DTW_IB 8
 #endif
 constexpr int IB = FD_DTW_IB;         // query rows of a block (the register column); the macro is for ablation builds
-constexpr int MAX_K = 16;
-constexpr int MAX_SPLITS = 64;
 constexpr int MAX_T = 1024;
 constexpr int MAX_BAND = 256;         // largest stored band column min(2 w + 1, T)
 constexpr int DTW_KNN = 0, DTW_COUNT = 1, DTW_PAIRS = 2;
@@ -153,33 +148,6 @@ __device__ __forceinline__ float dtw_tile(const float* __restrict__ x, const flo
     return result;
 }
 
-// ---------------------------------------------------------------------------------------------- k-best list
-__device__ __forceinline__ bool dtw_before(float a, int ai, float b, int bi) { return a < b || (a == b && ai < bi); }
-
-// KMAX (distance, index) pairs in registers, ascending; unused slots hold (+inf, INT_MAX), which nothing real comes after
-template <int KMAX>
-struct DtwBest {
-    float d[KMAX];
-    int i[KMAX];
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int p = 0; p < KMAX; ++p) { d[p] = INFINITY; i[p] = INT_MAX; }
-    }
-    __device__ __forceinline__ void push(float v, int j) {
-        if (!dtw_before(v, j, d[KMAX - 1], i[KMAX - 1])) return;
-        d[KMAX - 1] = v;
-        i[KMAX - 1] = j;
-#pragma unroll
-        for (int p = KMAX - 1; p > 0; --p) {
-            const bool sw = dtw_before(d[p], i[p], d[p - 1], i[p - 1]);
-            const float lo_d = sw ? d[p] : d[p - 1], hi_d = sw ? d[p - 1] : d[p];
-            const int lo_i = sw ? i[p] : i[p - 1], hi_i = sw ? i[p - 1] : i[p];
-            d[p - 1] = lo_d; d[p] = hi_d;
-            i[p - 1] = lo_i; i[p] = hi_i;
-        }
-    }
-};
-
 // ---------------------------------------------------------------------------------------------- kernels
 // img[((tile T + t) C + c) 64 + lane] = r[tile 64 + lane][t][c], 0 past row m
 __global__ __launch_bounds__(256) void k_dtw_image(const float* __restrict__ r, float* __restrict__ img, int m, int T, int C,
@@ -216,7 +184,7 @@ __global__ __launch_bounds__(LANES) void k_dtw(DtwArgs g) {
     if (MODE == DTW_PAIRS) { t0 = qi / LANES; t1 = t0 + 1; }
     else { t0 = blockIdx.y * g.tiles_per_split; t1 = min(g.ntiles, t0 + g.tiles_per_split); }
 
-    DtwBest<KMAX> best;
+    KBest<KMAX> best;
     best.init();
     int cnt = 0;
     for (int tile = t0; tile < t1; ++tile) {
@@ -251,34 +219,15 @@ __global__ __launch_bounds__(LANES) void k_dtw(DtwArgs g) {
     }
 }
 
-// one thread per query: the k best of the splits' lists
-template <int KMAX>
-__global__ __launch_bounds__(256) void k_dtw_merge(const float* __restrict__ pd, const int* __restrict__ pi, int splits, int n, int k,
-                                                   float* __restrict__ dist2, int32_t* __restrict__ idx) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    DtwBest<KMAX> best;
-    best.init();
-    for (int z = 0; z < splits; ++z) {
-        const size_t o = ((size_t)z * n + i) * KMAX;
-#pragma unroll
-        for (int p = 0; p < KMAX; ++p) best.push(pd[o + p], pi[o + p]);
+// the tail of the merge: distances and indices; an empty slot (the inputs were not finite) is index -1
+struct DtwTail {
+    float* dist2;
+    int32_t* idx;
+    __device__ void operator()(size_t o, float d, int j) const {
+        dist2[o] = d;
+        idx[o] = j == INT_MAX ? -1 : j;
     }
-#pragma unroll
-    for (int p = 0; p < KMAX; ++p)
-        if (p < k) {
-            dist2[(size_t)i * k + p] = best.d[p];
-            idx[(size_t)i * k + p] = best.i[p] == INT_MAX ? -1 : best.i[p];      // (an empty slot: the inputs were not finite)
-        }
-}
-
-__global__ __launch_bounds__(256) void k_dtw_sum_counts(const int* __restrict__ pc, int splits, int n, int32_t* __restrict__ counts) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int s = 0;
-    for (int z = 0; z < splits; ++z) s += pc[(size_t)z * n + i];
-    counts[i] = s;
-}
+};
 
 // ---------------------------------------------------------------------------------------------- host side
 struct DtwPlan {
@@ -286,47 +235,31 @@ struct DtwPlan {
     size_t lds, image_floats, o_img, o_pd, o_pi, bytes;
 };
 
-// splits of the reference tiles: one when the queries fill the device (a wave per query, about eight waves per CU), else enough to;
-// FDIFF_DTW_SPLITS forces a count (tests)
-void dtw_splits(const fd_ctx* ctx, int n, int ntiles, int* splits, int* tiles_per_split) {
-    int s = 1;
-    const char* e = getenv("FDIFF_DTW_SPLITS");
-    const int forced = e ? atoi(e) : 0;
-    const long long want = 8ll * ctx->num_cu;
-    if (forced > 0) s = forced;
-    else if (n < want) s = fd_cdiv(want, n);
-    s = std::min(s, std::min(ntiles, MAX_SPLITS));
-    *tiles_per_split = fd_cdiv(ntiles, s);
-    *splits = fd_cdiv(ntiles, *tiles_per_split);
-}
-
-// k = 0: counts (integer partials); pairs: m = n, one tile per wave, no partials
+// Splits of the reference tiles: one when the queries fill the device (a wave per query, about eight waves per CU), else enough to;
+// FDIFF_DTW_SPLITS forces a count (tests).  k = 0: counts (integer partials); pairs: m = n, one tile per wave, no partials
 DtwPlan dtw_plan(const fd_ctx* ctx, int n, int m, int T, int C, int w, int k, bool pairs) {
     DtwPlan p;
     p.ntiles = fd_cdiv(m, LANES);
     if (pairs) { p.splits = 1; p.tiles_per_split = 1; }
-    else dtw_splits(ctx, n, p.ntiles, &p.splits, &p.tiles_per_split);
+    else plan_splits("FDIFF_DTW_SPLITS", n < 8 * ctx->num_cu ? fd_cdiv(8 * ctx->num_cu, n) : 1, p.ntiles, &p.splits, &p.tiles_per_split);
     p.ring = std::min(T, 2 * w + IB);
     p.lds = (size_t)p.ring * LANES * sizeof(float);
     p.kmax = k <= 1 ? 1 : MAX_K;
     p.image_floats = (size_t)p.ntiles * LANES * T * C;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += fd_ws::padded(bytes); return o; };
-    p.o_img = take(p.image_floats * sizeof(float));
+    Carve ws;
+    p.o_img = ws.take(p.image_floats * sizeof(float));
     p.o_pd = p.o_pi = 0;
     if (!pairs) {
         if (k > 0) {
-            p.o_pd = take((size_t)p.splits * n * p.kmax * sizeof(float));
-            p.o_pi = take((size_t)p.splits * n * p.kmax * sizeof(int));
+            p.o_pd = ws.take((size_t)p.splits * n * p.kmax * sizeof(float));
+            p.o_pi = ws.take((size_t)p.splits * n * p.kmax * sizeof(int));
         } else {
-            p.o_pd = take((size_t)p.splits * n * sizeof(int));
+            p.o_pd = ws.take((size_t)p.splits * n * sizeof(int));
         }
     }
-    p.bytes = off + 256;                      // the caller's pointer is rounded up to 256 bytes
+    p.bytes = ws.bytes();
     return p;
 }
-
-char* dtw_align(void* work) { return (char*)(((uintptr_t)work + 255) & ~(uintptr_t)255); }
 
 // the checks every entry point shares; `who` is its name
 int dtw_check(fd_ctx* ctx, const char* who, int n, int m, int T, int C, int window) {
@@ -379,7 +312,7 @@ extern "C" int fd_dtw_pairs(fd_ctx* ctx, const float* a, const float* b, int n, 
     if (int rc = fd_ws_reserve(ctx, p.bytes)) return rc;
     ++ctx->ws_gen;
     hipStream_t s = (hipStream_t)stream;
-    float* img = (float*)(dtw_align(ctx->ws) + p.o_img);
+    float* img = (float*)(Carve::align(ctx->ws) + p.o_img);
     dtw_image(ctx, p, b, img, n, T, C, s);
     DtwArgs g = dtw_args(p, a, img, n, n, T, C, window);
     g.out = dist2;
@@ -411,20 +344,19 @@ extern "C" int fd_dtw_knn(fd_ctx* ctx, const float* q, int n, const float* r, in
     FD_REQUIRE(ctx, work_bytes >= p.bytes, "fd_dtw_knn: workspace of %zu bytes, fd_dtw_knn_workspace_bytes asks for %zu", work_bytes,
                p.bytes);
     hipStream_t s = (hipStream_t)stream;
-    char* base = dtw_align(work);
+    char* base = Carve::align(work);
     float* img = (float*)(base + p.o_img);
     dtw_image(ctx, p, r, img, m, T, C, s);
     DtwArgs g = dtw_args(p, q, img, n, m, T, C, window);
     g.exclude_self = exclude_self ? 1 : 0;
     g.pd = (float*)(base + p.o_pd);
     g.pi = (int*)(base + p.o_pi);
-    const dim3 gq(fd_cdiv(n, 256));
     if (p.kmax == 1) {
         if (int rc = dtw_launch<DTW_KNN, 1>(ctx, p, g, s)) return rc;
-        hipLaunchKernelGGL(k_dtw_merge<1>, gq, dim3(256), 0, s, g.pd, g.pi, p.splits, n, k, dist2, idx);
+        merge_lists<1>(g.pd, g.pi, p.splits, n, k, DtwTail{dist2, idx}, s);
     } else {
         if (int rc = dtw_launch<DTW_KNN, MAX_K>(ctx, p, g, s)) return rc;
-        hipLaunchKernelGGL(k_dtw_merge<MAX_K>, gq, dim3(256), 0, s, g.pd, g.pi, p.splits, n, k, dist2, idx);
+        merge_lists<MAX_K>(g.pd, g.pi, p.splits, n, k, DtwTail{dist2, idx}, s);
     }
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
@@ -447,14 +379,14 @@ extern "C" int fd_dtw_ball_counts(fd_ctx* ctx, const float* q, int n, const floa
     FD_REQUIRE(ctx, work_bytes >= p.bytes, "fd_dtw_ball_counts: workspace of %zu bytes, fd_dtw_ball_counts_workspace_bytes asks for %zu",
                work_bytes, p.bytes);
     hipStream_t s = (hipStream_t)stream;
-    char* base = dtw_align(work);
+    char* base = Carve::align(work);
     float* img = (float*)(base + p.o_img);
     dtw_image(ctx, p, r, img, m, T, C, s);
     DtwArgs g = dtw_args(p, q, img, n, m, T, C, window);
     g.rad2 = radius2;
     g.pc = (int*)(base + p.o_pd);
     if (int rc = dtw_launch<DTW_COUNT, 1>(ctx, p, g, s)) return rc;
-    hipLaunchKernelGGL(k_dtw_sum_counts, dim3(fd_cdiv(n, 256)), dim3(256), 0, s, g.pc, p.splits, n, counts);
+    sum_counts(g.pc, p.splits, n, counts, s);
     FD_LAUNCH_CHECK(ctx);
     return FD_OK;
 }

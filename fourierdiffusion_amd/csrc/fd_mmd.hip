@@ -7,9 +7,11 @@
 //
 // One fused kernel (k_mmd): the N x N kernel matrix never exists.
 //
-//   first product   as k_nn of fd_neighbours.hip: the pooled rows are centred by their column mean into a padded copy, a workgroup
-//                   owns 128 rows and streams 128-row tiles (16 features at a time) through the LDS; d2 = max(0, ||a||^2 + ||b||^2
-//                   - 2 a.b) on v_mfma_f32_32x32x2_f32 with the STREAMED rows as A (rows of D) and the OWNED rows as B (columns).
+//   first product   the centring and the tile loop of fd_pairs.h, which k_nn of fd_neighbours.hip uses too: the pooled rows are
+//                   centred by their column mean into a padded copy (here also the double mean and deviations, for the
+//                   bandwidth), a workgroup owns 128 rows and streams 128-row tiles (16 features at a time) through the LDS;
+//                   d2 = max(0, ||a||^2 + ||b||^2 - 2 a.b) on v_mfma_f32_32x32x2_f32 with the STREAMED rows as A (rows of D) and
+//                   the OWNED rows as B (columns).  What follows is this file's: the epilogue of that loop.
 //   exponentials    Q v_exp_f32 per pair on d2 * (-log2 e / (c_q base2)), summed in ascending q; the diagonal and the padding are
 //                   zeroed by index.  Every step is symmetric in (i, j) and independent of the tile, so k is one symmetric matrix.
 //   second product  in the C/D layout register r of a lane holds streamed row 8 (r / 4) + (r % 4) + 4 (lane >> 5) of owned row
@@ -27,72 +29,15 @@
 //                   term is therefore the 128 gt <= 2048 additions inside T.  gridDim.y (col_splits) hands whole groups to
 //                   workgroups; since every group's partial is written separately and k_mmd_reduce adds them in group order, the
 //                   result does not depend on the split.  No atomics: two runs are bit-identical.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-
-#include "fd_common.h"
+#include "fd_pairs.h"
 
 namespace {
+using namespace fdp;
 
-constexpr int TQ = 128, TR = 128, KC = 16, NT = 256, LDW = 128 + 4;
-constexpr int MEAN_ROWS = 512;       // rows per partial column sum
 constexpr int MAX_GROUP_TILES = 16;  // streamed tiles summed in fp32 before the hand-over to double
 constexpr int MAX_SCALES = 8, MAX_P = 1024;
-typedef float mmd_f32x16 __attribute__((ext_vector_type(16)));
 
-// ---------------------------------------------------------------------------------------------- centring, bandwidth, packing
-// partial column sums in double: block b = (row chunk b / ncb, column block b % ncb), rows in ascending order
-__global__ __launch_bounds__(256) void k_mmd_col_partial(const float* __restrict__ x, double* __restrict__ part, int m, int d, int ncb) {
-    const int chunk = blockIdx.x / ncb, c = (blockIdx.x - chunk * ncb) * 256 + threadIdx.x;
-    if (c >= d) return;
-    const int r0 = chunk * MEAN_ROWS, r1 = min(m, r0 + MEAN_ROWS);
-    double s = 0.0;
-#pragma unroll 8
-    for (int r = r0; r < r1; ++r) s += (double)x[(size_t)r * d + c];
-    part[(size_t)chunk * d + c] = s;
-}
-
-// the column mean (partials in chunk order) in double and rounded to f32, 0 in the padded columns
-__global__ __launch_bounds__(256) void k_mmd_col_mean(const double* __restrict__ part, double* __restrict__ meand, float* __restrict__ mean,
-                                                      int chunks, int m, int d, int dp) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= dp) return;
-    double s = 0.0;
-    if (c < d)
-        for (int z = 0; z < chunks; ++z) s += part[(size_t)z * d + c];
-    s /= (double)m;
-    meand[c] = s;
-    mean[c] = (float)s;
-}
-
-// zc (rows_pad, dp) = z - mean in f32, zero in the padding; norm[row] = ||zc[row]||^2 (double sum of the f32 values' squares); ss[row]
-// = ||z[row] - mean||^2 entirely in double (the bandwidth's closed form).  One wave per row.
-__global__ __launch_bounds__(256) void k_mmd_centre(const float* __restrict__ x, const float* __restrict__ mean,
-                                                    const double* __restrict__ meand, float* __restrict__ xc, float* __restrict__ norm,
-                                                    double* __restrict__ ss, int rows, int rows_pad, int d, int dp) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= rows_pad) return;
-    double s = 0.0, e = 0.0;
-    for (int c = lane; c < dp; c += 64) {
-        float v = 0.f;
-        if (row < rows && c < d) {
-            const float xv = x[(size_t)row * d + c];
-            v = xv - mean[c];
-            const double w = (double)xv - meand[c];
-            e += w * w;
-        }
-        xc[(size_t)row * dp + c] = v;
-        s += (double)v * (double)v;
-    }
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); e += __shfl_down(e, o); }
-    if (lane == 0) {
-        norm[row] = (float)s;
-        ss[row] = e;
-    }
-}
-
+// ---------------------------------------------------------------------------------------------- bandwidth, packing
 struct MmdScales { double c[MAX_SCALES]; };
 
 // base2 = bandwidth2 > 0 ? bandwidth2 : 2 sum_i ss[i] / (N - 1) (strided partials, then a fixed tree); sc[q] = -log2(e) / (c_q base2)
@@ -151,9 +96,6 @@ template <int NPT>
 __global__ __launch_bounds__(NT, 2) void k_mmd(MmdArgs g) {
     constexpr int W = 32 * NPT, MS = W + 8;  // MS: rows j and j + 4 of the membership tile fall into different banks
     static_assert(NPT == 1 || NPT == 2 || NPT == 4 || NPT == 8, "one LDS read of NPT bytes per kernel value");
-    __shared__ float Qs[KC][LDW];
-    __shared__ float Rs[KC][LDW];
-    __shared__ float aux[2][TR];             // [tile parity][row of the tile]: ||z_j||^2
     __shared__ __attribute__((aligned(8))) uint8_t Ms[TR * MS];
     __shared__ double red[4][NPT][32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
@@ -167,56 +109,15 @@ __global__ __launch_bounds__(NT, 2) void k_mmd(MmdArgs g) {
 #pragma unroll
     for (int q = 0; q < MAX_SCALES; ++q) sc[q] = g.sc[q];
 
-    mmd_f32x16 acc[4], T[NPT];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    FD_GRAM_ACC(acc);
+    f32x16 T[NPT];
 #pragma unroll
     for (int pt = 0; pt < NPT; ++pt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) T[pt][i] = 0.f;
 
-    // staging: thread -> (row = id / 4, features 4 (id % 4) .. + 3) of both 128 x 16 tiles, two ids per thread
-    float4 rq[2], rr[2];
-    float ra0 = 0.f;
-    auto gload = [&](int tile, int kc) {
-        const int j0 = tile * TR, k0 = kc * KC;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int id = tid + i * NT, row = id >> 2, kq = id & 3;
-            rq[i] = *reinterpret_cast<const float4*>(g.zc + (size_t)(q0 + row) * dp + k0 + 4 * kq);
-            rr[i] = *reinterpret_cast<const float4*>(g.zc + (size_t)(j0 + row) * dp + k0 + 4 * kq);
-        }
-        if (kc == 0 && tid < TR) ra0 = g.zn[j0 + tid];
-    };
-    auto sstore = [&](int tile, int kc) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int id = tid + i * NT, row = id >> 2, kq = id & 3;
-            Qs[4 * kq + 0][row] = rq[i].x; Qs[4 * kq + 1][row] = rq[i].y; Qs[4 * kq + 2][row] = rq[i].z; Qs[4 * kq + 3][row] = rq[i].w;
-            Rs[4 * kq + 0][row] = rr[i].x; Rs[4 * kq + 1][row] = rr[i].y; Rs[4 * kq + 2][row] = rr[i].z; Rs[4 * kq + 3][row] = rr[i].w;
-        }
-        if (kc == 0 && tid < TR) aux[tile & 1][tid] = ra0;
-    };
-
-    if (tbeg < tend) gload(tbeg, 0);
-    for (int tile = tbeg; tile < tend; ++tile) {
-        for (int kc = 0; kc < nkc; ++kc) {
-            sstore(tile, kc);
-            __syncthreads();
-            if (kc + 1 < nkc) gload(tile, kc + 1);
-            else if (tile + 1 < tend) gload(tile + 1, 0);
-            // 32x32x2: lane l holds row / column l & 31 of k-slot l >> 5; A = streamed rows (rows of D), B = owned rows (columns of D)
-#pragma unroll
-            for (int kk = 0; kk < KC / 2; ++kk) {
-                const int k = 2 * kk + half;
-                const float b = Qs[k][32 * wave + l31];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(Rs[k][32 * t + l31], b, acc[t], 0, 0, 0);
-            }
-            __syncthreads();
-        }
+    // aux: ||z_j||^2 of the streamed rows
+    FD_GRAM_TILES_BEGIN(1, 1, g.zc, g.zc, dp, nkc, q0, 0, tbeg, tend, ra0 = g.zn[j];)
         // the membership rows of this tile: every earlier reader of Ms is behind the barriers of the loop above
         const int j0 = tile * TR;
         for (int id = tid; id < TR * (W / 8); id += NT) {
@@ -230,13 +131,10 @@ __global__ __launch_bounds__(NT, 2) void k_mmd(MmdArgs g) {
         // streamed rows {rl, rl + 4}; the B operand of k-slot lane >> 5 is the membership row of the same rl.
         // Everything that depends on the lane is in three bases, so that every (t, i) below adds a compile-time constant c to them.
         const int jb = j0 + 4 * half, dself = oi - jb, dend = g.n - jb;      // c == dself: the diagonal; c >= dend: the padding
-        const float* an = aux[tile & 1] + 4 * half;
+        const float* an = aux[tile & 1][0] + 4 * half;
         const uint8_t* mlane = Ms + 4 * half * MS + l31 * NPT;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int c = 32 * t + 8 * (i >> 2) + (i & 3);
+        FD_GRAM_DRAIN(t, i) {
+                const int c = FD_GRAM_ROW(0, t, i, 0);
                 const float d2 = fmaxf(fmaf(-2.f, acc[t][i], onorm + an[c]), 0.f);
                 acc[t][i] = 0.f;
                 float kv = __builtin_amdgcn_exp2f(d2 * sc[0]);
@@ -273,7 +171,7 @@ __global__ __launch_bounds__(NT, 2) void k_mmd(MmdArgs g) {
                 double s = 0.0;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = q0 + 32 * wave + 8 * (r >> 2) + 4 * half + (r & 3);
+                    const int row = FD_GRAM_ROW(q0 + 32 * wave, 0, r, half);
                     const float v = T[pt][r];
                     s += g.mp[(size_t)row * pw + slot] ? (double)v : 0.0;
                     if (row < g.n) {
@@ -293,7 +191,7 @@ __global__ __launch_bounds__(NT, 2) void k_mmd(MmdArgs g) {
             }
             // red is rewritten at the next group's end, behind the barriers of at least one more tile
         }
-    }
+    FD_GRAM_TILES_END
 }
 
 // quad[p] = inv_q * sum over (group, row block) in ascending order; rowsum / col0 [i] = inv_q * sum over groups
@@ -323,7 +221,7 @@ __global__ __launch_bounds__(256) void k_mmd_reduce(const double* __restrict__ q
 
 // ---------------------------------------------------------------------------------------------- host side
 struct MmdPlan {
-    int dp, npad, ntiles, chunks, gt, groups, splits, groups_per_split, npt, pch, pw;
+    int dp, npad, ntiles, gt, groups, splits, groups_per_split, npt, pch, pw;
     size_t o_part, o_meand, o_mean, o_zc, o_zn, o_ss, o_sc, o_mp, o_qpart, o_rpart, bytes;
 };
 
@@ -331,10 +229,9 @@ struct MmdPlan {
 // is a whole number of groups, and the group length depends on N alone: the partial sums, hence the results, are those of every split.
 MmdPlan mmd_plan(const fd_ctx* ctx, int N, int d, int P, int col_splits) {
     MmdPlan p;
-    p.dp = fd_cdiv(d, KC) * KC;
-    p.npad = fd_cdiv(N, TQ) * TQ;
+    p.dp = padded_features(d);
+    p.npad = padded_rows(N);
     p.ntiles = p.npad / TR;
-    p.chunks = fd_cdiv(N, MEAN_ROWS);
     p.gt = std::max(1, std::min(MAX_GROUP_TILES, p.ntiles / 16));
     p.groups = fd_cdiv(p.ntiles, p.gt);
     const int pc = P + 1;
@@ -346,19 +243,18 @@ MmdPlan mmd_plan(const fd_ctx* ctx, int N, int d, int P, int col_splits) {
     s = std::min(s, p.groups);
     p.groups_per_split = fd_cdiv(p.groups, s);
     p.splits = fd_cdiv(p.groups, p.groups_per_split);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += fd_ws::padded(bytes); return o; };
-    p.o_part = take((size_t)p.chunks * d * sizeof(double));
-    p.o_meand = take((size_t)p.dp * sizeof(double));
-    p.o_mean = take((size_t)p.dp * sizeof(float));
-    p.o_zc = take((size_t)p.npad * p.dp * sizeof(float));
-    p.o_zn = take((size_t)p.npad * sizeof(float));
-    p.o_ss = take((size_t)p.npad * sizeof(double));
-    p.o_sc = take(MAX_SCALES * sizeof(float));
-    p.o_mp = take((size_t)p.npad * p.pw);
-    p.o_qpart = take((size_t)p.groups * p.ntiles * p.pw * sizeof(double));
-    p.o_rpart = take((size_t)p.groups * 2 * p.npad * sizeof(double));
-    p.bytes = off + 256;                      // the caller's pointer is rounded up to 256 bytes
+    Carve ws;
+    p.o_part = ws.take((size_t)mean_chunks(N) * d * sizeof(double));
+    p.o_meand = ws.take((size_t)p.dp * sizeof(double));
+    p.o_mean = ws.take((size_t)p.dp * sizeof(float));
+    p.o_zc = ws.take((size_t)p.npad * p.dp * sizeof(float));
+    p.o_zn = ws.take((size_t)p.npad * sizeof(float));
+    p.o_ss = ws.take((size_t)p.npad * sizeof(double));
+    p.o_sc = ws.take(MAX_SCALES * sizeof(float));
+    p.o_mp = ws.take((size_t)p.npad * p.pw);
+    p.o_qpart = ws.take((size_t)p.groups * p.ntiles * p.pw * sizeof(double));
+    p.o_rpart = ws.take((size_t)p.groups * 2 * p.npad * sizeof(double));
+    p.bytes = ws.bytes();
     return p;
 }
 
@@ -398,8 +294,7 @@ extern "C" int fd_kernel_quadforms(fd_ctx* ctx, const float* z, int N, int d, co
     FD_REQUIRE(ctx, work_bytes >= p.bytes, "fd_kernel_quadforms: workspace of %zu bytes, fd_kernel_quadforms_workspace_bytes asks for %zu",
                work_bytes, p.bytes);
     hipStream_t s = (hipStream_t)stream;
-    char* base = (char*)(((uintptr_t)work + 255) & ~(uintptr_t)255);
-    double* part = (double*)(base + p.o_part);
+    char* base = Carve::align(work);
     double* meand = (double*)(base + p.o_meand);
     float* mean = (float*)(base + p.o_mean);
     float* zc = (float*)(base + p.o_zc);
@@ -407,10 +302,8 @@ extern "C" int fd_kernel_quadforms(fd_ctx* ctx, const float* z, int N, int d, co
     double* ss = (double*)(base + p.o_ss);
     float* scf = (float*)(base + p.o_sc);
     uint8_t* mp = (uint8_t*)(base + p.o_mp);
-    const int ncb = fd_cdiv(d, 256);
-    hipLaunchKernelGGL(k_mmd_col_partial, dim3((unsigned)p.chunks * ncb), dim3(256), 0, s, z, part, N, d, ncb);
-    hipLaunchKernelGGL(k_mmd_col_mean, dim3(fd_cdiv(p.dp, 256)), dim3(256), 0, s, part, meand, mean, p.chunks, N, d, p.dp);
-    hipLaunchKernelGGL(k_mmd_centre, dim3(p.npad / 4), dim3(256), 0, s, z, mean, meand, zc, zn, ss, N, p.npad, d, p.dp);
+    centre_mean(z, N, d, (double*)(base + p.o_part), meand, mean, s);
+    centre_rows(z, N, d, mean, meand, zc, zn, ss, s);       // ss: ||z_i - mean||^2 in double, the bandwidth's closed form
     hipLaunchKernelGGL(k_mmd_bandwidth, dim3(1), dim3(256), 0, s, ss, N, bandwidth2, sc, n_scales, scf, out_base2);
     const size_t mp_total = (size_t)p.npad * p.pw;
     hipLaunchKernelGGL(k_mmd_pack, dim3((unsigned)((mp_total + 255) / 256)), dim3(256), 0, s, member, mp, N, P, p.pw, p.npt, mp_total);

@@ -13,16 +13,13 @@ matrix never exists, results are deterministic, ties go to the lower index, and 
 for bit ``dtw_pairs`` of that pair."""
 from __future__ import annotations
 
-import ctypes as C
 import operator
 
-import numpy as np
 import torch
 
 from .. import _C
-from .tensors import check_flat_array
+from ._pairs import MAX_K, call_with_workspace, check_k, check_radii, same_pair, squared_on  # noqa: F401  (MAX_K: public here)
 
-MAX_K = 16
 MAX_LENGTH = 1024
 MAX_BAND = 256        # the largest band column min(2 w + 1, T) the kernel stores
 
@@ -75,19 +72,13 @@ def _check_pair(a, b, what_a: str, what_b: str) -> tuple[int, int]:
     return T, Cn
 
 
-def _pair(a, b) -> tuple[torch.Tensor, torch.Tensor]:
-    x = check_flat_array(a)
-    y = x if a is b else check_flat_array(b).to(x.device)
-    return x, y
-
-
 def dtw_pairs(a, b, window=None) -> torch.Tensor:
     """(n,) float32 on the device: dtw(a_i, b_i) of the rows of two (n, T, C) sets."""
     T, Cn = _check_pair(a, b, "a", "b")
     if a.shape[0] != b.shape[0]:
         raise ValueError(f"a has {a.shape[0]} series and b {b.shape[0]}")
     w = _window(window, T)
-    x, y = _pair(a, b)
+    x, y = same_pair(a, b)
     dist2 = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
     h = _C.ctx(x.device)
     _C.check(_C.lib().fd_dtw_pairs(h, x.data_ptr(), y.data_ptr(), x.shape[0], T, Cn, w, dist2.data_ptr(), _C.stream_of(x)), h)
@@ -102,21 +93,15 @@ def dtw_knn(queries, references, k: int, window=None, exclude_self: bool = False
     w = _window(window, T)
     if exclude_self and queries is not references:
         raise ValueError("exclude_self needs the queries and the references to be the same array")
-    limit = min(MAX_K, references.shape[0] - (1 if exclude_self else 0))
-    if isinstance(k, bool) or int(k) != k or not 1 <= k <= limit:
-        raise ValueError(f"k={k} outside [1, {limit}] (at most {MAX_K}, and no more than the references "
-                         f"{'other than the series itself ' if exclude_self else ''}can supply)")
-    k = int(k)
-    q, r = _pair(queries, references)
+    k = check_k(k, references, exclude_self, "series", allow_bool=False)
+    q, r = same_pair(queries, references)
     n, m = q.shape[0], r.shape[0]
-    h, L = _C.ctx(q.device), _C.lib()
-    need = C.c_size_t(0)
-    _C.check(L.fd_dtw_knn_workspace_bytes(h, n, m, T, Cn, w, k, C.byref(need)), h)
-    work = torch.empty((need.value,), dtype=torch.uint8, device=q.device)
+    L = _C.lib()
     dist2 = torch.empty((n, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((n, k), dtype=torch.int32, device=q.device)
-    _C.check(L.fd_dtw_knn(h, q.data_ptr(), n, r.data_ptr(), m, T, Cn, w, k, 1 if exclude_self else 0, dist2.data_ptr(),
-                          idx.data_ptr(), work.data_ptr(), need.value, _C.stream_of(q)), h)
+    call_with_workspace(q, L.fd_dtw_knn_workspace_bytes, (n, m, T, Cn, w, k), lambda h, work, nbytes, stream: L.fd_dtw_knn(
+        h, q.data_ptr(), n, r.data_ptr(), m, T, Cn, w, k, 1 if exclude_self else 0, dist2.data_ptr(), idx.data_ptr(), work, nbytes,
+        stream))
     return dist2.sqrt_(), idx.long()
 
 
@@ -124,22 +109,12 @@ def dtw_ball_counts(queries, references, radii, window=None) -> torch.Tensor:
     """counts (n,) int64 on the device: for every query the number of reference series j with dtw(q_i, r_j) <= radii[j]."""
     T, Cn = _check_pair(queries, references, "queries", "references")
     w = _window(window, T)
-    if isinstance(radii, np.ndarray):
-        radii = torch.from_numpy(np.ascontiguousarray(radii))
-    rad = torch.as_tensor(radii).detach().float().reshape(-1)
-    if rad.shape[0] != references.shape[0]:
-        raise ValueError(f"{rad.shape[0]} radii for {references.shape[0]} references")
-    if not bool((torch.isfinite(rad) & (rad >= 0)).all()):
-        raise ValueError("radii must be finite and >= 0")
-    q, r = _pair(queries, references)
-    rad = rad.to(q.device).contiguous()
+    rad = check_radii(radii, references)
+    q, r = same_pair(queries, references)
     n, m = q.shape[0], r.shape[0]
-    rad2 = rad * rad
-    h, L = _C.ctx(q.device), _C.lib()
-    need = C.c_size_t(0)
-    _C.check(L.fd_dtw_ball_counts_workspace_bytes(h, n, m, T, Cn, w, C.byref(need)), h)
-    work = torch.empty((need.value,), dtype=torch.uint8, device=q.device)
+    rad2 = squared_on(rad, q.device)
+    L = _C.lib()
     counts = torch.empty((n,), dtype=torch.int32, device=q.device)
-    _C.check(L.fd_dtw_ball_counts(h, q.data_ptr(), n, r.data_ptr(), m, T, Cn, w, rad2.data_ptr(), counts.data_ptr(), work.data_ptr(),
-                                  need.value, _C.stream_of(q)), h)
+    call_with_workspace(q, L.fd_dtw_ball_counts_workspace_bytes, (n, m, T, Cn, w), lambda h, work, nbytes, stream: L.fd_dtw_ball_counts(
+        h, q.data_ptr(), n, r.data_ptr(), m, T, Cn, w, rad2.data_ptr(), counts.data_ptr(), work, nbytes, stream))
     return counts.long()

@@ -6,15 +6,11 @@ never exists; the returned distances are recomputed exactly for the returned ind
 kernel with a compare-and-count epilogue.  Both are deterministic; ties go to the lower index."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from .. import _C
-from .tensors import check_flat_array
-
-MAX_K = 16
+from ._pairs import MAX_K, call_with_workspace, check_k, check_radii, same_pair, squared_on  # noqa: F401  (MAX_K: public here)
 
 
 def _rows_features(x) -> tuple[int, int]:
@@ -31,12 +27,6 @@ def _check_pair(queries, references) -> None:
         raise ValueError(f"queries have {dq} features and references {dr}")
 
 
-def _pair(queries, references) -> tuple[torch.Tensor, torch.Tensor]:
-    q = check_flat_array(queries)
-    r = q if queries is references else check_flat_array(references).to(q.device)
-    return q, r
-
-
 def knn(queries, references, k: int, exclude_self: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
     """(dist (n, k) float32 Euclidean, idx (n, k) int64) on the device: the k nearest rows of `references` for every row of
     `queries`, ascending in (distance, index).  exclude_self: `queries` and `references` are the same set (pass the same object)
@@ -44,40 +34,26 @@ def knn(queries, references, k: int, exclude_self: bool = False) -> tuple[torch.
     _check_pair(queries, references)
     if exclude_self and queries is not references:
         raise ValueError("exclude_self needs the queries and the references to be the same array")
-    limit = min(MAX_K, references.shape[0] - (1 if exclude_self else 0))
-    if int(k) != k or not 1 <= k <= limit:
-        raise ValueError(f"k={k} outside [1, {limit}] (at most {MAX_K}, and no more than the references "
-                         f"{'other than the row itself ' if exclude_self else ''}can supply)")
-    k = int(k)
-    q, r = _pair(queries, references)
+    k = check_k(k, references, exclude_self, "row", allow_bool=True)
+    q, r = same_pair(queries, references)
     n, d = q.shape
     m = r.shape[0]
-    h, L = _C.ctx(q.device), _C.lib()
-    need = C.c_size_t(0)
-    _C.check(L.fd_knn_rows_workspace_bytes(h, n, m, d, k, C.byref(need)), h)
-    work = torch.empty((need.value,), dtype=torch.uint8, device=q.device)
+    L = _C.lib()
     dist2 = torch.empty((n, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((n, k), dtype=torch.int32, device=q.device)
-    _C.check(L.fd_knn_rows(h, q.data_ptr(), n, r.data_ptr(), m, d, k, 1 if exclude_self else 0, dist2.data_ptr(), idx.data_ptr(),
-                           work.data_ptr(), need.value, _C.stream_of(q)), h)
+    call_with_workspace(q, L.fd_knn_rows_workspace_bytes, (n, m, d, k), lambda h, work, nbytes, stream: L.fd_knn_rows(
+        h, q.data_ptr(), n, r.data_ptr(), m, d, k, 1 if exclude_self else 0, dist2.data_ptr(), idx.data_ptr(), work, nbytes, stream))
     return dist2.sqrt_(), idx.long()
 
 
 def ball_counts(queries, references, radii) -> torch.Tensor:
     """counts (n,) int64 on the device: for every query the number of reference rows j with d(q_i, r_j) <= radii[j]."""
     _check_pair(queries, references)
-    if isinstance(radii, np.ndarray):
-        radii = torch.from_numpy(np.ascontiguousarray(radii))
-    rad = torch.as_tensor(radii).detach().float().reshape(-1)
-    if rad.shape[0] != references.shape[0]:
-        raise ValueError(f"{rad.shape[0]} radii for {references.shape[0]} references")
-    if not bool((torch.isfinite(rad) & (rad >= 0)).all()):
-        raise ValueError("radii must be finite and >= 0")
-    q, r = _pair(queries, references)
-    rad = rad.to(q.device).contiguous()
+    rad = check_radii(radii, references)
+    q, r = same_pair(queries, references)
     n, d = q.shape
     counts = torch.empty((n,), dtype=torch.int32, device=q.device)
-    rad2 = rad * rad
+    rad2 = squared_on(rad, q.device)
     h = _C.ctx(q.device)
     _C.check(_C.lib().fd_ball_counts(h, q.data_ptr(), n, r.data_ptr(), r.shape[0], d, rad2.data_ptr(), counts.data_ptr(),
                                      _C.stream_of(q)), h)

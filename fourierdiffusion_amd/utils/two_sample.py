@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import _C
+from ._pairs import call_with_workspace
 from .neighbours import _rows_features
 from .tensors import check_flat_array
 
@@ -110,18 +111,16 @@ def kernel_quadforms(z, member, scales: Sequence[float] = DEFAULT_SCALES, bandwi
     if isinstance(member, np.ndarray):
         member = torch.from_numpy(np.ascontiguousarray(member).view(np.uint8))
     mt = member.detach().to(device=zt.device, dtype=torch.uint8).contiguous()
-    h, L = _C.ctx(zt.device), _C.lib()
-    need = C.c_size_t(0)
-    _C.check(L.fd_kernel_quadforms_workspace_bytes(h, N, d, P, col_splits, C.byref(need)), h)
-    work = torch.empty((need.value,), dtype=torch.uint8, device=zt.device)
+    L = _C.lib()
     quad = torch.empty((P,), dtype=torch.float64, device=zt.device)
     rowsum = torch.empty((N,), dtype=torch.float64, device=zt.device)
     col0 = torch.empty((N,), dtype=torch.float64, device=zt.device)
     base2 = torch.empty((1,), dtype=torch.float64, device=zt.device)
     cs = (C.c_double * len(scales))(*scales)
-    _C.check(L.fd_kernel_quadforms(h, zt.data_ptr(), N, d, cs, len(scales), bw2, mt.data_ptr(), P, col_splits, quad.data_ptr(),
-                                   rowsum.data_ptr(), col0.data_ptr(), base2.data_ptr(), work.data_ptr(), need.value,
-                                   _C.stream_of(zt)), h)
+    call_with_workspace(zt, L.fd_kernel_quadforms_workspace_bytes, (N, d, P, col_splits), lambda h, work, nbytes, stream:
+                        L.fd_kernel_quadforms(h, zt.data_ptr(), N, d, cs, len(scales), bw2, mt.data_ptr(), P, col_splits,
+                                              quad.data_ptr(), rowsum.data_ptr(), col0.data_ptr(), base2.data_ptr(), work, nbytes,
+                                              stream))
     return quad, rowsum, col0, base2
 
 
