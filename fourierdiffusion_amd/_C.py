@@ -196,6 +196,11 @@ _PROTOS = {
     "fd_kernel_quadforms_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_kernel_quadforms": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, _vp, C.c_int, C.c_int,
                                       _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fd_softmin_pairs_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_softmin_pairs": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_double, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "fd_sinkhorn_potentials_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_sinkhorn_potentials": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.c_int,
+                                         C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

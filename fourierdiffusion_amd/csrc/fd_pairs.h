@@ -1,16 +1,16 @@
-// fd_pairs.h -- what the all-pairs metric kernels share: fd_neighbours.hip (k_nn), fd_mmd.hip (k_mmd) and
-// fd_dtw.hip (k_dtw) include it; every piece below exists once.
+// fd_pairs.h -- what the all-pairs metric kernels share: fd_neighbours.hip (k_nn), fd_mmd.hip (k_mmd),
+// fd_dtw.hip (k_dtw) and fd_sinkhorn.hip (k_softmin) include it; every piece below exists once.
 //
 //   k-best list     KBest<KMAX> under the strict (distance, index) order, the merge of the splits' lists (k_merge_lists, its
 //                   output written by the caller's tail) and the sum of the splits' counts (sum_counts): k_nn and k_dtw.
 //   centring        column mean of a row set (double partial sums in a fixed order) and the centred, padded copy with its row
-//                   norms (centre_mean, centre_rows); the double-precision mean and deviations are an option: k_nn and k_mmd.
+//                   norms (centre_mean, centre_rows); the double-precision mean and deviations are an option: k_nn, k_mmd and k_softmin.
 //                   These and sum_counts are plain kernels, compiled once in fd_pairs.hip.
 //   Gram tiles      FD_GRAM_TILES_BEGIN / _END: a workgroup of 256 threads OWNS 128 rows (the columns of D) and STREAMS 128-row
 //                   tiles of a second set (the rows of D), 16 features at a time, double-buffered through the LDS into
 //                   v_mfma_f32_32x32x2_f32; every finished 128 x 128 accumulator tile goes to the caller's epilogue.
-//                   FD_GRAM_ROW / FD_GRAM_DRAIN are the only place that knows which accumulator register is which row: k_nn
-//                   and k_mmd.
+//                   FD_GRAM_ROW / FD_GRAM_DRAIN are the only place that knows which accumulator register is which row: k_nn,
+//                   k_mmd and k_softmin.
 //   planning        plan_splits (forced count or fill the device, clamped, whole units per split) and Carve (offsets of a
 //                   256-byte-aligned workspace).
 #pragma once

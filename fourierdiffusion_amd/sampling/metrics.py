@@ -6,7 +6,9 @@ Not in the reference: `PrecisionRecall` and `Memorisation`, nearest-neighbour me
 see what a projection-based distance cannot -- a generator that replays its training set, or one that covers a single mode; and
 `KernelTwoSample`, the kernel two-sample test (utils/two_sample.py), which puts a p-value on "can the samples be told apart from
 real data at this sample size"; and `DTWPrecisionRecall` / `DTWMemorisation`, the two nearest-neighbour metrics under banded dynamic
-time warping (utils/dtw.py), which see a training series replayed a few samples early or late as the copy it is."""
+time warping (utils/dtw.py), which see a training series replayed a few samples early or late as the copy it is; and
+`SinkhornDivergence`, the debiased entropic transport cost between the two sets in their full sample space (utils/sinkhorn.py): the
+Wasserstein-2 distance that the sliced metric stands in for."""
 from __future__ import annotations
 
 import inspect
@@ -20,6 +22,7 @@ import torch
 from ..utils.dtw import _series_shape, _window, dtw_ball_counts, dtw_knn
 from ..utils.fourier import dft, spectral_density
 from ..utils.neighbours import MAX_K, ball_counts, knn
+from ..utils.sinkhorn import DEFAULT_REG, sinkhorn_divergence
 from ..utils.tensors import check_flat_array
 from ..utils.two_sample import DEFAULT_SCALES, MAX_COLUMNS, _check_scales, mmd_permutation_test
 from ..utils.wasserstein import WassersteinDistances
@@ -442,3 +445,61 @@ class KernelTwoSample(Metric):
     @property
     def name(self) -> str:
         return "kernel_two_sample"
+
+
+class SinkhornDivergence(Metric):
+    """Debiased Sinkhorn divergence (Genevay et al. 2018, Feydy et al. 2019) of the generated samples against real ones, cost
+    ||x - y||^2 on the flat rows, eps = `reg` times the mean squared distance over the pooled pairs:
+      sinkhorn_divergence, sinkhorn_w2, sinkhorn_marginal_error    against the original samples
+      ..._holdout                                                  (with `holdout_samples`) against real samples the model was not
+                                                                   trained on
+      ..._self                                                     (baseline) the two folds of the original samples
+    sinkhorn_w2 = sqrt(max(divergence, 0)) estimates the Wasserstein-2 distance of the two sets in sample space; the marginal
+    error says how far the iteration was from convergence (0: converged).  `max_original` evaluates against a seeded subsample of
+    the real set."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 reg: float = DEFAULT_REG, max_original: Optional[int] = None, random_seed: int = 0) -> None:
+        if isinstance(reg, bool) or not (np.isfinite(float(reg)) and float(reg) > 0):
+            raise ValueError(f"reg={reg} must be finite and > 0")
+        if max_original is not None and (int(max_original) != max_original or max_original < 2):
+            raise ValueError(f"max_original={max_original} must be an integer >= 2")
+        if len(original_samples) < 1:
+            raise ValueError("SinkhornDivergence needs at least one original sample")
+        if holdout_samples is not None and len(holdout_samples) < 1:
+            raise ValueError("SinkhornDivergence needs at least one held-out sample")
+        super().__init__(original_samples=original_samples)
+        self.reg, self.max_original, self.random_seed = float(reg), max_original, random_seed
+        n = self.original_samples.shape[0]
+        if max_original is not None and n > max_original:
+            keep = torch.from_numpy(subsample_indices(n, int(max_original), random_seed)).to(self.original_samples.device)
+            self.original_samples = self.original_samples[keep].contiguous()
+        self.holdout_samples = None
+        if holdout_samples is not None:
+            self.holdout_samples = check_flat_array(holdout_samples)
+            if self.holdout_samples.shape[1] != self.original_samples.shape[1]:
+                raise ValueError("original and held-out samples must have the same number of features")
+
+    def _divergence(self, samples: torch.Tensor, real: torch.Tensor, suffix: str) -> dict[str, float]:
+        res = sinkhorn_divergence(samples, real, reg=self.reg)
+        return {f"sinkhorn_divergence{suffix}": float(res.divergence), f"sinkhorn_w2{suffix}": float(res.w2),
+                f"sinkhorn_marginal_error{suffix}": float(res.marginal_error)}
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = check_flat_array(other_samples)
+        out = self._divergence(samples, self.original_samples, "")
+        if self.holdout_samples is not None:
+            out.update(self._divergence(samples, self.holdout_samples, "_holdout"))
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        n_samples = self.original_samples.shape[0]                    # two folds of the original samples, as the Wasserstein metrics
+        if n_samples // 2 < 1:
+            return {}
+        return self._divergence(self.original_samples[: n_samples // 2].contiguous(),
+                                self.original_samples[n_samples // 2:].contiguous(), "_self")
+
+    @property
+    def name(self) -> str:
+        return "sinkhorn_divergence"

@@ -818,6 +818,48 @@ int fd_kernel_quadforms(fd_ctx* ctx, const float* z, int N, int d, const double*
                         double* out_col0 /* (N) or NULL */, double* out_base2 /* (1) device */, void* work, size_t work_bytes,
                         void* stream);
 
+/* Entropic optimal transport between two sample sets, cost ||x - y||^2 (NOT in the reference; Genevay et al. 2018, Feydy et al.
+ * 2019; the debiased Sinkhorn divergence is host arithmetic on the potentials, utils/sinkhorn.py).  x (n, d), y (m, d) dense
+ * row-major fp32 device rows with finite entries.
+ *
+ * fd_softmin_pairs: one pass, out[i] = -eps log sum_j exp((h[j] - ||x_i - y_j||^2) / eps); h (m) and out (n) device doubles, h
+ * finite.  One fused kernel (csrc/fd_sinkhorn.hip): both sets centred by the mean of the pooled rows, squared distances as in
+ * fd_knn_rows (fp32-MFMA expansion clamped at 0), the exponent (h_j - d2) s with s = f32(log2 e / eps) by one fma on d2, a running
+ * (max, sum) per owned row with v_exp_f32 on the difference to the maximum; rows of the padding are masked by INDEX.  The n x m
+ * matrix never exists.  `same`: x and y are one array (x == y and n == m is detected by the call itself).
+ * Error.  With u = 2^-24, delta_ij the expansion error of fd_knn_rows about the pooled mean and c = 64 gt + 1 <= 1025 the longest
+ * fp32 addition chain (gt = min(16, max(1, tiles / 16)), tiles = ceil(m / 128)):
+ *   |out~_i - out_i| <= max_j (delta_ij + u |h_j|) + 6 u max_j |h_j - d2_ij| + eps (67 gt + 9) u
+ * (the soft-min is 1-Lipschitz in its exponents under the sup norm: the roundings of s, s h_j, the fma and the subtraction of the
+ * maximum; then 2 u per v_exp_f32, c u for the chain and 3 u per rescaling of the running sum.  DESIGN.md 3.28 derives the terms).
+ * splits: 0 = automatic, else the number of workgroup columns the streamed row groups are divided over.  The groups' fp32 (max,
+ * sum) pairs go to work and are merged in double in group order by a second kernel; no atomics: results are bit-identical between
+ * runs and for every splits.
+ *
+ * fd_sinkhorn_potentials: the whole iteration, enqueued on the stream with no host synchronisation: centring once, then n_steps
+ * iterations, iteration k at eps[k] eps_base (absolute != 0: at eps[k]); eps: n_steps HOST doubles.
+ *   eps_base    the mean squared distance over the pooled pairs i != j in its closed form 2 sum ||z_i - mean||^2 / (N - 1), in
+ *               double (as base2 of fd_kernel_quadforms); 1 when every row is the same
+ *   a, b        device doubles (n) / (m), positive and summing to 1, or NULL = uniform; a soft-min over the rows of y runs on
+ *               h_j = g_j + eps log b_j
+ *   symmetric 0 f <- softmin_Y(g), g <- softmin_X(f) per iteration, from g = 0; ends on a g update
+ *   symmetric 1 (x == y, n == m) p <- (p + softmin_X(p)) / 2 from p = 0 with the weights a; out_f = out_g = p
+ *   out_f (n), out_g (m), out_eps_base (1): device doubles
+ * Every soft-min obeys the bound above, and both updates are non-expansive in the sup norm: after L soft-min passes the error of a
+ * potential is at most the sum of the L per-pass bounds.
+ * work: caller-owned device bytes, at least the matching _workspace_bytes of the same shape.
+ * FD_ERR_ARG: null pointer (a, b excepted), n, m or d < 1, n * d, m * d or n + m >= 2^31, an eps that is not finite and > 0,
+ * splits < 0, n_steps outside [1, 256], same / symmetric with different sets, a workspace that is too small. */
+int fd_softmin_pairs_workspace_bytes(fd_ctx* ctx, int n, int m, int d, int same, int splits, size_t* bytes);
+int fd_softmin_pairs(fd_ctx* ctx, const float* x, int n, const float* y, int m, int d, const double* h /* (m) device */, double eps,
+                     int splits /* 0: automatic */, double* out /* (n) device */, void* work, size_t work_bytes, void* stream);
+int fd_sinkhorn_potentials_workspace_bytes(fd_ctx* ctx, int n, int m, int d, int symmetric, size_t* bytes);
+int fd_sinkhorn_potentials(fd_ctx* ctx, const float* x, int n, const float* y, int m, int d, int symmetric,
+                           const double* a /* (n) device or NULL */, const double* b /* (m) device or NULL */,
+                           const double* eps /* (n_steps) host */, int n_steps, int absolute, double* out_f /* (n) */,
+                           double* out_g /* (m) */, double* out_eps_base /* (1) device */, void* work, size_t work_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
