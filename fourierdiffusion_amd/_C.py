@@ -201,6 +201,8 @@ _PROTOS = {
     "fd_sinkhorn_potentials_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_sinkhorn_potentials": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.c_int,
                                          C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fd_series_dependence_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_series_dependence": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -8,7 +8,9 @@ see what a projection-based distance cannot -- a generator that replays its trai
 real data at this sample size"; and `DTWPrecisionRecall` / `DTWMemorisation`, the two nearest-neighbour metrics under banded dynamic
 time warping (utils/dtw.py), which see a training series replayed a few samples early or late as the copy it is; and
 `SinkhornDivergence`, the debiased entropic transport cost between the two sets in their full sample space (utils/sinkhorn.py): the
-Wasserstein-2 distance that the sliced metric stands in for."""
+Wasserstein-2 distance that the sliced metric stands in for; and `TemporalDependence`, the first metric that looks INSIDE a series
+(utils/dependence.py): differences of the mean autocorrelation, of the mean cross-correlation between channels and of the skewness
+and kurtosis between the samples and the real set."""
 from __future__ import annotations
 
 import inspect
@@ -19,6 +21,8 @@ from typing import Any, Optional
 import numpy as np
 import torch
 
+from ..utils.dependence import _series_shape as _dependence_shape
+from ..utils.dependence import resolve_lags, series_dependence
 from ..utils.dtw import _series_shape, _window, dtw_ball_counts, dtw_knn
 from ..utils.fourier import dft, spectral_density
 from ..utils.neighbours import MAX_K, ball_counts, knn
@@ -503,3 +507,98 @@ class SinkhornDivergence(Metric):
     @property
     def name(self) -> str:
         return "sinkhorn_divergence"
+
+
+class TemporalDependence(Metric):
+    """Does the generator reproduce the dependence structure inside a series?  Per series the normalised autocorrelation (lags
+    1..`lags`), the normalised cross-correlation of every ordered channel pair (lags 0..`cross_lags`) and the skewness and excess
+    kurtosis of every channel (utils/dependence.py); then, between the samples and the real set,
+      acf_distance, acf_distance_max            mean / max over (lag, channel) of |mean ACF of the samples - mean ACF of the real set|
+                                                (the autocorrelation difference of TSGBench)
+      ccf_distance, ccf_distance_max            the same over (lag, c != d): the correlational score; omitted for one channel
+      skewness_distance, kurtosis_distance      mean over channels of the absolute difference of the set means
+      acf_marginal_wasserstein_mean, _max       Wasserstein-2 per (lag, channel) between the DISTRIBUTIONS of the per-series ACF
+                                                values (MarginalWasserstein's arithmetic on the (n, lags C) feature rows)
+      ..._holdout                               (with `holdout_samples`) against real series the model was not trained on
+      ..._self                                  (baseline) the two folds of the original samples
+    `lags=None` is max(1, T // 4), `cross_lags=None` is min(lags, 8).  `max_original` evaluates against a seeded subsample of the real
+    set.  The real set's features are computed once, here.  Needs (n, T, C) original samples; a spectrum's "time" axis has no
+    autocorrelation worth the name: bound in the time view only."""
+    views = ("time",)
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 lags: Optional[int] = None, cross_lags: Optional[int] = None, max_original: Optional[int] = None,
+                 random_seed: int = 0) -> None:
+        if len(tuple(original_samples.shape)) != 3:
+            raise ValueError(f"TemporalDependence needs the original samples as (n, T, C) series, got shape "
+                             f"{tuple(original_samples.shape)}: a flat (n, d) array has lost its time axis")
+        _, T, C = _dependence_shape(original_samples, "original samples")
+        self.series_shape = (T, C)
+        self.lags, self.cross_lags = resolve_lags(T, C, lags, cross_lags)
+        if max_original is not None and (isinstance(max_original, bool) or int(max_original) != max_original or max_original < 2):
+            raise ValueError(f"max_original={max_original} must be an integer >= 2")
+        if len(original_samples) < 1:
+            raise ValueError("TemporalDependence needs at least one original sample")
+        if holdout_samples is not None:
+            if len(holdout_samples) < 1:
+                raise ValueError("TemporalDependence needs at least one held-out sample")
+            if int(np.prod(tuple(holdout_samples.shape)[1:])) != T * C:
+                raise ValueError("original and held-out samples must have the same number of features")
+        super().__init__(original_samples=original_samples)
+        self.max_original, self.random_seed = max_original, random_seed
+        n = self.original_samples.shape[0]
+        if max_original is not None and n > max_original:
+            keep = torch.from_numpy(subsample_indices(n, int(max_original), random_seed)).to(self.original_samples.device)
+            self.original_samples = self.original_samples[keep].contiguous()
+            n = int(max_original)
+        self._real = self._features(self.original_samples)
+        self._held = self._features(check_flat_array(holdout_samples)) if holdout_samples is not None else None
+        self._folds = None
+        if n // 2 >= 1:
+            self._folds = (self._features(self.original_samples[: n // 2].contiguous()),
+                           self._features(self.original_samples[n // 2:].contiguous()))
+        self._baseline: Optional[dict[str, float]] = None
+
+    def _features(self, rows: torch.Tensor):
+        T, C = self.series_shape
+        if rows.dim() != 2 or rows.shape[1] != T * C:
+            raise ValueError(f"samples of {tuple(rows.shape[1:])} features, the original samples are series of shape {(T, C)}")
+        return series_dependence(rows.view(rows.shape[0], T, C), lags=self.lags, cross_lags=self.cross_lags, per_series=("acf",))
+
+    def _compare(self, samples, real, suffix: str) -> dict[str, float]:
+        C = self.series_shape[1]
+        out: dict[str, float] = {}
+        if self.lags >= 1:
+            d = (samples.set_mean.acf - real.set_mean.acf).abs().cpu().numpy()
+            out[f"acf_distance{suffix}"], out[f"acf_distance_max{suffix}"] = float(d.mean()), float(d.max())
+        if C > 1 and real.set_mean.ccf is not None:
+            d = (samples.set_mean.ccf - real.set_mean.ccf).abs().cpu().numpy()
+            d = d[:, ~np.eye(C, dtype=bool)]
+            out[f"ccf_distance{suffix}"], out[f"ccf_distance_max{suffix}"] = float(d.mean()), float(d.max())
+        d = (samples.set_mean.moments - real.set_mean.moments).abs().cpu().numpy()
+        out[f"skewness_distance{suffix}"], out[f"kurtosis_distance{suffix}"] = float(d[:, 2].mean()), float(d[:, 3].mean())
+        if self.lags >= 1:
+            w = WassersteinDistances(original_data=real.acf.reshape(real.acf.shape[0], -1),
+                                     other_data=samples.acf.reshape(samples.acf.shape[0], -1), seed=self.random_seed).marginal_distances()
+            out[f"acf_marginal_wasserstein_mean{suffix}"] = float(np.mean(w))
+            out[f"acf_marginal_wasserstein_max{suffix}"] = float(np.max(w))
+        return out
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = self._features(check_flat_array(other_samples))
+        out = self._compare(samples, self._real, "")
+        if self._held is not None:
+            out.update(self._compare(samples, self._held, "_holdout"))
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        if self._folds is None:
+            return {}
+        if self._baseline is None:                                    # two folds of the original samples, as the Wasserstein metrics
+            self._baseline = self._compare(self._folds[0], self._folds[1], "_self")
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "temporal_dependence"

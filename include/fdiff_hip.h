@@ -860,6 +860,53 @@ int fd_sinkhorn_potentials(fd_ctx* ctx, const float* x, int n, const float* y, i
                            double* out_g /* (m) */, double* out_eps_base /* (1) device */, void* work, size_t work_bytes,
                            void* stream);
 
+/* Dependence structure inside a series (NOT in the reference; the autocorrelation difference of TSGBench, the correlational score
+ * of Ni et al. and Diffusion-TS; the metric is host arithmetic on the set means, utils/dependence.py).  x (n, T, C) dense
+ * row-major fp32 device series with finite entries; L = acf_lags in [0, T - 1], Lx = ccf_lags in [-1, T - 1] (-1: no ccf).
+ * For one series and channel c (the biased estimators of numpy / statsmodels: the lag matrices are positive semidefinite):
+ *   mu_c = (1/T) sum_t x[t,c],  e[t,c] = x[t,c] - mu_c,  m_k = (1/T) sum_t e^k
+ *   out_moments (n, C, 4) fp32 or NULL   (mu, sqrt(m_2), m_3 / m_2^1.5, m_4 / m_2^2 - 3)
+ *   out_acf     (n, L, C) fp32 or NULL   acf[l-1, c] = sum_{t=0}^{T-1-l} e[t,c] e[t+l,c] / (T m_2(c)),  l = 1..L
+ *   out_ccf     (n, Lx+1, C, C) fp32 or NULL   ccf[l, c, d] = sum_{t=0}^{T-1-l} e[t,c] e[t+l,d] / (T sqrt(m_2(c) m_2(d))),  l = 0..Lx,
+ *               every ordered pair: a negative lag of (c, d) is the positive lag of (d, c)
+ *   out_set_mean (F) DOUBLES or NULL     the mean over the n series of every fp32 feature as returned, in the order
+ *               moments | acf | ccf, F = 4 C + L C + (Lx + 1) C^2; computed whether or not the per-series arrays are asked for
+ * A channel whose T entries are bit-equal has e == 0 exactly (below): its skewness, kurtosis, acf and every ccf entry it takes
+ * part in are 0, not NaN; its mean is the value and its deviation 0; no other entry is affected.
+ * Arithmetic (csrc/fd_dependence.hip).  One fused kernel: a series is read once into the LDS, transposed.  mu is a DOUBLE sum (P
+ * lanes per channel, strided, then a butterfly; P the largest power of two <= 64 / C) divided by T; T <= 1024 equal floats v make
+ * every partial sum k v exact (34 bits), so mu = v and e = 0.  e = f32(x - mu) with the difference taken in double before any
+ * product; every sum of products of e (S_k = sum e^k, and each lag's sum, over t ascending) is accumulated in double by fma;
+ * value = f32(sum / sqrt(S_2(c) S_2(d))).  fp32 enters twice: once in e, once in the returned value.
+ * Pure function per series: a series' features depend on that series and (T, C) alone -- not on n, its position, the grid,
+ * L, Lx or which outputs are asked for.  ccf[l, c, c] is acf[l - 1, c] bit for bit (one product serves both), and ccf[0, c, c] is
+ * exactly 1 for a non-constant channel (the two double sums of e^2 differ by at most T 2^-52 relative, far inside the fp32
+ * rounding of 1).
+ * Set means: series are cut into chunks of 32 (fd_series_dependence's own constant); a chunk's features are added in double in
+ * series order by the one thread that owns the feature, the chunk sums go to work, a second kernel adds the chunks of every 64 in
+ * chunk order and a third those sums in order: a grouping that depends on n alone.
+ * No atomics: results are bit-identical between runs and for every grid (FDIFF_DEP_SPLITS forces the workgroup count).
+ * Error against the float64 value, u = 2^-24, v = 2^-53, h_t = (u + 2 v) |e_t| + rho, rho = (T + 2) v max_t |x_t| (the mean's
+ * share: centring survives an offset of 1000 at a cost of about 1e-11 of the deviation):
+ *   acf, ccf   |r~ - r| <= (dN + |r| dD) / (D - dD) + u |r|,  D = sqrt(S_2(c) S_2(d)),  dN = sum (|e| h' + h |e'| + h h') + T v sum (|e| + h)(|e'| + h'),
+ *              dD from dS_2 = sum (2 |e| h + h^2) + T v sum (|e| + h)^2; by Cauchy-Schwarz (sum |e e'| <= D) this is at most
+ *              c u + O(rho / sd) with c = 5 + O(T 2^-29) for every T: the chains are double, so c does not grow with T
+ *   skewness   the same quotient rule on sqrt(T) S_3 / S_2^1.5: about 3 u sum |e|^3 / (T m_2^1.5) + 4 u |skewness|
+ *   kurtosis   on T S_4 / S_2^2 - 3: about 4 u sum e^4 / (T m_2^2) + 5 u (kurtosis + 3)
+ *   mean, deviation  u |mu| + rho;  u sd + dS_2 / (2 T sd)
+ * (tests/dependence_ref.py evaluates these per entry; DESIGN.md 3.29 derives them).
+ * Limits: T <= 1024, C <= 64, and the series plus one double per feature of a series (lags padded to the kernel's lag block) within
+ * 160 KiB of LDS -- every datamodule shape and T <= 1024 with C <= 16 at the default lags.  work: caller-owned device bytes, at
+ * least fd_series_dependence_workspace_bytes of the same shape; needed (non-null) only with out_set_mean.
+ * FD_ERR_ARG (nothing is launched): null x, n, T or C < 1, T > 1024 or C > 64, acf_lags outside [0, T - 1], ccf_lags outside
+ * [-1, T - 1], every output null, out_acf with acf_lags = 0, out_ccf with ccf_lags = -1, more LDS than a CU has, n F or n T C >= 2^31,
+ * out_set_mean with a workspace that is null or too small. */
+int fd_series_dependence_workspace_bytes(fd_ctx* ctx, int n, int T, int C, int acf_lags, int ccf_lags, size_t* bytes);
+int fd_series_dependence(fd_ctx* ctx, const float* x, int n, int T, int C, int acf_lags, int ccf_lags,
+                         float* out_moments /* (n, C, 4) or NULL */, float* out_acf /* (n, L, C) or NULL */,
+                         float* out_ccf /* (n, Lx + 1, C, C) or NULL */, double* out_set_mean /* (F) or NULL */, void* work,
+                         size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
