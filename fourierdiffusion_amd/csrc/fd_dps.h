@@ -10,10 +10,10 @@ struct fd_dps_res {
     const float* x;          // (B,T,C) state x_i
     const float* score;      // (B,T,C) s_theta(x_i, t_i)
     const float* x0;         // (B/obs_rep,T,C) A^-1(where(m, y, 0))
-    const uint8_t* mask;     // (B/obs_rep,T,C) or (T,C), 1 = observed, time domain
+    const uint8_t* mask;     // (B/obs_rep,M,C) or (M,C), 1 = observed, over the operator's M rows (time steps / windows)
     const float* stdv;       // (T,C) feature std or nullptr (= 1)
     const float* G;          // (T)
-    const float* basis;      // F (Tp x Tp) then F^T (Tp x Tp); FOURIER only
+    const float* basis;      // the operator's pair: F then F^T (Tp x Tp each), or A_w (Jp x Tp) then B_w (Tp x Jp); FOURIER only
     float* u;                // (B,T,C)
     float* dout;             // (B,T,C) s^2 G^2 u, or nullptr (no Jacobian)
     double* part;            // (B, ncb) sum r^2 of each channel block

@@ -13,10 +13,11 @@
 //
 // The guidance is multiplied by sigma where the projection divides by it, so near-empty spectral bins receive almost nothing.
 //
-// k_dps_residual<FOURIER>: one workgroup per (row, block of 16 channels), on fd_impute.hip's basis and LDS layout.  Phase 1:
-// sigma (x0_obs - x0_hat) / rho into the k-quad LDS image U; phase 2: V = F^T U (v_mfma_f32_16x16x4_f32), masked into W = r, and
-// the block's sum r^2 in double; phase 3: Y = F W, u = sigma Y / rho, dout = s^2 G^2 u.  The block's sum goes to part[b][block]
-// (no atomics).  k_dps_step: elementwise over k_sde_step's Philox groups; a row's ||r||^2 is the sum of its blocks in order, so
+// k_dps_residual<FOURIER, PAIR, Op>: one workgroup per (row, block of 16 channels), on fd_impute.hip's basis and on the LDS images,
+// product, block sum and launch of fd_project.h, which k_impute shares.  Phase 1: sigma (x0_obs - x0_hat) / rho into the k-quad LDS
+// image U; phase 2: V = F^T U (v_mfma_f32_16x16x4_f32), masked into W = r, and the block's sum r^2 in double; phase 3: Y = F W,
+// u = sigma Y / rho, dout = s^2 G^2 u.  The block's sum goes to part[b][block] (no atomics).  Op = WindowOp: the residual of window
+// means (fd_aggregate.hip), r over windows, W = r / l, the bases A_w / B_w.  k_dps_step: elementwise over k_sde_step's Philox groups; a row's ||r||^2 is the sum of its blocks in order, so
 // runs are bit-identical.  Every stage buffer lives in ctx->ll_buf, outside the arena that holds the training forward's saved
 // activations.
 //
@@ -36,15 +37,14 @@
 #include "fd_engine.h"
 #include "fd_loop.h"
 #include "fd_philox.h"
+#include "fd_project.h"
 #include "fd_sde.h"
 
 namespace {
 
-constexpr int kThreads = 512;    // residual: 8 waves, the row tiles of a product dealt round-robin
-constexpr int kCB = 16;          // channels per workgroup = N of the MFMA tile
-constexpr int kStepBlock = 256;
+using namespace fdproj;
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+constexpr int kStepBlock = 256;
 
 typedef fd_dps_res ResArgs;      // fd_dps.h
 // PAIR: x and score are (2B,T,C), dout too (w v in the conditional half, (1 - w) v in the null half); u and part stay B rows
@@ -56,9 +56,6 @@ template <bool PAIR>
 struct ResArgsOf { typedef ResArgs type; };
 template <>
 struct ResArgsOf<true> { typedef ResArgsPair type; };
-
-__device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k == T)) ? 1.0f : 2.0f; }
-__device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB + c) * 4 + (k & 3); }
 
 // the score Tweedie's estimate reads at element e, and the VJP input s^2 G^2 u of element e
 template <bool PAIR, class Args>
@@ -76,18 +73,20 @@ __device__ __forceinline__ void res_dout(const Args& a, size_t e, float v) {
     }
 }
 
-template <bool FOURIER, bool PAIR = false>
-__global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PAIR>::type a) {
+// Op (fd_project.h): the coordinate mask, or window means (fd_aggregate.hip), which go with no PAIR
+template <bool FOURIER, bool PAIR, class Op>
+__global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PAIR>::type a, Op op) {
+    static_assert(!(Op::kWindow && PAIR), "window means go with no guide");
     extern __shared__ float lds[];
-    __shared__ double red[kThreads];
     const int tid = threadIdx.x;
     const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
-    const int T = a.T, C = a.C, Tp = a.Tp;
+    const int T = a.T, C = a.C, Tp = a.Tp, M = op.rows(T), Mp = op.rows_padded(Tp);
     const size_t TC = (size_t)T * C, base = (size_t)b * TC, obase = (size_t)(b / a.obs_rep) * TC;
-    const uint8_t* mrow = a.mask + (a.mask_per_series ? obase : 0);
+    const uint8_t* mrow = a.mask + (a.mask_per_series ? (size_t)(b / a.obs_rep) * M * C : 0);
     double rr = 0.0;
 
-    if (!FOURIER) {
+    if constexpr (!FOURIER && !Op::kWindow) {
+        // ---- the mask in the time domain selects elementwise: no LDS image
         for (int i = tid; i < T * kCB; i += kThreads) {
             const int t = i / kCB, c = c0 + i % kCB;
             if (c >= C) continue;
@@ -102,10 +101,12 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
             if (a.dout) res_dout<PAIR>(a, e, sg2 * uv);
         }
     } else {
-        float* U = lds;                            // sigma (x0_obs - x0_hat) / rho, frequency rows
-        float* W = lds + (size_t)Tp * kCB;         // r, time rows
-        for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
-        __syncthreads();
+        float* U = lds;                            // FOURIER: sigma (x0_obs - x0_hat) / rho, frequency rows (k-quad); else time rows [t][channel]
+        float* W = lds + (size_t)Tp * kCB;         // FOURIER: the adjoint's input (r, or r / l), the operator's rows (k-quad)
+        if (FOURIER) {
+            for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
+            __syncthreads();
+        }
         // ---- phase 1
         for (int i = tid; i < T * kCB; i += kThreads) {
             const int k = i / kCB, cl = i % kCB, c = c0 + cl;
@@ -114,78 +115,84 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
             const float Gk = a.G[k];
             const float sd = a.stdv ? a.stdv[kc] : 1.0f;
             const float x0h = (a.x[e] + a.s2 * (Gk * Gk) * res_score<PAIR>(a, e)) / a.alpha;
-            U[quad_idx(k, cl)] = sd * (a.x0[obase + kc] - x0h) * inv_r(k, T);
+            const float dv = sd * (a.x0[obase + kc] - x0h);
+            if (FOURIER) U[quad_idx(k, cl)] = dv * inv_r(k, T);
+            else U[i] = dv;
         }
         __syncthreads();
-        const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
-        const int li = lane & 15, kq = lane >> 4;
-        const int ntile = Tp / 16;
-        const float* Fm = a.basis;
-        const float* Ft = a.basis + (size_t)Tp * Tp;
-        // ---- phase 2: V = F^T U (row i of the tile = time t0 + i); W = r = m ? V : 0
-        for (int tile = wave; tile < ntile; tile += nw) {
-            const int t0 = tile * 16;
-            const float* arow = Ft + (size_t)(t0 + li) * Tp + 4 * kq;
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-            for (int k0 = 0; k0 < Tp; k0 += 16) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(U + ((k0 / 4 + kq) * kCB + li) * 4);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+
+        if constexpr (!FOURIER) {
+            // ---- window means in the time domain: one thread per (window, channel), r = the masked mean in ascending t;
+            // u = sigma r / l over the window
+            for (int i = tid; i < M * kCB; i += kThreads) {
+                const int j = i / kCB, cl = i % kCB, c = c0 + cl;
+                if (c >= C) continue;
+                const int t0 = j * op.window, l = win_len(j, op.window, T);
+                float r = 0.f;
+                if (mrow[(size_t)j * C + c]) {
+                    float sum = 0.f;
+                    for (int k = 0; k < l; ++k) sum += U[(t0 + k) * kCB + cl];
+                    r = sum / (float)l;
+                }
+                rr += (double)r * (double)r;
+                const float rl = r / (float)l;
+                for (int k = 0; k < l; ++k) {
+                    const int t = t0 + k;
+                    const size_t tc = (size_t)t * C + c, e = base + tc;
+                    const float sd = a.stdv ? a.stdv[tc] : 1.0f;
+                    const float uv = sd * rl;
+                    a.u[e] = uv;
+                    if (a.dout) {
+                        const float Gt = a.G[t];
+                        res_dout<PAIR>(a, e, a.s2 * (Gt * Gt) * uv);
+                    }
+                }
             }
+        } else {
+            const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
+            const int li = lane & 15, kq = lane >> 4;
             const int c = c0 + li;
-            f32x4 w;
+            const float* Ao = op.to_obs(a.basis, Tp);
+            const float* Bo = op.from_obs(a.basis, Tp);
+            // ---- phase 2: r = m . (Ao U) (row i of the tile = observation row j0 + i: a time step or a window), its squares in
+            // double; W = the adjoint's input
+            for (int tile = wave; tile < Mp / 16; tile += nw) {
+                const int j0 = tile * 16;
+                const f32x4 acc = tile_product(Ao, j0, Tp, U, li, kq);
+                f32x4 w;
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int t = t0 + 4 * kq + v;
-                const bool keep = t < T && c < C && mrow[(size_t)t * C + c];
-                w[v] = keep ? acc0[v] + acc1[v] : 0.f;
-                rr += (double)w[v] * (double)w[v];
+                for (int v = 0; v < 4; ++v) {
+                    const int j = j0 + 4 * kq + v;
+                    const bool keep = j < M && c < C && mrow[(size_t)j * C + c];
+                    const float rv = keep ? acc[v] : 0.f;
+                    rr += (double)rv * (double)rv;
+                    w[v] = keep ? op.adjoint(rv, j, T) : 0.f;
+                }
+                *reinterpret_cast<f32x4*>(W + ((j0 / 4 + kq) * kCB + li) * 4) = w;
             }
-            *reinterpret_cast<f32x4*>(W + ((t0 / 4 + kq) * kCB + li) * 4) = w;
-        }
-        __syncthreads();
-        // ---- phase 3: Y = F W (row i of the tile = packed row r0 + i); u = sigma Y / rho, dout = s^2 G^2 u
-        for (int tile = wave; tile < ntile; tile += nw) {
-            const int r0 = tile * 16;
-            const float* arow = Fm + (size_t)(r0 + li) * Tp + 4 * kq;
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-            for (int k0 = 0; k0 < Tp; k0 += 16) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(W + ((k0 / 4 + kq) * kCB + li) * 4);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
-            }
-            const int c = c0 + li;
-            if (c >= C) continue;
+            __syncthreads();
+            // ---- phase 3: Y = Bo W (row i of the tile = packed row r0 + i); u = sigma Y / rho, dout = s^2 G^2 u
+            for (int tile = wave; tile < Tp / 16; tile += nw) {
+                const int r0 = tile * 16;
+                const f32x4 acc = tile_product(Bo, r0, Mp, W, li, kq);
+                if (c >= C) continue;
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int k = r0 + 4 * kq + v;
-                if (k >= T) continue;
-                const size_t kc = (size_t)k * C + c, e = base + kc;
-                const float sd = a.stdv ? a.stdv[kc] : 1.0f;
-                const float uv = sd * inv_r(k, T) * (acc0[v] + acc1[v]);
-                a.u[e] = uv;
-                if (a.dout) {
-                    const float Gk = a.G[k];
-                    res_dout<PAIR>(a, e, a.s2 * (Gk * Gk) * uv);
+                for (int v = 0; v < 4; ++v) {
+                    const int k = r0 + 4 * kq + v;
+                    if (k >= T) continue;
+                    const size_t kc = (size_t)k * C + c, e = base + kc;
+                    const float sd = a.stdv ? a.stdv[kc] : 1.0f;
+                    const float uv = sd * inv_r(k, T) * acc[v];
+                    a.u[e] = uv;
+                    if (a.dout) {
+                        const float Gk = a.G[k];
+                        res_dout<PAIR>(a, e, a.s2 * (Gk * Gk) * uv);
+                    }
                 }
             }
         }
     }
-    // the block's sum r^2: fixed-order LDS tree
-    red[tid] = rr;
-    __syncthreads();
-#pragma unroll
-    for (int w = kThreads / 2; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) a.part[blockIdx.x] = red[0];
+    block_sum(rr, a.part + blockIdx.x);
 }
 
 struct StepArgs {
@@ -293,16 +300,10 @@ int fd_dps_prepare(fd_score* m, fd_dps_res& r, const float* G, const float* x, c
 
 namespace {
 
-template <bool FOURIER, bool PAIR>
-int launch_residual(fd_ctx* ctx, const typename ResArgsOf<PAIR>::type& r, int B, hipStream_t s) {
-    static unsigned long long attr_set = 0;
-    const size_t lds = FOURIER ? (size_t)2 * r.Tp * kCB * sizeof(float) : 0;
-    if (FOURIER && fd_first_on_device(attr_set, ctx->device))
-        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_dps_residual<FOURIER, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        128 * 1024));
-    hipLaunchKernelGGL((k_dps_residual<FOURIER, PAIR>), dim3((unsigned)(B * r.ncb)), dim3(kThreads), lds, s, r);
-    FD_LAUNCH_CHECK(ctx);
-    return FD_OK;
+template <bool FOURIER, bool PAIR, class Op = MaskOp>
+int launch_residual(fd_ctx* ctx, const typename ResArgsOf<PAIR>::type& r, int B, hipStream_t s, Op op = Op()) {
+    return launch_kernel<k_dps_residual<FOURIER, PAIR, Op>, 128 * 1024>(ctx, (unsigned)(B * r.ncb), image_bytes(op, r.T, r.Tp, FOURIER),
+                                                                         s, r, op);
 }
 
 // the step (or, GRAD, the gradient) over the B rows of a.n; g: a paired guide, or null
@@ -339,14 +340,10 @@ int fd_dps_eval(fd_score* m, fd_dps_res& r, const fd_dps_bufs& bf, const float* 
     }
     r.x = x;
     r.score = bf.score;
-    if (ag) {        // window means (fd_aggregate.hip): r.mask is (B/obs_rep,J,C) or (J,C)
-        fd_agg_res_args ra{};
-        ra.x = r.x; ra.score = r.score; ra.x0 = r.x0; ra.mask = r.mask; ra.stdv = r.stdv; ra.G = r.G;
-        ra.u = r.u; ra.dout = r.dout; ra.part = r.part;
-        ra.T = r.T; ra.C = r.C; ra.Tp = r.Tp; ra.ncb = r.ncb; ra.mask_per_series = r.mask_per_series; ra.obs_rep = r.obs_rep;
-        ra.alpha = r.alpha; ra.s2 = r.s2;
-        ra.p = *ag;
-        if (int rc = fd_agg_launch_residual(ctx, ra, B, fourier, s)) return rc;
+    if (ag) {        // window means (fd_aggregate.h): r.mask is (B/obs_rep,J,C) or (J,C)
+        r.basis = ag->basis;
+        if (int rc = fourier ? launch_residual<true, false>(ctx, r, B, s, ag->op) : launch_residual<false, false>(ctx, r, B, s, ag->op))
+            return rc;
     } else if (g) {
         ResArgsPair rp{};
         static_cast<ResArgs&>(rp) = r;

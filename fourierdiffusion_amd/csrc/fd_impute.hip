@@ -19,6 +19,11 @@
 // Phase 2: V = F^T U (v_mfma_f32_16x16x4_f32, 16 time rows x 16 channels per tile), masked into the LDS image W.  Phase 3:
 // Y = F W, out += Y / sigma.  Both LDS images are Tp x 16 floats in k-quad order, [(k / 4)][channel][k % 4], so that the
 // B operand of four consecutive MFMAs is one conflict-free ds_read_b128 per lane; LDS = 128 Tp bytes (128 KiB at T = 1024).
+// The images, the product, the group walk of phase 1 and the launch are fd_project.h's, shared with k_dps_residual (fd_dps.hip).
+//
+// The mask enters in one place, between the two products, so k_impute is a template on the observation operator (fd_project.h):
+// MaskOp is the above; WindowOp conditions on window means (fd_aggregate.hip: the middle image holds windows, the bases are
+// A_w / B_w) and adds the one body that differs, the time-domain window sum.
 //
 // RePaint resampling (Lugmayr et al. 2022; fd_sampler_run_impute_repaint): the steps are cut into blocks of jump_length, each block
 // runs `resample` times, and between two runs the state is diffused forward from the block's last level to its first by the
@@ -33,26 +38,23 @@
 #include "fd_common.h"
 #include "fd_engine.h"
 #include "fd_loop.h"
-#include "fd_philox.h"
+#include "fd_project.h"
 #include "fd_sde.h"
 
 namespace {
 
-constexpr int kThreads = 512;    // 8 waves: the row tiles of a product are dealt round-robin
-constexpr int kCB = 16;          // channels per workgroup = N of the MFMA tile
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using namespace fdproj;
 
 struct ImpArgs {
     const float* x;          // (B,T,C) state before the step (may alias out)
     const float* score;      // (B,T,C) score at t_i (STEP only)
     const float* zstep;      // (B,T,C) injected predictor noise or nullptr (Philox at off_step)
     const float* x0;         // (B/obs_rep,T,C) A^-1(where(m, y, 0)): state row b reads observation row b / obs_rep
-    const uint8_t* mask;     // (B/obs_rep,T,C) or (T,C), 1 = observed, time domain
+    const uint8_t* mask;     // (B/obs_rep,M,C) or (M,C), 1 = observed, over the operator's M rows (time steps / windows)
     const float* stdv;       // (T,C) feature std of the packed spectrum or nullptr (= 1)
     const float* G;          // (T)
     const float* zobs;       // (B,T,C) injected observation noise or nullptr (Philox at off_obs)
-    const float* basis;      // F (Tp x Tp) then F^T (Tp x Tp)
+    const float* basis;      // the operator's pair: F then F^T (Tp x Tp each), or A_w (Jp x Tp) then B_w (Tp x Jp)
     float* out;
     int B, T, C, Tp, ncb, mask_per_series, obs_rep;
     SdeCoef cf;
@@ -72,79 +74,41 @@ struct ImpArgsOf { typedef ImpArgs type; };
 template <>
 struct ImpArgsOf<true> { typedef ImpArgsPair type; };
 
-// 1 / r of packed row k: 1 at DC and Nyquist (T even), 2 at every other bin (the Hermitian pair it stands for)
-__device__ __forceinline__ float inv_r(int k, int T) { return (k == 0 || (2 * k == T)) ? 1.0f : 2.0f; }
-
-// LDS image index of (k, channel) in k-quad order
-__device__ __forceinline__ int quad_idx(int k, int c) { return ((k >> 2) * kCB + c) * 4 + (k & 3); }
-
+// Op (fd_project.h): the coordinate mask, or window means (fd_aggregate.hip), which go with neither PAIR nor RENOISE.
 // PAIR: the workgroup of (b, channel block) reads x[b], steps with the guided score fd_guided(score[b], score[B + b]) and writes
 // every final value to rows b and B + b, so the two halves stay bit-equal; the Philox counters and lanes are those of the unpaired
 // launch over n = B T C (the second half draws nothing).
 // RENOISE: the projected state is diffused forward in the same pass, out = ra (projected x) + rb G z_r (see the head of the file).
-template <bool STEP, bool FOURIER, bool PAIR = false, bool RENOISE = false>
-__global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::type a) {
+template <bool STEP, bool FOURIER, bool PAIR, bool RENOISE, class Op>
+__global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::type a, Op op) {
+    static_assert(!(Op::kWindow && (PAIR || RENOISE)), "window means go with neither a guide nor RePaint");
+    constexpr bool IMAGE = FOURIER || Op::kWindow;      // the mask in the time domain selects elementwise: no LDS
     extern __shared__ float lds[];
-    float* U = lds;                            // sigma d / r, frequency rows
-    float* W = lds + (size_t)a.Tp * kCB;       // m . idft(sigma d), time rows
+    float* U = lds;                            // FOURIER: sigma d / r, frequency rows (k-quad); else sigma d, time rows [t][channel]
+    float* W = lds + (size_t)a.Tp * kCB;       // FOURIER: m . (the observed rows of idft(sigma d)), the operator's rows (k-quad)
     const int tid = threadIdx.x;
     const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
-    const int T = a.T, C = a.C, Tp = a.Tp;
+    const int T = a.T, C = a.C, Tp = a.Tp, M = op.rows(T), Mp = op.rows_padded(Tp);
     const size_t TC = (size_t)T * C, base = (size_t)b * TC, obase = (size_t)(b / a.obs_rep) * TC;
-    const uint8_t* mrow = a.mask + (a.mask_per_series ? obase : 0);
+    const uint8_t* mrow = a.mask + (a.mask_per_series ? (size_t)(b / a.obs_rep) * M * C : 0);
     [[maybe_unused]] const size_t half = (size_t)a.B * TC;      // PAIR: the null half of x / score / out starts here
 
-    if (FOURIER)
+    if (FOURIER) {
         for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
-    if (FOURIER) __syncthreads();
+        __syncthreads();
+    }
 
-    // ---- phase 1: step + d, over the Philox groups that touch this series (a group straddling two series is drawn by both)
+    // ---- phase 1: step + d, over the Philox groups that touch this series
     const size_t g_lo = base / 4, g_hi = (base + TC + 3) / 4;
     for (size_t g = g_lo + tid; g < g_hi; g += kThreads) {
         int loc[4];
-        bool own[4], any = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const size_t e = g * 4 + j;
-            own[j] = false;
-            loc[j] = 0;
-            if (e >= base && e < base + TC) {
-                loc[j] = (int)(e - base);
-                const int c = loc[j] % C;
-                own[j] = c >= c0 && c < c0 + kCB;
-            }
-            any |= own[j];
-        }
-        if (!any) continue;
+        bool own[4];
+        if (!group_of(g, base, TC, C, c0, loc, own)) continue;
         float zs[4] = {0.f, 0.f, 0.f, 0.f}, zo[4] = {0.f, 0.f, 0.f, 0.f};
-        if (STEP) {
-            if (a.zstep) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (own[j]) zs[j] = a.zstep[base + loc[j]];
-            } else {
-                fd_randn4(a.off_step + g, a.seed, zs);
-            }
-        }
-        if (a.s != 0.f) {        // the hard projection (s = 0) reads no observation noise
-            if (a.zobs) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (own[j]) zo[j] = a.zobs[base + loc[j]];
-            } else {
-                fd_randn4(a.off_obs + g, a.seed, zo);
-            }
-        }
         [[maybe_unused]] float zr[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (RENOISE) {
-            if (a.zre) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (own[j]) zr[j] = a.zre[base + loc[j]];
-            } else {
-                fd_randn4(a.off_re + g, a.seed, zr);
-            }
-        }
+        if (STEP) group_noise(loc, own, a.zstep, base, a.off_step + g, a.seed, zs);
+        if (a.s != 0.f) group_noise(loc, own, a.zobs, base, a.off_obs + g, a.seed, zo);      // the hard projection (s = 0) reads none
+        if constexpr (RENOISE) group_noise(loc, own, a.zre, base, a.off_re + g, a.seed, zr);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (!own[j]) continue;
@@ -158,88 +122,83 @@ __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::t
                 xv = fd_sde_apply(xv, sc, zs[j], Gt, a.cf);
             }
             const float xo = a.alpha * a.x0[obase + loc[j]] + a.s * (Gt * zo[j]);
-            if constexpr (RENOISE) {
-                const float nz = a.rb * (Gt * zr[j]);
-                const float xt = a.ra * xv + nz;
-                if (FOURIER) {
-                    a.out[e] = xt;
-                    const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
-                    U[quad_idx(t, c - c0)] = sd * (a.ra * (xo - xv)) * inv_r(t, T);
-                } else {
-                    const float o = mrow[(size_t)t * C + c] ? a.ra * xo + nz : xt;
-                    a.out[e] = o;
-                    if constexpr (PAIR) a.out[half + e] = o;
+            if constexpr (!IMAGE) {
+                float o = mrow[(size_t)t * C + c] ? xo : xv;
+                if constexpr (RENOISE) {       // (both sums written out: selecting first contracts differently and moves the last bit)
+                    const float nz = a.rb * (Gt * zr[j]);
+                    o = mrow[(size_t)t * C + c] ? a.ra * xo + nz : a.ra * xv + nz;
                 }
-            } else if (FOURIER) {
-                a.out[e] = xv;
-                const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
-                U[quad_idx(t, c - c0)] = sd * (xo - xv) * inv_r(t, T);
-            } else {
-                const float o = mrow[(size_t)t * C + c] ? xo : xv;
                 a.out[e] = o;
                 if constexpr (PAIR) a.out[half + e] = o;
+            } else {
+                float xt = xv, dv = xo - xv;       // what goes to `out` before the projection, and d
+                if constexpr (RENOISE) {
+                    xt = a.ra * xv + a.rb * (Gt * zr[j]);
+                    dv = a.ra * dv;
+                }
+                a.out[e] = xt;
+                const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
+                if (FOURIER) U[quad_idx(t, c - c0)] = sd * dv * inv_r(t, T);
+                else U[t * kCB + (c - c0)] = sd * dv;
             }
         }
     }
-    if (!FOURIER) return;
-    __syncthreads();     // U complete; out holds x_new (workgroup-scope release / acquire covers the global stores)
+    if constexpr (IMAGE) __syncthreads();     // U complete; out holds x_new (workgroup-scope release / acquire covers the global stores)
 
-    const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
-    const int li = lane & 15, kq = lane >> 4;
-    const int ntile = Tp / 16;
-    const float* Fm = a.basis;
-    const float* Ft = a.basis + (size_t)Tp * Tp;
-
-    // ---- phase 2: V = F^T U (row i of the tile = time t0 + i); W = m ? V : 0
-    for (int tile = wave; tile < ntile; tile += nw) {
-        const int t0 = tile * 16;
-        const float* arow = Ft + (size_t)(t0 + li) * Tp + 4 * kq;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < Tp; k0 += 16) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(U + ((k0 / 4 + kq) * kCB + li) * 4);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+    if constexpr (Op::kWindow && !FOURIER) {
+        // ---- window means in the time domain: one thread per (window, channel), the mean in ascending t, masked, written back
+        // over the window
+        for (int i = tid; i < M * kCB; i += kThreads) {
+            const int j = i / kCB, cl = i % kCB, c = c0 + cl;
+            if (c >= C || !mrow[(size_t)j * C + c]) continue;
+            const int t0 = j * op.window, l = win_len(j, op.window, T);
+            float sum = 0.f;
+            for (int k = 0; k < l; ++k) sum += U[(t0 + k) * kCB + cl];
+            const float mean = sum / (float)l;
+            for (int k = 0; k < l; ++k) {
+                const size_t tc = (size_t)(t0 + k) * C + c;
+                const float sd = a.stdv ? a.stdv[tc] : 1.0f;
+                a.out[base + tc] += mean / sd;
+            }
         }
-        // lane holds V[t0 + 4 kq + v][li], v = 0..3: one k-quad of W
-        const int c = c0 + li;
-        f32x4 w;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int t = t0 + 4 * kq + v;
-            const bool keep = t < T && c < C && mrow[(size_t)t * C + c];
-            w[v] = keep ? acc0[v] + acc1[v] : 0.f;
-        }
-        *reinterpret_cast<f32x4*>(W + ((t0 / 4 + kq) * kCB + li) * 4) = w;
     }
-    __syncthreads();
-
-    // ---- phase 3: Y = F W (row i of the tile = packed row r0 + i); out += Y / sigma
-    for (int tile = wave; tile < ntile; tile += nw) {
-        const int r0 = tile * 16;
-        const float* arow = Fm + (size_t)(r0 + li) * Tp + 4 * kq;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < Tp; k0 += 16) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(arow + k0);
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(W + ((k0 / 4 + kq) * kCB + li) * 4);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
-        }
+    if constexpr (FOURIER) {
+        const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
+        const int li = lane & 15, kq = lane >> 4;
         const int c = c0 + li;
-        if (c >= C) continue;
+        const float* Ao = op.to_obs(a.basis, Tp);
+        const float* Bo = op.from_obs(a.basis, Tp);
+
+        // ---- phase 2: W = m . (Ao U) (row i of the tile = observation row j0 + i: a time step or a window)
+        for (int tile = wave; tile < Mp / 16; tile += nw) {
+            const int j0 = tile * 16;
+            const f32x4 acc = tile_product(Ao, j0, Tp, U, li, kq);
+            f32x4 w;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int r = r0 + 4 * kq + v;
-            if (r >= T) continue;
-            const size_t e = base + (size_t)r * C + c;
-            const float sd = a.stdv ? a.stdv[(size_t)r * C + c] : 1.0f;
-            const float o = a.out[e] + (acc0[v] + acc1[v]) / sd;
-            a.out[e] = o;
-            if constexpr (PAIR) a.out[half + e] = o;
+            for (int v = 0; v < 4; ++v) {
+                const int j = j0 + 4 * kq + v;
+                const bool keep = j < M && c < C && mrow[(size_t)j * C + c];
+                w[v] = keep ? acc[v] : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(W + ((j0 / 4 + kq) * kCB + li) * 4) = w;
+        }
+        __syncthreads();
+
+        // ---- phase 3: Y = Bo W (row i of the tile = packed row r0 + i); out += Y / sigma
+        for (int tile = wave; tile < Tp / 16; tile += nw) {
+            const int r0 = tile * 16;
+            const f32x4 acc = tile_product(Bo, r0, Mp, W, li, kq);
+            if (c >= C) continue;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int r = r0 + 4 * kq + v;
+                if (r >= T) continue;
+                const size_t e = base + (size_t)r * C + c;
+                const float sd = a.stdv ? a.stdv[(size_t)r * C + c] : 1.0f;
+                const float o = a.out[e] + acc[v] / sd;
+                a.out[e] = o;
+                if constexpr (PAIR) a.out[half + e] = o;
+            }
         }
     }
 }
@@ -263,15 +222,10 @@ __global__ __launch_bounds__(256) void k_impute_basis(float* __restrict__ Fm, fl
     }
 }
 
-template <bool STEP, bool FOURIER, bool PAIR = false, bool RENOISE = false>
-int launch_variant(fd_ctx* ctx, const typename ImpArgsOf<PAIR>::type& a, size_t lds, hipStream_t s) {
-    static unsigned long long attr_set = 0;
-    if (FOURIER && fd_first_on_device(attr_set, ctx->device))
-        FD_HIP(ctx, hipFuncSetAttribute((const void*)k_impute<STEP, FOURIER, PAIR, RENOISE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024));
-    hipLaunchKernelGGL((k_impute<STEP, FOURIER, PAIR, RENOISE>), dim3((unsigned)(a.B * a.ncb)), dim3(kThreads), FOURIER ? lds : 0, s, a);
-    FD_LAUNCH_CHECK(ctx);
-    return FD_OK;
+template <bool STEP, bool FOURIER, bool PAIR = false, bool RENOISE = false, class Op = MaskOp>
+int launch_variant(fd_ctx* ctx, const typename ImpArgsOf<PAIR>::type& a, hipStream_t s, Op op = Op()) {
+    return launch_kernel<k_impute<STEP, FOURIER, PAIR, RENOISE, Op>, (Op::kWindow ? 128 : 160) * 1024>(
+        ctx, (unsigned)(a.B * a.ncb), image_bytes(op, a.T, a.Tp, FOURIER), s, a, op);
 }
 
 // fills the shape / conditioning fields of `a` and checks them
@@ -296,43 +250,35 @@ int prepare(fd_ctx* ctx, ImpArgs& a, const float* x0, const uint8_t* mask, int m
     return FD_OK;
 }
 
-// renoise: the RENOISE variants (a.ra, a.rb, a.zre, a.off_re set): the loop's fused step, or the step-wise projection
-int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s, bool renoise = false) {
-    const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
-    if (renoise) {
-        if (step) return fourier ? launch_variant<true, true, false, true>(ctx, a, lds, s)
-                                 : launch_variant<true, false, false, true>(ctx, a, lds, s);
-        return fourier ? launch_variant<false, true, false, true>(ctx, a, lds, s)
-                       : launch_variant<false, false, false, true>(ctx, a, lds, s);
-    }
-    if (step) return fourier ? launch_variant<true, true>(ctx, a, lds, s) : launch_variant<true, false>(ctx, a, lds, s);
-    return fourier ? launch_variant<false, true>(ctx, a, lds, s) : launch_variant<false, false>(ctx, a, lds, s);
+// renoise (the mask alone): the RENOISE variants (a.ra, a.rb, a.zre, a.off_re set): the loop's fused step, or the step-wise projection
+template <class Op = MaskOp>
+int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s, bool renoise = false, Op op = Op()) {
+    if constexpr (!Op::kWindow)
+        if (renoise) {
+            if (step) return fourier ? launch_variant<true, true, false, true>(ctx, a, s) : launch_variant<true, false, false, true>(ctx, a, s);
+            return fourier ? launch_variant<false, true, false, true>(ctx, a, s) : launch_variant<false, false, false, true>(ctx, a, s);
+        }
+    if (step)
+        return fourier ? launch_variant<true, true, false, false>(ctx, a, s, op) : launch_variant<true, false, false, false>(ctx, a, s, op);
+    return fourier ? launch_variant<false, true, false, false>(ctx, a, s, op) : launch_variant<false, false, false, false>(ctx, a, s, op);
 }
 
 // the guided step + projection on the paired state (a.B series, 2 a.B rows)
 int launch_pair(fd_ctx* ctx, const ImpArgs& a, const fd_guide& g, bool fourier, hipStream_t s, bool renoise = false) {
-    const size_t lds = (size_t)2 * a.Tp * kCB * sizeof(float);
     ImpArgsPair ap{};
     static_cast<ImpArgs&>(ap) = a;
     ap.w = g.w;
     ap.omw = g.omw;
-    if (renoise)
-        return fourier ? launch_variant<true, true, true, true>(ctx, ap, lds, s) : launch_variant<true, false, true, true>(ctx, ap, lds, s);
-    return fourier ? launch_variant<true, true, true>(ctx, ap, lds, s) : launch_variant<true, false, true>(ctx, ap, lds, s);
+    if (renoise) return fourier ? launch_variant<true, true, true, true>(ctx, ap, s) : launch_variant<true, false, true, true>(ctx, ap, s);
+    return fourier ? launch_variant<true, true, true>(ctx, ap, s) : launch_variant<true, false, true>(ctx, ap, s);
 }
 
-// window means (fd_aggregate.hip): the fields of `a` under the window geometry p; a.mask is (B/obs_rep,J,C) or (J,C), stdv is read in
-// both domains
-int launch_agg(fd_ctx* ctx, const ImpArgs& a, const fd_agg_plan& p, const float* stdv, bool step, bool fourier, hipStream_t s) {
-    fd_agg_imp_args g{};
-    g.x = a.x; g.score = a.score; g.zstep = a.zstep; g.x0 = a.x0; g.mask = a.mask; g.stdv = stdv; g.G = a.G; g.zobs = a.zobs;
-    g.out = a.out;
-    g.B = a.B; g.T = a.T; g.C = a.C; g.Tp = a.Tp; g.ncb = a.ncb; g.mask_per_series = a.mask_per_series; g.obs_rep = a.obs_rep;
-    g.cf = a.cf;
-    g.alpha = a.alpha; g.s = a.s;
-    g.seed = a.seed; g.off_step = a.off_step; g.off_obs = a.off_obs;
-    g.p = p;
-    return fd_agg_launch_impute(ctx, g, step, fourier, s);
+// window means: the geometry of (T, window) and, in `a`, what the window operator reads in the mask's place (fd_aggregate.h)
+int prepare_window(fd_ctx* ctx, ImpArgs& a, int window, const float* stdv, int fourier, hipStream_t s, fd_agg_plan* agg, const char* who) {
+    if (int rc = fd_agg_prepare(ctx, a.T, a.Tp, window, fourier, s, agg, who)) return rc;
+    a.stdv = stdv;
+    a.basis = agg->basis;
+    return FD_OK;
 }
 
 // (alpha, s) of level i of an n-step grid: the perturbation kernel at timesteps[i], the clean level (1, 0) at i = n
@@ -363,11 +309,11 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
     ImpArgs a{};
     if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, s, who)) return rc;
     a.obs_rep = obs_replicas;
-    // window > 1: the mask holds windows and fd_aggregate.hip's kernel takes the place of k_impute (no guide and no RePaint there)
+    // window > 1: the mask holds windows and k_impute runs on the window operator (no guide and no RePaint there)
     fd_agg_plan agg{};
     if (window > 1) {
         FD_REQUIRE(ctx, !g && resample == 1, "%s: window=%d goes with neither a guide nor resample > 1", who, window);
-        if (int rc = fd_agg_prepare(ctx, T, a.Tp, window, fourier, s, &agg, who)) return rc;
+        if (int rc = prepare_window(ctx, a, window, feat_std, fourier, s, &agg, who)) return rc;
     }
     // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
     // at the next grid point; the last step projects hard (alpha = 1, s = 0)
@@ -437,7 +383,7 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
             ++k;
         }
         if (window > 1) {
-            if (int rc = launch_agg(ctx, a, agg, feat_std, true, fourier != 0, s)) return rc;
+            if (int rc = launch(ctx, a, true, fourier != 0, s, false, agg.op)) return rc;
             continue;
         }
         if (int rc = pair ? launch_pair(ctx, a, *g, fourier != 0, s, renoise) : launch(ctx, a, true, fourier != 0, s, renoise)) return rc;
@@ -447,24 +393,11 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
 
 }  // namespace
 
-constexpr int kBasisKey = 2 << 20;     // ctx->fft_tw key -T - kBasisKey (fd_fourier.hip uses T, -T and -T - 2^20)
-
 const float* fd_impute_basis(fd_ctx* ctx, int T, int Tp, hipStream_t s) {
-    const int key = -T - kBasisKey;
-    for (auto& e : ctx->fft_tw)
-        if (e.first == key) return reinterpret_cast<const float*>(e.second);
-    void* d = nullptr;
-    if (hipMalloc(&d, sizeof(float) * 2 * (size_t)Tp * Tp) != hipSuccess) return nullptr;
-    float* Fm = reinterpret_cast<float*>(d);
-    hipLaunchKernelGGL(k_impute_basis, dim3((unsigned)std::min<size_t>(((size_t)Tp * Tp + 255) / 256, 4096)), dim3(256), 0, s, Fm,
-                       Fm + (size_t)Tp * Tp, T, Tp);
-    // once per (context, T): later callers may use another stream
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-        (void)hipFree(d);
-        return nullptr;
-    }
-    ctx->fft_tw.emplace_back(key, d);
-    return Fm;
+    const size_t n = (size_t)Tp * Tp;
+    return fdproj::cached_table(ctx, -T - (2 << 20), 2 * n, s, [&](float* Fm) {
+        hipLaunchKernelGGL(k_impute_basis, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, s, Fm, Fm + n, T, Tp);
+    });
 }
 
 // marginal mean coefficient and std of the perturbation kernel at t (sde.py:108-123, 187-210), in double
@@ -507,12 +440,12 @@ extern "C" int fd_impute_project_agg(fd_ctx* ctx, const float* x, const float* x
     ImpArgs a{};
     if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, fourier, G, B, T, C, hs, "fd_impute_project_agg")) return rc;
     fd_agg_plan agg{};
-    if (int rc = fd_agg_prepare(ctx, T, a.Tp, window, fourier, hs, &agg, "fd_impute_project_agg")) return rc;
+    if (int rc = prepare_window(ctx, a, window, feat_std, fourier, hs, &agg, "fd_impute_project_agg")) return rc;
     a.x = x; a.out = out;
     a.zobs = z;
     a.alpha = alpha; a.s = s;
     a.seed = seed; a.off_obs = offset;
-    return launch_agg(ctx, a, agg, feat_std, false, fourier != 0, hs);
+    return launch(ctx, a, false, fourier != 0, hs, false, agg.op);
 }
 
 extern "C" int fd_impute_project_renoise(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
