@@ -21,6 +21,7 @@ FD_MODE_BF16 = 1
 FD_COMM_ID_BYTES = 128
 FD_BACKBONE_TRANSFORMER, FD_BACKBONE_MLP, FD_BACKBONE_LSTM = 0, 1, 2
 FD_VARIOGRAM_HALF, FD_VARIOGRAM_ONE, FD_VARIOGRAM_TWO = 0, 1, 2
+FD_POSTHOC_CLASSIFY, FD_POSTHOC_PREDICT = 0, 1
 
 
 class FdError(RuntimeError):
@@ -203,6 +204,12 @@ _PROTOS = {
                                          C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fd_series_dependence_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_series_dependence": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fd_posthoc_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, _vp, _vp, _vp, _vp]),
+    "fd_posthoc_head": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "fd_posthoc_fit_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_posthoc_fit": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64,
+                                 C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

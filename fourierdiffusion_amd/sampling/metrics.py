@@ -10,7 +10,9 @@ time warping (utils/dtw.py), which see a training series replayed a few samples 
 `SinkhornDivergence`, the debiased entropic transport cost between the two sets in their full sample space (utils/sinkhorn.py): the
 Wasserstein-2 distance that the sliced metric stands in for; and `TemporalDependence`, the first metric that looks INSIDE a series
 (utils/dependence.py): differences of the mean autocorrelation, of the mean cross-correlation between channels and of the skewness
-and kurtosis between the samples and the real set."""
+and kurtosis between the samples and the real set; and `DiscriminativeScore` / `PredictiveScore`, the two post-hoc scores of TimeGAN
+and TSGBench (utils/posthoc.py): a small causal LSTM trained on the engine after the fact, to tell the samples from real series, and
+to forecast real series after training on the samples."""
 from __future__ import annotations
 
 import inspect
@@ -26,6 +28,8 @@ from ..utils.dependence import resolve_lags, series_dependence
 from ..utils.dtw import _series_shape, _window, dtw_ball_counts, dtw_knn
 from ..utils.fourier import dft, spectral_density
 from ..utils.neighbours import MAX_K, ball_counts, knn
+from ..utils.posthoc import MAX_D_MODEL as POSTHOC_MAX_D_MODEL
+from ..utils.posthoc import discriminative_score, predictive_score
 from ..utils.sinkhorn import DEFAULT_REG, sinkhorn_divergence
 from ..utils.tensors import check_flat_array
 from ..utils.two_sample import DEFAULT_SCALES, MAX_COLUMNS, _check_scales, mmd_permutation_test
@@ -602,3 +606,123 @@ class TemporalDependence(Metric):
     @property
     def name(self) -> str:
         return "temporal_dependence"
+
+
+class _PosthocScore(Metric):
+    """What the two post-hoc scores share (utils/posthoc.py): (n, T, C) original samples, the knobs of the network and its training,
+    the rows of a flat array seen as series again."""
+    views = ("time",)
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 steps: int = 2000, batch_size: int = 128, lr: float = 1e-3, d_model: int = 32, num_layers: int = 1,
+                 max_samples: int = 10_000, random_seed: int = 0) -> None:
+        who = type(self).__name__
+        if len(tuple(original_samples.shape)) != 3:
+            raise ValueError(f"{who} needs the original samples as (n, T, C) series, got shape {tuple(original_samples.shape)}: a "
+                             "flat (n, d) array has lost its time axis")
+        T, C = (int(v) for v in tuple(original_samples.shape)[1:])
+        self.series_shape = (T, C)
+        if len(original_samples) < 2:
+            raise ValueError(f"{who} needs at least two original samples")
+        if holdout_samples is not None:
+            if len(holdout_samples) < 2:
+                raise ValueError(f"{who} needs at least two held-out samples")
+            if int(np.prod(tuple(holdout_samples.shape)[1:])) != T * C:
+                raise ValueError("original and held-out samples must have the same number of features")
+        if d_model % 2 != 0 or not 2 <= d_model <= POSTHOC_MAX_D_MODEL:
+            raise ValueError(f"d_model={d_model} must be even and <= {POSTHOC_MAX_D_MODEL}, the widest LSTM the engine trains")
+        super().__init__(original_samples=original_samples)
+        self.holdout_samples = check_flat_array(holdout_samples) if holdout_samples is not None else None
+        self.random_seed = random_seed
+        self.knobs = dict(steps=steps, batch_size=batch_size, lr=lr, d_model=d_model, num_layers=num_layers, max_samples=max_samples)
+        self._baseline: Optional[dict[str, float]] = None
+
+    def _series(self, rows: torch.Tensor) -> torch.Tensor:
+        T, C = self.series_shape
+        if rows.dim() != 2 or rows.shape[1] != T * C:
+            raise ValueError(f"samples of {tuple(rows.shape[1:])} features, the original samples are series of shape {(T, C)}")
+        return rows.view(rows.shape[0], T, C)
+
+    def _folds(self) -> tuple[torch.Tensor, torch.Tensor]:
+        real = self._series(self.original_samples)
+        return real[: real.shape[0] // 2], real[real.shape[0] // 2:]
+
+
+class DiscriminativeScore(_PosthocScore):
+    """Can a classifier trained after the fact tell the samples from real series (TimeGAN / TSGBench)?  A small causal LSTM is
+    trained on the engine to separate the two sets, standardised with the real set's statistics, and tested on rows it has not seen:
+      discriminative_score, discriminative_accuracy   |accuracy - 0.5| and the accuracy, samples against the original samples
+      ..._holdout                                     (with `holdout_samples`) against real series the model was not trained on
+      discriminative_score_self                       (baseline) two folds of the original samples against each other: about 0
+    One training run per key pair, `steps` AdamW steps of `batch_size`; deterministic given `random_seed`.  Needs (n, T, C) original
+    samples; bound in the time view only."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 steps: int = 2000, batch_size: int = 128, lr: float = 1e-3, d_model: int = 32, num_layers: int = 1,
+                 test_fraction: float = 0.2, max_samples: int = 10_000, random_seed: int = 0) -> None:
+        if not 0.0 < test_fraction < 1.0:
+            raise ValueError(f"test_fraction={test_fraction} must lie strictly between 0 and 1")
+        super().__init__(original_samples=original_samples, holdout_samples=holdout_samples, steps=steps, batch_size=batch_size, lr=lr,
+                         d_model=d_model, num_layers=num_layers, max_samples=max_samples, random_seed=random_seed)
+        self.knobs["test_fraction"] = test_fraction
+
+    def _score(self, real: torch.Tensor, other: torch.Tensor) -> dict:
+        return discriminative_score(real, other, seed=self.random_seed, **self.knobs)
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = self._series(check_flat_array(other_samples))
+        res = self._score(self._series(self.original_samples), samples)
+        out = {"discriminative_score": res["score"], "discriminative_accuracy": res["accuracy"]}
+        if self.holdout_samples is not None:
+            res = self._score(self._series(self.holdout_samples), samples)
+            out.update(discriminative_score_holdout=res["score"], discriminative_accuracy_holdout=res["accuracy"])
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        if self._baseline is None:
+            self._baseline = {"discriminative_score_self": self._score(*self._folds())["score"]}
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "discriminative_score"
+
+
+class PredictiveScore(_PosthocScore):
+    """Are the samples as useful as real data for forecasting ("train on synthetic, test on real", TimeGAN / TSGBench)?  A small
+    causal LSTM is trained on the engine to forecast the next point of the SAMPLES and tested on real series; the score is its mean
+    absolute one-step error in units of the real set's per-channel deviation:
+      predictive_score            trained on the samples, tested on the original samples
+      predictive_score_holdout    (with `holdout_samples`) the same, tested on real series the model was not trained on
+      predictive_score_self       (baseline) trained on one fold of the original samples, tested on the other
+    Deterministic given `random_seed`.  Needs (n, T, C) original samples with T >= 2; bound in the time view only."""
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 steps: int = 2000, batch_size: int = 128, lr: float = 1e-3, d_model: int = 32, num_layers: int = 1,
+                 max_samples: int = 10_000, random_seed: int = 0) -> None:
+        super().__init__(original_samples=original_samples, holdout_samples=holdout_samples, steps=steps, batch_size=batch_size, lr=lr,
+                         d_model=d_model, num_layers=num_layers, max_samples=max_samples, random_seed=random_seed)
+        if self.series_shape[0] < 2:
+            raise ValueError("PredictiveScore forecasts x[t + 1] from x[<= t] and needs series of at least 2 points")
+
+    def _score(self, train_set: torch.Tensor, test_set: torch.Tensor) -> float:
+        return predictive_score(train_set, test_set, stats_from=self._series(self.original_samples), seed=self.random_seed,
+                                **self.knobs)["mae"]
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = self._series(check_flat_array(other_samples))
+        out = {"predictive_score": self._score(samples, self._series(self.original_samples))}
+        if self.holdout_samples is not None:
+            out["predictive_score_holdout"] = self._score(samples, self._series(self.holdout_samples))
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        if self._baseline is None:
+            self._baseline = {"predictive_score_self": self._score(*self._folds())}
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "predictive_score"

@@ -907,6 +907,54 @@ int fd_series_dependence(fd_ctx* ctx, const float* x, int n, int T, int C, int a
                          float* out_ccf /* (n, Lx + 1, C, C) or NULL */, double* out_set_mean /* (F) or NULL */, void* work,
                          size_t work_bytes, void* stream);
 
+/* Post-hoc discriminative and predictive scores (NOT in the reference; TimeGAN, Yoon et al. 2019, and TSGBench; DESIGN.md 3.31,
+ * utils/posthoc.py): what a small network trained AFTER the fact needs around the causal LSTM backbone (fd_score_create_ex with
+ * FD_BACKBONE_LSTM), whose output at time t sees the inputs <= t only -- out[:, t] regressed on x[:, t + 1] is a next-step
+ * forecaster, the mean over channels of out[:, T - 1] a classifier logit.  Plain fp32 / fp64 kernels (csrc/fd_posthoc.hip), no
+ * atomics, every sum in double in an order that depends on the shape alone: two runs are bit-identical.
+ *
+ * fd_posthoc_batch   one minibatch drawn and gathered on the device.  a (na, T, C), b (nb, T, C): dense fp32 device pools; mean,
+ *                    inv_std: fp32[C].  x (B, T, C) = (row - mean) * inv_std (one subtraction, one product, each rounded once),
+ *                    label (B) and idx (B) int32.  FD_POSTHOC_CLASSIFY (b non-null, B even): rows j < B / 2 come from a with label 1,
+ *                    the others from b with label 0.  FD_POSTHOC_PREDICT: every row from a, label 1, b and nb ignored.
+ *                    Index rule, restatable from fd_philox_words: row j of step s takes word j % 4 of counter
+ *                    offset + s * ceil(B / 4) + j / 4 under the key seed; idx = (uint64(word) * n) >> 32, n the size of the pool the
+ *                    row draws from (with replacement).
+ * fd_posthoc_head    the task head, its loss and d loss / d out in one pass over out (B, T, C).
+ *                    PREDICT:  loss = mean over b, t < T - 1, c of |out[b,t,c] - x[b,t+1,c]|; dout = sign(diff) / (B (T - 1) C) with
+ *                              sign(0) = 0 and the rows t = T - 1 exactly 0; per_series[b] = that series' sum of absolute errors;
+ *                              label unused (may be NULL); T < 2: FD_ERR_ARG.
+ *                    CLASSIFY: logit_b = mean_c out[b, T - 1, c]; loss = mean_b (softplus(logit_b) - label_b logit_b), softplus(v) =
+ *                              max(v, 0) + log1p(exp(-|v|)); dout[b, T - 1, c] = (sigmoid(logit_b) - label_b) / (B C), exactly 0
+ *                              everywhere else; per_series[b] = logit_b; x unused (may be NULL); label may be NULL when loss and
+ *                              dout both are (the logits alone).
+ *                    Differences, sums, sigmoid and softplus in double; loss and dout are rounded to fp32 once.  per_series: B DOUBLES,
+ *                    required.  loss == NULL: not computed; dout == NULL: evaluation only.
+ * fd_posthoc_fit     the training loop as ONE call: for k = 0 .. steps - 1, with s = first_step + k, it enqueues fd_posthoc_batch
+ *                    (step s) -> fd_score_forward_train (t = 0 on every row, dropout 0) -> fd_posthoc_head -> fd_score_backward
+ *                    (accumulate 0) -> [fd_grad_sqnorm, when max_norm > 0] -> fd_adamw_step (step s + 1, constant lr, betas (0.9, 0.999),
+ *                    eps 1e-8, weight_decay 1e-2, time_encoder.W skipped), with no host synchronisation; the same calls made one by
+ *                    one give the same bits.  T and C are the model's.  params: the buffer fd_score_prepare bound (FD_ERR_ARG
+ *                    otherwise); grads, exp_avg, exp_avg_sq: its size.  loss_trace: device float[steps], the loss of every step
+ *                    BEFORE its update.  idx_trace: device int32[steps * B] or NULL, the indices of every step.  work: caller-owned
+ *                    device bytes, at least fd_posthoc_fit_workspace_bytes(B, T, C).  The weights changed: call fd_score_prepare
+ *                    (or mark the parameters changed) before the model is used through another entry point.
+ *                    FD_ERR_UNSUPPORTED for a model whose backbone is not the LSTM (nothing is launched).
+ * FD_ERR_ARG (nothing is launched): an unknown task, a null pointer other than those named optional, a shape < 1, B T C >= 2^31,
+ * classify with b null, nb < 1 or an odd B, step or first_step < 0, steps < 1, lr <= 0, a workspace that is null or too small. */
+#define FD_POSTHOC_CLASSIFY 0
+#define FD_POSTHOC_PREDICT 1
+int fd_posthoc_batch(fd_ctx* ctx, int task, const float* a, int na, const float* b /* or NULL */, int nb, const float* mean,
+                     const float* inv_std, uint64_t seed, uint64_t offset, int step, int B, int T, int C, float* x /* (B, T, C) */,
+                     int* label /* (B) */, int* idx /* (B) */, void* stream);
+int fd_posthoc_head(fd_ctx* ctx, int task, const float* out, const float* x, const int* label, int B, int T, int C,
+                    float* loss /* (1) or NULL */, float* dout /* (B, T, C) or NULL */, double* per_series /* (B) */, void* stream);
+int fd_posthoc_fit_workspace_bytes(fd_ctx* ctx, int B, int T, int C, size_t* bytes);
+int fd_posthoc_fit(fd_score* m, int task, float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* a, int na,
+                   const float* b /* or NULL */, int nb, const float* mean, const float* inv_std, uint64_t seed, uint64_t offset,
+                   int first_step, int steps, int B, float lr, float max_norm, float* loss_trace /* (steps) */,
+                   int* idx_trace /* (steps, B) or NULL */, void* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
