@@ -61,8 +61,20 @@ class SamplingRunner:
         self.metrics = None
         if "metrics" in cfg and cfg.metrics is not None and self.dist.is_main:
             # a metrics config with `holdout: true` (metrics=neighbours) also gets the held-out split, for the memorisation metrics
-            node = {k: v for k, v in cfg.metrics.items() if k != "holdout"}
-            bound = {"holdout_samples": self.datamodule.X_test} if cfg.metrics.get("holdout", False) else {}
+            # and one with `labels: true` (metrics=conditional) the classes of both splits, for the label-aware metrics
+            node = {k: v for k, v in cfg.metrics.items() if k not in ("holdout", "labels")}
+            holdout = bool(cfg.metrics.get("holdout", False))
+            bound = {"holdout_samples": self.datamodule.X_test} if holdout else {}
+            if cfg.metrics.get("labels", False):
+                if getattr(self.datamodule, "y_train", None) is None:
+                    raise ValueError(f"the metrics config asks for labels (labels: true), but {type(self.datamodule).__name__} has no "
+                                     "labels (y_train is None): use a labelled datamodule or a metrics config without `labels`")
+                if self.score_model.n_classes <= 0 and self.sampler.labels is None:
+                    raise ValueError("the metrics config asks for labels (labels: true), but no labels will be drawn: the model is "
+                                     "not class-conditional and sampler.labels is null")
+                bound["original_labels"] = self.datamodule.y_train
+                if holdout:
+                    bound["holdout_labels"] = self.datamodule.y_test
             self.metrics = instantiate(node)(original_samples=self.datamodule.X_train, **bound)
 
     def sample(self) -> None:
@@ -97,7 +109,8 @@ class SamplingRunner:
         if self.dist.is_main:
             results = {"num_samples": int(X.shape[0]), "sample_mean": float(X.mean()), "sample_std": float(X.std())}
             if self.metrics is not None:
-                results.update(self.metrics(X))                                     # reference cmd/sample.py:84-86
+                # reference cmd/sample.py:84-86; the classes the samples were drawn for go to the label-aware metrics only
+                results.update(self.metrics(X, other_labels=labels))
             logging.info(f"Saving samples ands metrics to {self.save_dir}.\n{dict_to_str(results)}")
             yaml.dump(data=results, stream=open(self.save_dir / "results.yaml", "w"))
             torch.save(X, self.save_dir / "samples.pt")

@@ -22,6 +22,7 @@ FD_COMM_ID_BYTES = 128
 FD_BACKBONE_TRANSFORMER, FD_BACKBONE_MLP, FD_BACKBONE_LSTM = 0, 1, 2
 FD_VARIOGRAM_HALF, FD_VARIOGRAM_ONE, FD_VARIOGRAM_TWO = 0, 1, 2
 FD_POSTHOC_CLASSIFY, FD_POSTHOC_PREDICT = 0, 1
+FD_POSTHOC_MAX_CLASSES = 256
 
 
 class FdError(RuntimeError):
@@ -210,6 +211,14 @@ _PROTOS = {
     "fd_posthoc_fit_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_posthoc_fit": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64,
                                  C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fd_posthoc_batch_labelled": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "fd_posthoc_head_multiclass": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fd_posthoc_fit_multiclass_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_posthoc_fit_multiclass": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_uint64,
+                                            C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _vp, _vp, _vp, C.c_size_t,
+                                            _vp]),
+    "fd_posthoc_confusion": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -12,7 +12,9 @@ Wasserstein-2 distance that the sliced metric stands in for; and `TemporalDepend
 (utils/dependence.py): differences of the mean autocorrelation, of the mean cross-correlation between channels and of the skewness
 and kurtosis between the samples and the real set; and `DiscriminativeScore` / `PredictiveScore`, the two post-hoc scores of TimeGAN
 and TSGBench (utils/posthoc.py): a small causal LSTM trained on the engine after the fact, to tell the samples from real series, and
-to forecast real series after training on the samples."""
+to forecast real series after training on the samples; and `ClassificationScore`, the first metric that reads a LABEL (TSTR / TRTS
+classification accuracy, utils/posthoc.py): a K-way classifier trained after the fact on the samples with the classes they were drawn
+for and tested on real series, and the other way round."""
 from __future__ import annotations
 
 import inspect
@@ -28,8 +30,9 @@ from ..utils.dependence import resolve_lags, series_dependence
 from ..utils.dtw import _series_shape, _window, dtw_ball_counts, dtw_knn
 from ..utils.fourier import dft, spectral_density
 from ..utils.neighbours import MAX_K, ball_counts, knn
+from ..utils.posthoc import MAX_CLASSES as POSTHOC_MAX_CLASSES
 from ..utils.posthoc import MAX_D_MODEL as POSTHOC_MAX_D_MODEL
-from ..utils.posthoc import discriminative_score, predictive_score
+from ..utils.posthoc import discriminative_score, fit_classifier, predictive_score
 from ..utils.sinkhorn import DEFAULT_REG, sinkhorn_divergence
 from ..utils.tensors import check_flat_array
 from ..utils.two_sample import DEFAULT_SCALES, MAX_COLUMNS, _check_scales, mmd_permutation_test
@@ -62,6 +65,10 @@ def _takes_holdout(make: partial) -> bool:
     return "holdout_samples" in inspect.signature(make.func).parameters
 
 
+def _takes_labels(make: partial) -> bool:
+    return "original_labels" in inspect.signature(make.func).parameters
+
+
 def subsample_indices(n: int, size: int, seed: int) -> np.ndarray:
     """`size` of the n row indices, drawn without replacement from numpy's Generator(seed), ascending."""
     return np.sort(np.random.default_rng(seed).choice(n, size=size, replace=False))
@@ -77,11 +84,12 @@ class _View:
     def _prefixed(self, results) -> dict[str, Any]:
         return {f"{self.prefix}_{key}": val for res in results for key, val in res.items()}
 
-    def evaluate(self, samples: torch.Tensor) -> dict[str, Any]:
+    def evaluate(self, samples: torch.Tensor, labels=None) -> dict[str, Any]:
         if not self.metrics:
             return {}
         mapped = self.transform(samples)
-        return self._prefixed(m(mapped) for m in self.metrics)
+        # the labels go only to the metrics that say they read them
+        return self._prefixed(m(mapped, labels) if getattr(m, "needs_labels", False) else m(mapped) for m in self.metrics)
 
     def baselines(self) -> dict[str, Any]:
         return self._prefixed(m.baseline_metrics for m in self.metrics)
@@ -95,11 +103,16 @@ class MetricCollection:
     returns the union of the views' results (+ the time / freq baselines) sorted by key.
 
     `holdout_samples` (not in the reference): real samples the model was not trained on, mapped into each view like the original
-    samples and handed to the metrics whose class takes them (`Memorisation`); without it nothing changes."""
+    samples and handed to the metrics whose class takes them (`Memorisation`); without it nothing changes.
+
+    `original_labels` / `holdout_labels` (not in the reference): the class of every original / held-out sample, handed to the metrics
+    whose class takes `original_labels` (`ClassificationScore`); such a metric gets the held-out samples only together with their
+    labels.  A call passes `other_labels`, the classes the samples were drawn for, to the metrics with `needs_labels` set and to no
+    other: a collection without one returns the same with and without labels."""
 
     def __init__(self, metrics: list, original_samples: Optional[np.ndarray | torch.Tensor] = None,
                  include_baselines: bool = True, include_spectral_density: bool = False,
-                 holdout_samples: Optional[np.ndarray | torch.Tensor] = None) -> None:
+                 holdout_samples: Optional[np.ndarray | torch.Tensor] = None, original_labels=None, holdout_labels=None) -> None:
         factories = [m for m in metrics if isinstance(m, partial)]      # (like the reference, only partials are taken up)
         if factories and original_samples is None:
             raise AssertionError("Original samples must be provided for the metrics to be instantiated.")
@@ -110,12 +123,17 @@ class MetricCollection:
             wanted = [make for make in factories if view.prefix in getattr(make.func, "views", Metric.views)]
             if wanted:
                 bound_to = view.transform(original)
-                if holdout is None:
-                    view.metrics = [make(original_samples=bound_to) for make in wanted]
-                else:
-                    held = view.transform(holdout)
-                    view.metrics = [make(original_samples=bound_to, holdout_samples=held) if _takes_holdout(make)
-                                    else make(original_samples=bound_to) for make in wanted]
+                held = view.transform(holdout) if holdout is not None else None
+                for make in wanted:
+                    extra: dict[str, Any] = {}
+                    labelled = _takes_labels(make)
+                    if labelled:
+                        extra["original_labels"] = original_labels
+                    if held is not None and _takes_holdout(make) and (not labelled or holdout_labels is not None):
+                        extra["holdout_samples"] = held
+                        if labelled:
+                            extra["holdout_labels"] = holdout_labels
+                    view.metrics.append(make(**extra, original_samples=bound_to))
         self.include_baselines = include_baselines
         self.metric_spectral = None
         self._spectral_view = None
@@ -133,11 +151,11 @@ class MetricCollection:
     def metrics_freq(self) -> list:
         return self._views[1].metrics
 
-    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+    def __call__(self, other_samples: np.ndarray | torch.Tensor, other_labels=None) -> dict[str, Any]:
         samples = _as_tensor(other_samples)
         merged: dict[str, Any] = {}
         for view in self._views:
-            merged.update(view.evaluate(samples))
+            merged.update(view.evaluate(samples, other_labels))
         if self.include_baselines:
             merged.update(self.baseline_metrics)
         if self._spectral_view is not None:
@@ -726,3 +744,98 @@ class PredictiveScore(_PosthocScore):
     @property
     def name(self) -> str:
         return "predictive_score"
+
+
+def _label_array(labels, n: int, what: str) -> np.ndarray:
+    y = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    if y.dtype == np.bool_ or not np.issubdtype(y.dtype, np.integer):
+        raise ValueError(f"{what} must be integer classes, got dtype {y.dtype}")
+    if y.ndim != 1 or y.shape[0] != n:
+        raise ValueError(f"{what} of shape {tuple(y.shape)} for {n} samples: one class per sample")
+    if n and y.min() < 0:
+        raise ValueError(f"{what} must not be negative")
+    return y.astype(np.int64)
+
+
+class ClassificationScore(_PosthocScore):
+    """Do the samples of a class look like that class (TSTR / TRTS: RCGAN, Esteban et al. 2017; the classification accuracy score of
+    Ravuri & Vinyals 2019)?  A small causal LSTM with a K-way softmax head is trained on the engine after the fact:
+      tstr_accuracy, tstr_balanced_accuracy   trained on the SAMPLES with the classes they were drawn for, tested on the original
+                                              samples: drops when the samples of a class do not look like it, or cover it badly
+      ..._holdout                             (with `holdout_samples` and `holdout_labels`) the same training, tested on real series
+                                              the model was not trained on
+      trts_accuracy, trts_balanced_accuracy   trained on the original samples (once per metric object), tested on the samples:
+                                              label fidelity, also under guidance
+      trtr_accuracy_self, trtr_balanced_accuracy_self   (baseline) trained on one real fold, tested on the other
+    Balanced accuracy is the mean recall over the classes present in the test set.  `n_classes` defaults to the largest original
+    label + 1; `balance=True` draws the training batches class by class.  A call takes the samples AND their classes
+    (`needs_labels`); deterministic given `random_seed`.  Needs (n, T, C) original samples; bound in the time view only."""
+    needs_labels = True
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, original_labels=None,
+                 holdout_samples: Optional[np.ndarray | torch.Tensor] = None, holdout_labels=None, n_classes: Optional[int] = None,
+                 balance: bool = False, steps: int = 2000, batch_size: int = 128, lr: float = 1e-3, d_model: int = 32,
+                 num_layers: int = 1, max_samples: int = 10_000, random_seed: int = 0) -> None:
+        # everything about the labels is checked before the samples move to the device
+        if original_labels is None:
+            raise ValueError("ClassificationScore needs original_labels, the class of every original sample (an unlabelled dataset "
+                             "has no classification score)")
+        labels = _label_array(original_labels, len(original_samples), "original_labels")
+        if n_classes is None:
+            n_classes = int(labels.max()) + 1
+        if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 2 <= n_classes <= POSTHOC_MAX_CLASSES:
+            raise ValueError(f"n_classes={n_classes} must be an integer from 2 to {POSTHOC_MAX_CLASSES} (by default the largest "
+                             "original label + 1)")
+        n_classes = int(n_classes)
+        if labels.max() >= n_classes:
+            raise ValueError(f"original_labels must lie in [0, {n_classes})")
+        held_labels = None
+        if holdout_samples is not None:
+            if holdout_labels is None:
+                raise ValueError("ClassificationScore got holdout_samples without holdout_labels")
+            held_labels = _label_array(holdout_labels, len(holdout_samples), "holdout_labels")
+            if held_labels.max() >= n_classes:
+                raise ValueError(f"holdout_labels must lie in [0, {n_classes})")
+        super().__init__(original_samples=original_samples, holdout_samples=holdout_samples, steps=steps, batch_size=batch_size, lr=lr,
+                         d_model=d_model, num_layers=num_layers, max_samples=max_samples, random_seed=random_seed)
+        self.original_labels, self.holdout_labels, self.n_classes = labels, held_labels, n_classes
+        self.knobs["balance"] = bool(balance)
+        self._real_classifier = None
+
+    def _fit(self, train_set: torch.Tensor, train_labels: np.ndarray):
+        return fit_classifier(train_set, train_labels, n_classes=self.n_classes, stats_from=self._series(self.original_samples),
+                              seed=self.random_seed, **self.knobs)
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor, other_labels=None) -> dict[str, Any]:
+        if other_labels is None:
+            raise ValueError("ClassificationScore needs other_labels, the classes the samples were drawn for: sample a "
+                             "class-conditional model with sampler.labels set (a class, `balanced` or `data`) and pass the labels on")
+        samples = self._series(check_flat_array(other_samples))
+        labels = _label_array(other_labels, samples.shape[0], "other_labels")
+        if labels.max() >= self.n_classes:
+            raise ValueError(f"other_labels must lie in [0, {self.n_classes})")
+        real = self._series(self.original_samples)
+        on_samples = self._fit(samples, labels)
+        res = on_samples.score(real, self.original_labels)
+        out = {"tstr_accuracy": res["accuracy"], "tstr_balanced_accuracy": res["balanced_accuracy"]}
+        if self.holdout_samples is not None:
+            res = on_samples.score(self._series(self.holdout_samples), self.holdout_labels)
+            out.update(tstr_accuracy_holdout=res["accuracy"], tstr_balanced_accuracy_holdout=res["balanced_accuracy"])
+        if self._real_classifier is None:
+            self._real_classifier = self._fit(real, self.original_labels)
+        res = self._real_classifier.score(samples, labels)
+        out.update(trts_accuracy=res["accuracy"], trts_balanced_accuracy=res["balanced_accuracy"])
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        if self._baseline is None:
+            fold_a, fold_b = self._folds()
+            half = fold_a.shape[0]
+            res = self._fit(fold_a, self.original_labels[:half]).score(fold_b, self.original_labels[half:])
+            self._baseline = {"trtr_accuracy_self": res["accuracy"], "trtr_balanced_accuracy_self": res["balanced_accuracy"]}
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "classification_score"

@@ -955,6 +955,52 @@ int fd_posthoc_fit(fd_score* m, int task, float* params, float* grads, float* ex
                    int first_step, int steps, int B, float lr, float max_norm, float* loss_trace /* (steps) */,
                    int* idx_trace /* (steps, B) or NULL */, void* work, size_t work_bytes, void* stream);
 
+/* Label-aware post-hoc scores (NOT in the reference; TSTR / TRTS of RCGAN, Esteban et al. 2017, and the classification accuracy
+ * score of Ravuri & Vinyals 2019; DESIGN.md 3.32, utils/posthoc.py): the K-way task on the same causal LSTM.  The backbone maps
+ * (B, T, Cn) to (B, T, Cn), so the network has Cn = max(C, K) channels: the series fill the input channels < C, the others are fed
+ * +0.0, and the K logits of series b are out[b, T - 1, 0 .. K - 1], where the LSTM has seen the whole series.  mean and inv_std stay
+ * fp32[C].  Same house rules as above: fp32 / fp64, no atomics, fixed-order double sums, bit-identical runs.
+ *
+ * fd_posthoc_batch_labelled   one minibatch from ONE labelled pool a (na, T, C), ya (na) int32 in [0, K) (the caller's contract).
+ *                    Row j of step s takes the Philox word of fd_posthoc_batch (word j % 4 of counter offset + s * ceil(B / 4) + j / 4
+ *                    under the key seed).  Uniform (order and class_start NULL): idx = (uint64(word) * na) >> 32.  Balanced (both
+ *                    non-null): order (na) lists the rows sorted stably by class, class_start (K + 1) the offsets into it; with P
+ *                    the number of classes that hold a row and c the ((uint64)s * B + j) % P-th of them in ascending order,
+ *                    idx = order[class_start[c] + ((uint64(word) * count[c]) >> 32)].  x (B, T, Cn): channels < C are
+ *                    (a[idx] - mean) * inv_std (one subtraction, one product, each rounded once), channels >= C are +0.0;
+ *                    label[j] = ya[idx]; idx (B).  Indices read from a broken table are clamped into the pool.
+ * fd_posthoc_head_multiclass   softmax cross-entropy on out (B, T, Cn), one workgroup per series; every output is optional.
+ *                    logp (B, K) doubles: logit - max - log(sum exp(logit - max)), in double; pred (B) int32: the argmax, ties to
+ *                    the lowest class; nll (B) doubles: -logp[b, label_b] (NaN for a label outside [0, K)); loss: float
+ *                    mean_b nll[b], added in the fixed order of fd_posthoc_head's loss (needs nll); dout (B, T, Cn):
+ *                    (softmax - onehot) / B at [b, T - 1, k < K], +0.0 everywhere else.  label may be NULL when loss, dout and nll
+ *                    are.  T = 1 is allowed.
+ * fd_posthoc_fit_multiclass    the loop of fd_posthoc_fit with those two stages: fd_posthoc_batch_labelled (step s) ->
+ *                    fd_score_forward_train (t = 0, dropout 0) -> fd_posthoc_head_multiclass -> fd_score_backward ->
+ *                    [fd_grad_sqnorm] -> fd_adamw_step, same optimiser constants, time_encoder.W skipped, no host
+ *                    synchronisation; the same calls made one by one give the same bits.  The model is an LSTM of Cn = max(C, K)
+ *                    channels; C is the pool's.  work: at least fd_posthoc_fit_multiclass_workspace_bytes(B, T, Cn).
+ * fd_posthoc_confusion   counts (K, K) int32, counts[r, c] = #{i < n : label[i] == r, pred[i] == c}: rows are the true class.
+ *                    Every entry is written; pairs outside [0, K) are counted nowhere.
+ * FD_ERR_ARG (nothing is launched): K < 2 or K > FD_POSTHOC_MAX_CLASSES (one logit per thread of a workgroup), Cn != max(C, K)
+ * (head: Cn < K), an empty pool (na < 1), order without class_start or the reverse, loss, dout or nll without label, loss without
+ * nll, every head output NULL, n < 1, and what fd_posthoc_fit refuses.  FD_ERR_UNSUPPORTED: a model that is not the LSTM. */
+#define FD_POSTHOC_MAX_CLASSES 256
+int fd_posthoc_batch_labelled(fd_ctx* ctx, const float* a, int na, const int* ya, const int* order /* (na) or NULL */,
+                              const int* class_start /* (K + 1) or NULL */, int K, const float* mean, const float* inv_std,
+                              uint64_t seed, uint64_t offset, int step, int B, int T, int C, int Cn, float* x /* (B, T, Cn) */,
+                              int* label /* (B) */, int* idx /* (B) */, void* stream);
+int fd_posthoc_head_multiclass(fd_ctx* ctx, const float* out, const int* label /* (B) or NULL */, int B, int T, int Cn, int K,
+                               double* logp /* (B, K) or NULL */, int* pred /* (B) or NULL */, float* loss /* (1) or NULL */,
+                               float* dout /* (B, T, Cn) or NULL */, double* nll /* (B) or NULL */, void* stream);
+int fd_posthoc_fit_multiclass_workspace_bytes(fd_ctx* ctx, int B, int T, int Cn, size_t* bytes);
+int fd_posthoc_fit_multiclass(fd_score* m, int K, float* params, float* grads, float* exp_avg, float* exp_avg_sq, const float* a,
+                              int na, const int* ya, const int* order /* or NULL */, const int* class_start /* or NULL */, int C,
+                              const float* mean, const float* inv_std, uint64_t seed, uint64_t offset, int first_step, int steps,
+                              int B, float lr, float max_norm, float* loss_trace /* (steps) */,
+                              int* idx_trace /* (steps, B) or NULL */, void* work, size_t work_bytes, void* stream);
+int fd_posthoc_confusion(fd_ctx* ctx, const int* label, const int* pred, int n, int K, int* counts /* (K, K) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
