@@ -16,6 +16,11 @@ between two runs, r * num_diffusion_steps score evaluations; both are recorded w
 WINDOW MEANS instead (temporal super-resolution): mask.* is read in windows of w time steps (mask.horizon counts windows), the
 observation is the window means of the test split, every full-resolution entry counts as hidden in the scores, and results.yaml records
 `aggregate` and `max_abs_err_window_means`, the largest deviation of the result's window means over the observed windows.
+operator.kind=lowpass|moving_average|difference|gaussian_blur (with operator.n_freq / w / stride / sigma; sampling/masks.py) conditions
+on a GENERAL LINEAR observation y = P x instead: mask.* counts rows of P (under conditioning=replace a random mask needs orthogonal rows:
+lowpass), the observation is P applied to the test split, every full-resolution entry counts as hidden in the scores, and
+results.yaml records `operator` (kind, its parameters, M and cond(P)) and `max_abs_err_operator`, the largest deviation of P applied
+to the result from the observation over the observed rows.  Not with aggregate > 1, labels / cfg_scale, resample or conditioning=smc.
 multivariate_scores=true (K > 1) adds the scores that see the joint draw (energy score, variogram score with the `variogram` block's
 order / max_lag / weights, rank histogram and its reliability index), on channels divided by their standard deviation.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
@@ -34,7 +39,7 @@ from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
 from fourierdiffusion_amd.sampling.forecast import ensemble_scores, multivariate_scores  # noqa: E402
-from fourierdiffusion_amd.sampling.masks import observation_mask, window_means  # noqa: E402
+from fourierdiffusion_amd.sampling.masks import LinearOperator, apply_operator, observation_mask, operator_from_config, window_means  # noqa: E402
 from fourierdiffusion_amd.sampling.sampler import series_labels  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
@@ -122,6 +127,7 @@ class ImputationRunner:
         self.resample = int(cfg.get("resample", 1))
         self.jump_length = int(cfg.get("jump_length", 1))
         self.aggregate = int(cfg.get("aggregate", 1))
+        self.operator_cfg = {k: v for k, v in dict(cfg.get("operator", None) or {}).items()}
         self.multivariate: bool = bool(cfg.get("multivariate_scores", False))
         self.variogram = dict(cfg.get("variogram", None) or {})
         if self.multivariate and self.num_samples < 2:
@@ -146,10 +152,21 @@ class ImputationRunner:
         if not 1 <= w <= int(truth.shape[1]):
             raise ValueError(f"aggregate must lie in [1, {int(truth.shape[1])}], got {w}")
         coarse = truth if w == 1 else window_means(truth, w)                        # (n, J, C): what is observed, and its mask
+        ocfg = self.operator_cfg
+        Pm = operator_from_config(ocfg.get("kind", None), int(truth.shape[1]), **{k: ocfg[k] for k in ("n_freq", "w", "stride", "sigma")
+                                                                                   if ocfg.get(k, None) is not None})
+        op = None
+        if Pm is not None:
+            if w > 1:
+                raise ValueError("operator.kind and aggregate > 1 do not go together")
+            op = LinearOperator(Pm, max_condition=float(ocfg.get("max_condition", 1e4)))
+            coarse = apply_operator(truth, op).float()                              # (n, M, C)
         mask = observation_mask(self.mask_cfg.kind, tuple(coarse.shape), p=float(self.mask_cfg.get("p", 0.5)),
                                 horizon=int(self.mask_cfg.get("horizon", 1)), generator=gen)
         observed = coarse.masked_fill(~mask, float("nan"))                         # the sampler never sees a hidden entry
         agg = {} if w == 1 else dict(aggregate=w)
+        if op is not None:
+            agg = dict(operator=op)
         lo, hi = shard_range(int(truth.shape[0]), self.dist.rank, self.dist.world)  # independent rows: no exchange
         y = series_labels(self.labels, self.datamodule, int(truth.shape[0]), int(getattr(self.score_model, "n_classes", 0)))
         guided = {} if (y is None and self.cfg_scale == 1.0) else dict(y=None if y is None else y[lo:hi], cfg_scale=self.cfg_scale)
@@ -193,7 +210,7 @@ class ImputationRunner:
             results = yaml.safe_load(open(results_path)) if results_path.exists() else None
             results = results if isinstance(results, dict) else {}
             # window means: no full-resolution entry was observed, so the scores run over all of them
-            fine = mask if w == 1 else torch.zeros(truth.shape, dtype=torch.bool)
+            fine = mask if (w == 1 and op is None) else torch.zeros(truth.shape, dtype=torch.bool)
             scores = hidden_errors(X, truth, fine) if K == 1 else ensemble_results(X, truth, fine)
             results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **scores}
             if self.multivariate and (~fine).any():
@@ -203,6 +220,12 @@ class ImputationRunner:
                 if mask.any():
                     dev = (window_means(X.double(), w) - (coarse.double() if K == 1 else coarse.double()[:, None])).abs()
                     results["impute"]["max_abs_err_window_means"] = float(dev[(mask if K == 1 else mask[:, None]).expand_as(dev)].max())
+            if op is not None:
+                results["impute"]["operator"] = {"kind": str(ocfg["kind"]), "M": op.M, "condition": float(op.condition),
+                                                 **{k: ocfg[k] for k in ("n_freq", "w", "stride", "sigma") if ocfg.get(k, None) is not None}}
+                if mask.any():
+                    dev = (apply_operator(X.double(), op) - (coarse.double() if K == 1 else coarse.double()[:, None])).abs()
+                    results["impute"]["max_abs_err_operator"] = float(dev[(mask if K == 1 else mask[:, None]).expand_as(dev)].max())
             if self.conditioning == "smc":
                 st = smc_stats.mean(0)
                 results["impute"].update(conditioning="smc", guidance_jacobian=self.guidance_jacobian,

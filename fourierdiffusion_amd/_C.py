@@ -142,6 +142,17 @@ _PROTOS = {
     "fd_sampler_run_impute_dps_agg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                                 _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, _vp]),
+    "fd_linop_create": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(_vp)]),
+    "fd_linop_destroy": (C.c_int, [_vp]),
+    "fd_impute_project_op": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_float, C.c_float, _vp, C.c_uint64,
+                                       C.c_uint64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "fd_sampler_run_impute_op": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                           _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "fd_impute_guidance_op": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int,
+                                        _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "fd_sampler_run_impute_dps_op": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
+                                               _vp, C.c_int, C.c_float, C.c_int, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int,
+                                               _vp, C.c_int, _vp]),
     "fd_sampler_run_impute_smc": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, C.c_int,
                                             _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp,
                                             C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),

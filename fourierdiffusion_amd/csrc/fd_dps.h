@@ -52,6 +52,6 @@ int fd_dps_prepare(fd_score* m, fd_dps_res& r, const float* G, const float* x, c
 // Jacobian, else the sampler's forward), the residual of the B state rows, and the VJP; leaves score, u, dx and the block sums in
 // the buffers
 int fd_dps_eval(fd_score* m, fd_dps_res& r, const fd_dps_bufs& bf, const float* x, int B, int R, const fd_guide* g, bool jac,
-                bool fourier, int mode, hipStream_t s, const fd_agg_plan* ag = nullptr);
+                bool fourier, int mode, hipStream_t s, const fd_agg_plan* ag = nullptr, const fdproj::DenseOp* dn = nullptr);
 // the residual of the B state rows alone, from the x and score r points at (no network evaluation)
 int fd_dps_residual(fd_ctx* ctx, const fd_dps_res& r, int B, bool fourier, hipStream_t s);

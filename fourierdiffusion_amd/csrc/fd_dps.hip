@@ -17,7 +17,9 @@
 // product, block sum and launch of fd_project.h, which k_impute shares.  Phase 1: sigma (x0_obs - x0_hat) / rho into the k-quad LDS
 // image U; phase 2: V = F^T U (v_mfma_f32_16x16x4_f32), masked into W = r, and the block's sum r^2 in double; phase 3: Y = F W,
 // u = sigma Y / rho, dout = s^2 G^2 u.  The block's sum goes to part[b][block] (no atomics).  Op = WindowOp: the residual of window
-// means (fd_aggregate.hip), r over windows, W = r / l, the bases A_w / B_w.  k_dps_step: elementwise over k_sde_step's Philox groups; a row's ||r||^2 is the sum of its blocks in order, so
+// means (fd_aggregate.hip), r over windows, W = r / l, the bases A_w / B_w.  Op = DenseOp: the residual of a dense operator's rows
+// (fd_linop.hip), both domains on the two products, phase 3 on the operator's adjoint basis F P^T (P^T in the time domain, rho = 1).
+// k_dps_step: elementwise over k_sde_step's Philox groups; a row's ||r||^2 is the sum of its blocks in order, so
 // runs are bit-identical.  Every stage buffer lives in ctx->ll_buf, outside the arena that holds the training forward's saved
 // activations.
 //
@@ -35,6 +37,7 @@
 #include "fd_common.h"
 #include "fd_dps.h"
 #include "fd_engine.h"
+#include "fd_linop.h"
 #include "fd_loop.h"
 #include "fd_philox.h"
 #include "fd_project.h"
@@ -73,10 +76,13 @@ __device__ __forceinline__ void res_dout(const Args& a, size_t e, float v) {
     }
 }
 
-// Op (fd_project.h): the coordinate mask, or window means (fd_aggregate.hip), which go with no PAIR
+// Op (fd_project.h): the coordinate mask, or window means (fd_aggregate.hip) or a dense operator (fd_linop.hip), which go with no PAIR
 template <bool FOURIER, bool PAIR, class Op>
 __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PAIR>::type a, Op op) {
     static_assert(!(Op::kWindow && PAIR), "window means go with no guide");
+    static_assert(!(Op::kDense && PAIR), "a dense operator goes with no guide");
+    constexpr bool PRODUCTS = FOURIER || Op::kDense;    // the two MFMA products: a dense operator in the time domain is the Fourier
+                                                        // branch with rho = 1 on the time-domain bases
     extern __shared__ float lds[];
     const int tid = threadIdx.x;
     const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
@@ -85,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
     const uint8_t* mrow = a.mask + (a.mask_per_series ? (size_t)(b / a.obs_rep) * M * C : 0);
     double rr = 0.0;
 
-    if constexpr (!FOURIER && !Op::kWindow) {
+    if constexpr (!FOURIER && !Op::kWindow && !Op::kDense) {
         // ---- the mask in the time domain selects elementwise: no LDS image
         for (int i = tid; i < T * kCB; i += kThreads) {
             const int t = i / kCB, c = c0 + i % kCB;
@@ -101,9 +107,9 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
             if (a.dout) res_dout<PAIR>(a, e, sg2 * uv);
         }
     } else {
-        float* U = lds;                            // FOURIER: sigma (x0_obs - x0_hat) / rho, frequency rows (k-quad); else time rows [t][channel]
-        float* W = lds + (size_t)Tp * kCB;         // FOURIER: the adjoint's input (r, or r / l), the operator's rows (k-quad)
-        if (FOURIER) {
+        float* U = lds;                            // PRODUCTS: sigma (x0_obs - x0_hat) / rho, packed rows (k-quad); else time rows [t][channel]
+        float* W = lds + (size_t)Tp * kCB;         // PRODUCTS: the adjoint's input (r, or r / l), the operator's rows (k-quad)
+        if (PRODUCTS) {
             for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
             __syncthreads();
         }
@@ -117,11 +123,12 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
             const float x0h = (a.x[e] + a.s2 * (Gk * Gk) * res_score<PAIR>(a, e)) / a.alpha;
             const float dv = sd * (a.x0[obase + kc] - x0h);
             if (FOURIER) U[quad_idx(k, cl)] = dv * inv_r(k, T);
+            else if (Op::kDense) U[quad_idx(k, cl)] = dv;
             else U[i] = dv;
         }
         __syncthreads();
 
-        if constexpr (!FOURIER) {
+        if constexpr (!PRODUCTS) {
             // ---- window means in the time domain: one thread per (window, channel), r = the masked mean in ascending t;
             // u = sigma r / l over the window
             for (int i = tid; i < M * kCB; i += kThreads) {
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
             const int li = lane & 15, kq = lane >> 4;
             const int c = c0 + li;
             const float* Ao = op.to_obs(a.basis, Tp);
-            const float* Bo = op.from_obs(a.basis, Tp);
+            const float* Bo = op.adjoint_basis(a.basis, Tp);
             // ---- phase 2: r = m . (Ao U) (row i of the tile = observation row j0 + i: a time step or a window), its squares in
             // double; W = the adjoint's input
             for (int tile = wave; tile < Mp / 16; tile += nw) {
@@ -182,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void k_dps_residual(typename ResArgsOf<PA
                     if (k >= T) continue;
                     const size_t kc = (size_t)k * C + c, e = base + kc;
                     const float sd = a.stdv ? a.stdv[kc] : 1.0f;
-                    const float uv = sd * inv_r(k, T) * acc[v];
+                    const float uv = FOURIER ? sd * inv_r(k, T) * acc[v] : sd * acc[v];
                     a.u[e] = uv;
                     if (a.dout) {
                         const float Gk = a.G[k];
@@ -331,7 +338,7 @@ int launch_step(fd_ctx* ctx, const StepArgs& a, const fd_guide* g, hipStream_t s
 // Jacobian, else the sampler's forward), the residual of the B state rows, and the VJP; leaves score, u, dx and the block sums in
 // the buffers
 int fd_dps_eval(fd_score* m, fd_dps_res& r, const fd_dps_bufs& bf, const float* x, int B, int R, const fd_guide* g, bool jac,
-                bool fourier, int mode, hipStream_t s, const fd_agg_plan* ag) {
+                bool fourier, int mode, hipStream_t s, const fd_agg_plan* ag, const fdproj::DenseOp* dn) {
     fd_ctx* ctx = m->ctx;
     if (jac) {
         if (int rc = fd_score_forward_train(m, x, bf.tvec, bf.score, R, 0.f, 0, 0, s)) return rc;
@@ -343,6 +350,9 @@ int fd_dps_eval(fd_score* m, fd_dps_res& r, const fd_dps_bufs& bf, const float* 
     if (ag) {        // window means (fd_aggregate.h): r.mask is (B/obs_rep,J,C) or (J,C)
         r.basis = ag->basis;
         if (int rc = fourier ? launch_residual<true, false>(ctx, r, B, s, ag->op) : launch_residual<false, false>(ctx, r, B, s, ag->op))
+            return rc;
+    } else if (dn) {        // a dense operator (fd_linop.h): r.mask is (B/obs_rep,M,C) or (M,C)
+        if (int rc = fourier ? launch_residual<true, false>(ctx, r, B, s, *dn) : launch_residual<false, false>(ctx, r, B, s, *dn))
             return rc;
     } else if (g) {
         ResArgsPair rp{};
@@ -370,7 +380,7 @@ namespace {
 int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
                  const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian, float* g_out,
                  double* rnorm2_out, int B, int obs_replicas, int mode, hipStream_t s, const fd_guide* g, const char* who,
-                 int window = 1) {
+                 int window = 1, fd_linop* lop = nullptr) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, g_out && rnorm2_out, "%s: null pointer", who);
     FD_REQUIRE(ctx, std::isfinite(t) && t > 0.f, "%s: t=%g must be finite and > 0", who, (double)t);
@@ -380,6 +390,11 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
     if (window > 1) {
         FD_REQUIRE(ctx, !g, "%s: window=%d goes with no guide", who, window);
         if (int rc = fd_agg_prepare(ctx, r.T, r.Tp, window, fourier, s, &agg, who)) return rc;
+    }
+    DenseOp dop{};
+    if (lop) {
+        FD_REQUIRE(ctx, !g && window == 1, "%s: an operator goes with no guide and no window", who);
+        if (int rc = fd_linop_prepare(ctx, lop, r.T, fourier, s, &dop, who)) return rc;
     }
     const bool jac = jacobian != 0, pair = g && g->pair;
     const size_t n = (size_t)B * r.T * r.C;
@@ -400,7 +415,9 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
     fd_train_mode_scope tm(m, jac ? fd_diff_train_mode(m, mode) : m->train_mode);
     fd_label_dropout_scope ld(m, 0.f);
     fd_fill(bf.tvec, R, t, s);
-    if (int rc = fd_dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
+    if (int rc = fd_dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr,
+                             lop ? &dop : nullptr))
+        return rc;
     StepArgs a{};
     a.G = G; a.u = bf.u; a.dx = bf.dx; a.part = bf.part; a.gout = g_out; a.rn2_out = rnorm2_out;
     a.n = n; a.TC = (size_t)r.T * r.C; a.T = r.T; a.C = r.C; a.ncb = r.ncb;
@@ -412,7 +429,7 @@ int dps_guidance(fd_score* m, const fd_sde_params* sde, const float* G, float t,
 int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
              const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
              float guidance_scale, int jacobian, const float* z_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
-             hipStream_t s, const fd_guide* g, const char* who, int window = 1) {
+             hipStream_t s, const fd_guide* g, const char* who, int window = 1, fd_linop* lop = nullptr) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, timesteps, "%s: null pointer", who);
     FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
@@ -425,6 +442,11 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
     if (window > 1) {
         FD_REQUIRE(ctx, !g, "%s: window=%d goes with no guide", who, window);
         if (int rc = fd_agg_prepare(ctx, r.T, r.Tp, window, fourier, s, &agg, who)) return rc;
+    }
+    DenseOp dop{};
+    if (lop) {
+        FD_REQUIRE(ctx, !g && window == 1, "%s: an operator goes with no guide and no window", who);
+        if (int rc = fd_linop_prepare(ctx, lop, r.T, fourier, s, &dop, who)) return rc;
     }
     const bool jac = jacobian != 0, pair = g && g->pair;
     const size_t n = (size_t)B * r.T * r.C;
@@ -457,7 +479,9 @@ int dps_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float*
         fd_fill(bf.tvec, R, timesteps[i], s);
         r.alpha = al[i];
         r.s2 = s2[i];
-        if (int rc = fd_dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr)) return rc;
+        if (int rc = fd_dps_eval(m, r, bf, x, B, R, pair ? g : nullptr, jac, fourier != 0, mode, s, window > 1 ? &agg : nullptr,
+                             lop ? &dop : nullptr))
+            return rc;
         a.zin = z_steps ? z_steps + (size_t)i * n : nullptr;
         a.cf = cf[i];
         a.alpha = al[i];
@@ -506,6 +530,29 @@ extern "C" int fd_sampler_run_impute_dps_agg(fd_score* m, const fd_sde_params* s
                                          guidance_scale, jacobian, z_steps, seed, offset, B, obs_replicas, mode, stream);
     return dps_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, guidance_scale, jacobian,
                     z_steps, seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_dps_agg", window);
+}
+
+// fd_impute_guidance and fd_sampler_run_impute_dps on a dense operator: mask_u8 (B/obs_replicas,M,C) or (M,C) over the M rows of
+// `op`, the residual r (M,C) per row
+extern "C" int fd_impute_guidance_op(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x,
+                                     const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std,
+                                     int fourier, int jacobian, float* g_out, double* rnorm2_out, int B, int obs_replicas, fd_linop* op,
+                                     int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_impute_guidance_op")) return rc;
+    FD_REQUIRE(m->ctx, op, "fd_impute_guidance_op: null operator handle");
+    return dps_guidance(m, sde, G, t, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, jacobian, g_out, rnorm2_out, B,
+                        obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_impute_guidance_op", 1, op);
+}
+
+extern "C" int fd_sampler_run_impute_dps_op(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                            int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                            int mask_per_series, const float* feat_std, int fourier, float guidance_scale,
+                                            int jacobian, const float* z_steps, uint64_t seed, uint64_t offset, int B,
+                                            int obs_replicas, fd_linop* op, int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_dps_op")) return rc;
+    FD_REQUIRE(m->ctx, op, "fd_sampler_run_impute_dps_op: null operator handle");
+    return dps_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, guidance_scale, jacobian,
+                    z_steps, seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_dps_op", 1, op);
 }
 
 // fd_impute_guidance on a class-conditional model under classifier-free guidance: y (B) one label per row or null, w the scale;

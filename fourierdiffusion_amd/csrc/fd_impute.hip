@@ -23,7 +23,8 @@
 //
 // The mask enters in one place, between the two products, so k_impute is a template on the observation operator (fd_project.h):
 // MaskOp is the above; WindowOp conditions on window means (fd_aggregate.hip: the middle image holds windows, the bases are
-// A_w / B_w) and adds the one body that differs, the time-domain window sum.
+// A_w / B_w) and adds the one body that differs, the time-domain window sum; DenseOp conditions on a matrix the caller supplies
+// (fd_linop.hip: the middle image holds its rows, the bases are the operator's own) and runs the two products in both domains.
 //
 // RePaint resampling (Lugmayr et al. 2022; fd_sampler_run_impute_repaint): the steps are cut into blocks of jump_length, each block
 // runs `resample` times, and between two runs the state is diffused forward from the block's last level to its first by the
@@ -37,6 +38,7 @@
 #include "fd_aggregate.h"
 #include "fd_common.h"
 #include "fd_engine.h"
+#include "fd_linop.h"
 #include "fd_loop.h"
 #include "fd_project.h"
 #include "fd_sde.h"
@@ -54,7 +56,8 @@ struct ImpArgs {
     const float* stdv;       // (T,C) feature std of the packed spectrum or nullptr (= 1)
     const float* G;          // (T)
     const float* zobs;       // (B,T,C) injected observation noise or nullptr (Philox at off_obs)
-    const float* basis;      // the operator's pair: F then F^T (Tp x Tp each), or A_w (Jp x Tp) then B_w (Tp x Jp)
+    const float* basis;      // the operator's pair: F then F^T (Tp x Tp each), or A_w (Jp x Tp) then B_w (Tp x Jp); the dense
+                             // operator carries its own
     float* out;
     int B, T, C, Tp, ncb, mask_per_series, obs_rep;
     SdeCoef cf;
@@ -74,7 +77,8 @@ struct ImpArgsOf { typedef ImpArgs type; };
 template <>
 struct ImpArgsOf<true> { typedef ImpArgsPair type; };
 
-// Op (fd_project.h): the coordinate mask, or window means (fd_aggregate.hip), which go with neither PAIR nor RENOISE.
+// Op (fd_project.h): the coordinate mask, or window means (fd_aggregate.hip) or a dense operator (fd_linop.hip), which go with
+// neither PAIR nor RENOISE.
 // PAIR: the workgroup of (b, channel block) reads x[b], steps with the guided score fd_guided(score[b], score[B + b]) and writes
 // every final value to rows b and B + b, so the two halves stay bit-equal; the Philox counters and lanes are those of the unpaired
 // launch over n = B T C (the second half draws nothing).
@@ -82,10 +86,13 @@ struct ImpArgsOf<true> { typedef ImpArgsPair type; };
 template <bool STEP, bool FOURIER, bool PAIR, bool RENOISE, class Op>
 __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::type a, Op op) {
     static_assert(!(Op::kWindow && (PAIR || RENOISE)), "window means go with neither a guide nor RePaint");
-    constexpr bool IMAGE = FOURIER || Op::kWindow;      // the mask in the time domain selects elementwise: no LDS
+    static_assert(!(Op::kDense && (PAIR || RENOISE)), "a dense operator goes with neither a guide nor RePaint");
+    constexpr bool IMAGE = FOURIER || Op::kWindow || Op::kDense;      // the mask in the time domain selects elementwise: no LDS
+    constexpr bool PRODUCTS = FOURIER || Op::kDense;    // the two MFMA products: a dense operator in the time domain is the Fourier
+                                                        // branch with rho = 1 on the time-domain bases
     extern __shared__ float lds[];
-    float* U = lds;                            // FOURIER: sigma d / r, frequency rows (k-quad); else sigma d, time rows [t][channel]
-    float* W = lds + (size_t)a.Tp * kCB;       // FOURIER: m . (the observed rows of idft(sigma d)), the operator's rows (k-quad)
+    float* U = lds;                            // PRODUCTS: sigma d / r, packed rows (k-quad); else sigma d, time rows [t][channel]
+    float* W = lds + (size_t)a.Tp * kCB;       // PRODUCTS: m . (the observed rows of idft(sigma d)), the operator's rows (k-quad)
     const int tid = threadIdx.x;
     const int b = blockIdx.x / a.ncb, c0 = (blockIdx.x % a.ncb) * kCB;
     const int T = a.T, C = a.C, Tp = a.Tp, M = op.rows(T), Mp = op.rows_padded(Tp);
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::t
     const uint8_t* mrow = a.mask + (a.mask_per_series ? (size_t)(b / a.obs_rep) * M * C : 0);
     [[maybe_unused]] const size_t half = (size_t)a.B * TC;      // PAIR: the null half of x / score / out starts here
 
-    if (FOURIER) {
+    if (PRODUCTS) {
         for (int i = tid; i < Tp * kCB; i += kThreads) U[i] = 0.f;
         __syncthreads();
     }
@@ -139,6 +146,7 @@ __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::t
                 a.out[e] = xt;
                 const float sd = a.stdv ? a.stdv[(size_t)t * C + c] : 1.0f;
                 if (FOURIER) U[quad_idx(t, c - c0)] = sd * dv * inv_r(t, T);
+                else if (Op::kDense) U[quad_idx(t, c - c0)] = sd * dv;
                 else U[t * kCB + (c - c0)] = sd * dv;
             }
         }
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void k_impute(typename ImpArgsOf<PAIR>::t
             }
         }
     }
-    if constexpr (FOURIER) {
+    if constexpr (FOURIER || Op::kDense) {
         const int lane = tid & 63, wave = tid >> 6, nw = kThreads / 64;
         const int li = lane & 15, kq = lane >> 4;
         const int c = c0 + li;
@@ -224,7 +232,7 @@ __global__ __launch_bounds__(256) void k_impute_basis(float* __restrict__ Fm, fl
 
 template <bool STEP, bool FOURIER, bool PAIR = false, bool RENOISE = false, class Op = MaskOp>
 int launch_variant(fd_ctx* ctx, const typename ImpArgsOf<PAIR>::type& a, hipStream_t s, Op op = Op()) {
-    return launch_kernel<k_impute<STEP, FOURIER, PAIR, RENOISE, Op>, (Op::kWindow ? 128 : 160) * 1024>(
+    return launch_kernel<k_impute<STEP, FOURIER, PAIR, RENOISE, Op>, (Op::kWindow || Op::kDense ? 128 : 160) * 1024>(
         ctx, (unsigned)(a.B * a.ncb), image_bytes(op, a.T, a.Tp, FOURIER), s, a, op);
 }
 
@@ -253,7 +261,7 @@ int prepare(fd_ctx* ctx, ImpArgs& a, const float* x0, const uint8_t* mask, int m
 // renoise (the mask alone): the RENOISE variants (a.ra, a.rb, a.zre, a.off_re set): the loop's fused step, or the step-wise projection
 template <class Op = MaskOp>
 int launch(fd_ctx* ctx, const ImpArgs& a, bool step, bool fourier, hipStream_t s, bool renoise = false, Op op = Op()) {
-    if constexpr (!Op::kWindow)
+    if constexpr (!Op::kWindow && !Op::kDense)
         if (renoise) {
             if (step) return fourier ? launch_variant<true, true, false, true>(ctx, a, s) : launch_variant<true, false, false, true>(ctx, a, s);
             return fourier ? launch_variant<false, true, false, true>(ctx, a, s) : launch_variant<false, false, false, true>(ctx, a, s);
@@ -281,6 +289,13 @@ int prepare_window(fd_ctx* ctx, ImpArgs& a, int window, const float* stdv, int f
     return FD_OK;
 }
 
+// a dense operator: its bases in the call's domain and, in `a`, the feature std, which both domains read (fd_linop.h)
+int prepare_dense(fd_ctx* ctx, ImpArgs& a, fd_linop* lop, const float* stdv, int fourier, hipStream_t s, DenseOp* dop, const char* who) {
+    if (int rc = fd_linop_prepare(ctx, lop, a.T, fourier, s, dop, who)) return rc;
+    a.stdv = stdv;
+    return FD_OK;
+}
+
 // (alpha, s) of level i of an n-step grid: the perturbation kernel at timesteps[i], the clean level (1, 0) at i = n
 void level_coef(const fd_sde_params& sde, const float* timesteps, int n_steps, int i, double* alpha, double* sdev) {
     *alpha = 1.0;
@@ -292,12 +307,13 @@ void level_coef(const fd_sde_params& sde, const float* timesteps, int n_steps, i
 // the first, checked under the name `who`; a paired guide runs on x (2B,T,C) with its labels (2B) behind the score.  resample = r,
 // jump_length = j: the steps are cut into blocks [i0, min(i0 + j, n_steps)), each block runs r times, and the last step of every run
 // but the r-th re-noises from level i1 back to level i0 (RENOISE); r = 1 is the plain loop for every j.  E = r n_steps evaluations, K =
-// (r - 1) ceil(n_steps / j) re-noises; z_steps, zobs_steps (E,B,T,C) and zre_steps (K,B,T,C) in execution order.
+// (r - 1) ceil(n_steps / j) re-noises; z_steps, zobs_steps (E,B,T,C) and zre_steps (K,B,T,C) in execution order.  window > 1 or lop
+// (not both): the mask holds the operator's rows.
 int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
                 const float* x0_obs, const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier,
                 const float* z_steps, const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, int mode,
                 hipStream_t s, const fd_guide* g, const char* who, const float* zre_steps = nullptr, int resample = 1,
-                int jump_length = 1, int window = 1) {
+                int jump_length = 1, int window = 1, fd_linop* lop = nullptr) {
     fd_ctx* ctx = m->ctx;
     FD_REQUIRE(ctx, G && timesteps && x, "%s: null pointer", who);
     FD_REQUIRE(ctx, n_steps > 0, "%s: n_steps=%d", who, n_steps);
@@ -314,6 +330,11 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
     if (window > 1) {
         FD_REQUIRE(ctx, !g && resample == 1, "%s: window=%d goes with neither a guide nor resample > 1", who, window);
         if (int rc = prepare_window(ctx, a, window, feat_std, fourier, s, &agg, who)) return rc;
+    }
+    DenseOp dop{};
+    if (lop) {
+        FD_REQUIRE(ctx, !g && resample == 1 && window == 1, "%s: an operator goes with no guide, resample > 1 or window > 1", who);
+        if (int rc = prepare_dense(ctx, a, lop, feat_std, fourier, s, &dop, who)) return rc;
     }
     // per-step coefficients, on the host up front: the SDE step's (fd_sde_coef, as fd_sampler_run) and the projection's (alpha, s)
     // at the next grid point; the last step projects hard (alpha = 1, s = 0)
@@ -386,6 +407,10 @@ int impute_loop(fd_score* m, const fd_sde_params* sde, const float* G, const flo
             if (int rc = launch(ctx, a, true, fourier != 0, s, false, agg.op)) return rc;
             continue;
         }
+        if (lop) {
+            if (int rc = launch(ctx, a, true, fourier != 0, s, false, dop)) return rc;
+            continue;
+        }
         if (int rc = pair ? launch_pair(ctx, a, *g, fourier != 0, s, renoise) : launch(ctx, a, true, fourier != 0, s, renoise)) return rc;
     }
     return FD_OK;
@@ -448,6 +473,23 @@ extern "C" int fd_impute_project_agg(fd_ctx* ctx, const float* x, const float* x
     return launch(ctx, a, false, fourier != 0, hs, false, agg.op);
 }
 
+extern "C" int fd_impute_project_op(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                    const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
+                                    uint64_t seed, uint64_t offset, float* out, int B, int T, int C, fd_linop* op, void* stream) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, x && out, "fd_impute_project_op: null pointer");
+    hipStream_t hs = (hipStream_t)stream;
+    ImpArgs a{};
+    if (int rc = prepare(ctx, a, x0_obs, mask_u8, mask_per_series, feat_std, 0, G, B, T, C, hs, "fd_impute_project_op")) return rc;
+    DenseOp dop{};
+    if (int rc = prepare_dense(ctx, a, op, feat_std, fourier, hs, &dop, "fd_impute_project_op")) return rc;
+    a.x = x; a.out = out;
+    a.zobs = z;
+    a.alpha = alpha; a.s = s;
+    a.seed = seed; a.off_obs = offset;
+    return launch(ctx, a, false, fourier != 0, hs, false, dop);
+}
+
 extern "C" int fd_impute_project_renoise(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
                                          const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z,
                                          uint64_t seed, uint64_t offset, float a, float b, const float* z_re, uint64_t offset_re,
@@ -495,6 +537,19 @@ extern "C" int fd_sampler_run_impute_agg(fd_score* m, const fd_sde_params* sde, 
     return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
                        seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_agg", nullptr, 1, 1,
                        window);
+}
+
+// fd_sampler_run_impute_rep on a dense operator: mask_u8 (B/obs_replicas,M,C) or (M,C) over the M rows of `op`
+extern "C" int fd_sampler_run_impute_op(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps,
+                                        int n_steps, float dt, float* x, const float* x0_obs, const uint8_t* mask_u8,
+                                        int mask_per_series, const float* feat_std, int fourier, const float* z_steps,
+                                        const float* zobs_steps, uint64_t seed, uint64_t offset, int B, int obs_replicas, fd_linop* op,
+                                        int mode, void* stream) {
+    if (int rc = fd_loop_check(m, sde, B, mode, "fd_sampler_run_impute_op")) return rc;
+    FD_REQUIRE(m->ctx, op, "fd_sampler_run_impute_op: null operator handle");
+    return impute_loop(m, sde, G, timesteps, n_steps, dt, x, x0_obs, mask_u8, mask_per_series, feat_std, fourier, z_steps, zobs_steps,
+                       seed, offset, B, obs_replicas, mode, (hipStream_t)stream, nullptr, "fd_sampler_run_impute_op", nullptr, 1, 1, 1,
+                       op);
 }
 
 // fd_sampler_run_impute_rep on a class-conditional model under classifier-free guidance: y (B) one label per state row or null,

@@ -4,8 +4,9 @@
 // into a k-quad LDS image U (Tp x 16), phase 2 a dense product with a basis into a second image of the observation's rows, masked row
 // by row, phase 3 a second product back to the Tp packed rows with an elementwise epilogue.
 //
-//   operator        MaskOp / WindowOp: what stands between the two products.  The rows of the middle image (time steps / windows),
-//                   which half of the basis pair each product reads, and the factor of the adjoint (1 / 1 over the window length).
+//   operator        MaskOp / WindowOp / DenseOp: what stands between the two products.  The rows of the middle image (time steps /
+//                   windows / the rows of a user's matrix), which basis each product reads (the adjoint's included), and the factor
+//                   of the adjoint (1 / 1 over the window length / 1).
 //   images          quad_idx (the k-quad order [(k / 4)][channel][k % 4]: the B operand of four consecutive MFMAs is one
 //                   ds_read_b128 per lane), inv_r, win_len, image_bytes.
 //   tile_product    16 rows of a row-major basis times an image on v_mfma_f32_16x16x4_f32: every phase 2 / phase 3 loop.
@@ -33,30 +34,48 @@ __device__ __forceinline__ int win_len(int j, int w, int T) { return min(w, T - 
 
 // The coordinate mask: the middle image holds the Tp time rows, keep = mask[t][c].  basis = F (Tp x Tp) then F^T (Tp x Tp).
 struct MaskOp {
-    static constexpr bool kWindow = false;
+    static constexpr bool kWindow = false, kDense = false;
     __host__ __device__ int rows(int T) const { return T; }
     __host__ __device__ int rows_padded(int Tp) const { return Tp; }
     __device__ const float* to_obs(const float* basis, int Tp) const { return basis + (size_t)Tp * Tp; }
     __device__ const float* from_obs(const float* basis, int) const { return basis; }
+    __device__ const float* adjoint_basis(const float* basis, int Tp) const { return from_obs(basis, Tp); }
     __device__ float adjoint(float r, int, int) const { return r; }
 };
 // Window means (fd_aggregate.hip): the middle image holds the Jp window rows, keep = mask[j][c].  basis = A_w (Jp x Tp) then B_w
 // (Tp x Jp); the adjoint P^T divides the masked means by the window length and reads the same B_w.
 struct WindowOp {
-    static constexpr bool kWindow = true;
+    static constexpr bool kWindow = true, kDense = false;
     int window, J, Jp;
     __host__ __device__ int rows(int) const { return J; }
     __host__ __device__ int rows_padded(int) const { return Jp; }
     __device__ const float* to_obs(const float* basis, int) const { return basis; }
     __device__ const float* from_obs(const float* basis, int Tp) const { return basis + (size_t)Jp * Tp; }
+    __device__ const float* adjoint_basis(const float* basis, int Tp) const { return from_obs(basis, Tp); }
     __device__ float adjoint(float r, int j, int T) const { return r / (float)win_len(j, window, T); }
 };
+// A dense linear observation y = P v, P (M x T) of full row rank (fd_linop.hip): the middle image holds the Mp = 16 ceil(M / 16) rows
+// of P, keep = mask[j][c].  The operator carries its own bases (the kernels' `basis` argument is not read), row-major f32, zero
+// outside (M, T): A (Mp x Tp) to the observation, B (Tp x Mp) back from it, Bt (Tp x Mp) the adjoint's, which no per-row factor of B
+// expresses.  Fourier: A = P F^T, B = F P^+, Bt = F P^T; time domain: P, P^+, P^T themselves, and the kernels run their Fourier
+// branch with rho = 1.
+struct DenseOp {
+    static constexpr bool kWindow = false, kDense = true;
+    int M, Mp;
+    const float *A, *B, *Bt;
+    __host__ __device__ int rows(int) const { return M; }
+    __host__ __device__ int rows_padded(int) const { return Mp; }
+    __device__ const float* to_obs(const float*, int) const { return A; }
+    __device__ const float* from_obs(const float*, int) const { return B; }
+    __device__ const float* adjoint_basis(const float*, int) const { return Bt; }
+    __device__ float adjoint(float r, int, int) const { return r; }
+};
 
-// dynamic LDS of one workgroup.  fourier: U (Tp x 16) and the middle image; else the window operator's time image (T x 16), and
-// nothing for the mask, which selects elementwise
+// dynamic LDS of one workgroup.  fourier (and the dense operator in both domains): U (Tp x 16) and the middle image; else the window
+// operator's time image (T x 16), and nothing for the mask, which selects elementwise
 template <class Op>
 size_t image_bytes(const Op& op, int T, int Tp, bool fourier) {
-    if (fourier) return (size_t)(Tp + op.rows_padded(Tp)) * kCB * sizeof(float);
+    if (fourier || Op::kDense) return (size_t)(Tp + op.rows_padded(Tp)) * kCB * sizeof(float);
     return Op::kWindow ? (size_t)T * kCB * sizeof(float) : 0;
 }
 

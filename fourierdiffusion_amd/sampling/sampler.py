@@ -55,6 +55,7 @@ from ..models.score_models import _PRECISIONS, ScoreModule
 from ..schedulers.sde import SDE
 from ..utils.dataclasses import DiffusableBatch
 from ..utils.fourier import dft, dft_standardize
+from .masks import LinearOperator, as_operator
 from .likelihood import ESTIMATORS, EXACT_MAX_DIMS, RK45_MAX_EVALS, LikelihoodResult, drift_divergence, drift_integral
 
 
@@ -478,13 +479,13 @@ class DiffusionSampler:
                                 atol=atol)
 
     # ------------------------------------------------------------ conditional sampling (extension, not in the reference)
-    def impute(self, observed: torch.Tensor, mask: torch.Tensor, num_diffusion_steps: Optional[int] = None, *,
+    def impute(self, observed: torch.Tensor, mask: Optional[torch.Tensor], num_diffusion_steps: Optional[int] = None, *,
                fourier_transform: bool, feature_mean: Optional[torch.Tensor] = None, feature_std: Optional[torch.Tensor] = None,
                prior_noise: Optional[Sequence[torch.Tensor]] = None, step_noise: Optional[Sequence[torch.Tensor]] = None,
                obs_noise: Optional[Sequence[torch.Tensor]] = None, num_samples: Optional[int] = None,
                conditioning: str = "replace", guidance_scale: float = 1.0, guidance_jacobian: bool = True,
                resample: int = 1, jump_length: int = 1, renoise_noise: Optional[Sequence[torch.Tensor]] = None,
-               aggregate: int = 1, obs_std: Optional[float] = None, twist_scale: float = 1.0, ess_threshold: float = 0.5,
+               aggregate: int = 1, operator=None, obs_std: Optional[float] = None, twist_scale: float = 1.0, ess_threshold: float = 0.5,
                final_resample: bool = True, resample_noise: Optional[Sequence[torch.Tensor]] = None, return_info: bool = False,
                y=None, cfg_scale: float = 1.0):
         """Samples conditioned on observations: returns a CPU tensor (n, max_len, n_channels) in SAMPLE space, as ``sample`` (map
@@ -535,6 +536,17 @@ class DiffusionSampler:
         domains (it varies inside a window).  Ensembles and both Jacobian modes work; y / cfg_scale and resample > 1 do not
         (ValueError), and max_len <= 1024.  aggregate=1: the call without the argument, to the bit.
 
+        operator = P (a ``masks.LinearOperator``, or an (M, max_len) array / tensor wrapped on the fly): the observations are a
+        GENERAL LINEAR summary y = P x per channel -- a band-limited recording, an overlapping moving average, a blur, increments
+        (``masks.lowpass_operator`` and its siblings).  ``observed`` is (n, M, C) at data scale (``masks.apply_operator``), ``mask``
+        bool (n, M, C), (M, C) or None (every row observed): True = row j of P is observed.  The formulas are those of
+        ``aggregate`` with P, P^+ = pinv(P) and P^T general (fd_sampler_run_impute_op, fd_sampler_run_impute_dps_op); under
+        "replace" P A(result) reproduces ``observed`` on the observed rows up to f32 rounding, and a mask may hide single rows
+        only when the rows of P are mutually orthogonal (else every (series, channel) column of it is all True or all False:
+        ValueError); "dps" takes any mask.  P must have full row rank and cond(P) <= the operator's max_condition (ValueError: the
+        f32 bases lose about cond(P) 2^-24).  ``feature_std`` is read in both domains.  Ensembles and both Jacobian modes work;
+        y / cfg_scale, resample > 1, conditioning="smc" and aggregate > 1 do not (ValueError), and max_len <= 1024.
+
         conditioning="smc" (num_samples = K in [2, 1024]): twisted sequential Monte Carlo, the Twisted Diffusion Sampler of Wu et
         al. 2023 (fd_sampler_run_impute_smc).  The observation model is y = A(x_0) + obs_std eps at the observed entries (obs_std
         > 0, data scale).  The K rows of a series are particles: the "dps" gradient, scaled by 1 / (2 v_i), v_i = obs_std^2 +
@@ -549,6 +561,16 @@ class DiffusionSampler:
         aggregate > 1, resample > 1, obs_noise and guidance_scale do not apply (ValueError for the first four).  The other
         conditionings ignore these arguments (obs_std, resample_noise and return_info are errors there)."""
         self._check_aggregate(aggregate, "impute")
+        op = self._operator(operator, aggregate, "impute")
+        if op is not None:
+            if y is not None or cfg_scale != 1.0:
+                raise ValueError("impute: operator is not supported with y / cfg_scale (classifier-free guidance)")
+            if isinstance(resample, int) and resample > 1:
+                raise ValueError("impute: operator is not supported with resample > 1 (RePaint)")
+            if conditioning == "smc":
+                raise ValueError("impute: operator is not supported with conditioning='smc'")
+            if mask is None:
+                mask = torch.ones(op.M, self.n_channels, dtype=torch.bool)
         if conditioning == "smc":
             return self._impute_smc(observed, mask, num_diffusion_steps, fourier_transform, feature_mean, feature_std, prior_noise,
                                     step_noise, obs_noise, num_samples, guidance_jacobian, resample, renoise_noise, aggregate, y,
@@ -581,12 +603,14 @@ class DiffusionSampler:
         dps = conditioning == "dps"
         if dps and obs_noise is not None:
             raise ValueError("impute: obs_noise is not used by conditioning='dps' (no observation is noised)")
-        obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, aggregate)
+        if op is not None and not dps and isinstance(mask, torch.Tensor) and mask.dtype == torch.bool and mask.dim() >= 2:
+            op.check_row_mask(mask, "impute")        # (before any device work; the shape is checked next)
+        obs, mask_u8, per_series, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, aggregate, op)
         self.score_model.eval()
         N, ts_arr, dt = self._sde_grid(num_diffusion_steps)
         ctx, h, p, G, mode = self._engine_args()
-        # (the guidance weighs the residual by sigma in both domains, and sigma varies inside a window)
-        fstd = std if (fourier_transform or dps or aggregate > 1) else None
+        # (the guidance weighs the residual by sigma in both domains, and sigma varies inside a window / along a row of P)
+        fstd = std if (fourier_transform or dps or aggregate > 1 or op is not None) else None
         reps = 1 if num_samples is None else int(num_samples)
         n, bs = obs.shape[0], max(1, self.sample_batch_size // ((2 if pair else 1) * reps))
         labels = self._series_labels(y, n, "impute") if guided else None
@@ -604,8 +628,20 @@ class DiffusionSampler:
             zr = None if renoise_noise is None else self._noise(renoise_noise[b], (K, rows), "renoise_noise")
             key, off = (0, 0) if (z is not None and (zo is not None or dps) and (zr is not None or K == 0)) else _rng.stream()
             m_b = mask_u8[lo:lo + nb] if per_series else mask_u8
-            x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std, aggregate, self.max_len)
-            if aggregate > 1:
+            x0 = self._x0_obs(obs[lo:lo + nb], m_b, fourier_transform, mean, std, aggregate, self.max_len, op)
+            if op is not None:
+                if dps:
+                    rc = _C.lib().fd_sampler_run_impute_dps_op(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(),
+                                                               x0.data_ptr(), m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                               int(bool(fourier_transform)), float(guidance_scale),
+                                                               int(guidance_jacobian), _C.ptr(z), key, off, rows, reps,
+                                                               op.handle(ctx), mode, _C.stream_of(X))
+                else:
+                    rc = _C.lib().fd_sampler_run_impute_op(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), x0.data_ptr(),
+                                                           m_b.data_ptr(), int(per_series), _C.ptr(fstd),
+                                                           int(bool(fourier_transform)), _C.ptr(z), _C.ptr(zo), key, off, rows, reps,
+                                                           op.handle(ctx), mode, _C.stream_of(X))
+            elif aggregate > 1:
                 if dps:
                     rc = _C.lib().fd_sampler_run_impute_dps_agg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(),
                                                                 x0.data_ptr(), m_b.data_ptr(), int(per_series), _C.ptr(fstd),
@@ -755,7 +791,7 @@ class DiffusionSampler:
     def impute_project(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: Optional[float] = None, *,
                        fourier_transform: bool, feature_std: Optional[torch.Tensor] = None,
                        noise: Optional[torch.Tensor] = None, renoise_to: Optional[float] = None,
-                       renoise_noise: Optional[torch.Tensor] = None, aggregate: int = 1) -> torch.Tensor:
+                       renoise_noise: Optional[torch.Tensor] = None, aggregate: int = 1, operator=None) -> torch.Tensor:
         """The projection of ``impute`` alone (its step-wise twin, as ``reverse_diffusion_step`` is ``sample``'s): X (B,T,C) in
         sample space -> A^-1(m A(x_obs) + (1 - m) A(X)), x_obs = alpha x0_obs + s G z with (alpha, s) the perturbation kernel at
         ``timestep`` (None: alpha = 1, s = 0, the exact projection).  x0_obs from ``observed_to_sample_space``; noise: injected
@@ -764,18 +800,28 @@ class DiffusionSampler:
         transition kernel a = alpha(t') / alpha, b = sqrt(s(t')^2 - a^2 s^2); renoise_noise: injected z_r (B,T,C) or None (Philox,
         its own stream).  aggregate = w > 1: the projection on window means (fd_impute_project_agg), mask (B, J, C) or (J, C) over
         the J = ceil(T / w) windows, x0_obs from ``observed_to_sample_space(aggregate=w)``, feature_std read in both domains; not
-        with renoise_to.  Returns a new device tensor."""
+        with renoise_to.  operator = P (``impute``): the projection on a dense operator (fd_impute_project_op), mask (B, M, C), (M, C)
+        or None over the M rows of P under the row-mask rule of ``impute``, x0_obs from ``observed_to_sample_space(operator=P)``,
+        feature_std read in both domains; not with renoise_to or aggregate > 1.  Returns a new device tensor."""
         self._check_aggregate(aggregate, "impute_project", int(X.shape[1]) if isinstance(X, torch.Tensor) and X.dim() == 3 else None)
         if aggregate > 1 and (renoise_to is not None or renoise_noise is not None):
             raise ValueError("impute_project: aggregate > 1 is not supported with renoise_to (RePaint)")
+        op = self._operator(operator, aggregate, "impute_project", int(X.shape[1]) if isinstance(X, torch.Tensor) and X.dim() == 3 else None)
+        if op is not None:
+            if renoise_to is not None or renoise_noise is not None:
+                raise ValueError("impute_project: operator is not supported with renoise_to (RePaint)")
+            if mask is None:
+                mask = torch.ones(op.M, int(X.shape[2]), dtype=torch.bool)
+            if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool and mask.dim() >= 2:
+                op.check_row_mask(mask, "impute_project")        # (before any device work; the shape is checked below)
         xd = _C.dev_f32(X.to(self.score_model.device), "X")
         x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
         if x0.shape != xd.shape or xd.dim() != 3:
             raise ValueError(f"impute_project: X {tuple(xd.shape)} and x0_obs {tuple(x0.shape)} must be the same (B,T,C) shape")
         B, T, Cn = xd.shape
-        m_u8, per_series = self._mask_u8(mask, B, -(-T // aggregate), Cn, xd.device)
+        m_u8, per_series = self._mask_u8(mask, B, -(-T // aggregate) if op is None else op.M, Cn, xd.device)
         std = None
-        if (fourier_transform or aggregate > 1) and feature_std is not None:
+        if (fourier_transform or aggregate > 1 or op is not None) and feature_std is not None:
             std = _C.dev_f32(feature_std.to(xd.device), "feature_std")
             if tuple(std.shape) != (T, Cn):
                 raise ValueError(f"impute_project: feature_std must have shape {(T, Cn)}, got {tuple(std.shape)}")
@@ -805,6 +851,13 @@ class DiffusionSampler:
                                                     _C.ptr(zr), off_r, out.data_ptr(), B, T, Cn, _C.stream_of(xd))
             _C.check(rc, h)
             return out
+        if op is not None:
+            rc = _C.lib().fd_impute_project_op(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
+                                               int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha),
+                                               float(sdev), _C.ptr(z), key, off, out.data_ptr(), B, T, Cn, op.handle(h),
+                                               _C.stream_of(xd))
+            _C.check(rc, h)
+            return out
         if aggregate > 1:
             rc = _C.lib().fd_impute_project_agg(h, xd.data_ptr(), x0.data_ptr(), m_u8.data_ptr(), int(per_series), _C.ptr(std),
                                                 int(bool(fourier_transform)), sch.G_on(xd.device).data_ptr(), float(alpha),
@@ -820,7 +873,7 @@ class DiffusionSampler:
 
     def impute_guidance(self, X: torch.Tensor, x0_obs: torch.Tensor, mask: torch.Tensor, timestep: float, *,
                         fourier_transform: bool, feature_std: Optional[torch.Tensor] = None, jacobian: bool = True,
-                        aggregate: int = 1, y=None, cfg_scale: float = 1.0) -> tuple:
+                        aggregate: int = 1, operator=None, y=None, cfg_scale: float = 1.0) -> tuple:
         """One guidance evaluation of ``impute(conditioning="dps")`` alone (fd_impute_guidance): X (B,T,C) in sample space at
         ``timestep`` -> (g, rnorm2), g = -grad_X ||r||^2 (B,T,C) float32 and rnorm2 = ||r||^2 per row (B,) float64, both on the
         device.  x0_obs from ``observed_to_sample_space``; feature_std: the datamodule's std when it standardises (used in both
@@ -830,10 +883,17 @@ class DiffusionSampler:
         w J_c + (1 - w) J_u (fd_impute_guidance_cfg); g and rnorm2 for the B rows.
         aggregate = w > 1: the residual of the window means (fd_impute_guidance_agg), mask (B, J, C) or (J, C) over the
         J = ceil(T / w) windows, x0_obs from ``observed_to_sample_space(aggregate=w)``, rnorm2 the sum over windows; not with y /
-        cfg_scale."""
+        cfg_scale.  operator = P (``impute``): the residual of P's rows (fd_impute_guidance_op), any mask (B, M, C), (M, C) or None,
+        x0_obs from ``observed_to_sample_space(operator=P)``, rnorm2 the sum over rows; not with y / cfg_scale or aggregate > 1."""
         self._check_aggregate(aggregate, "impute_guidance")
         if aggregate > 1 and (y is not None or cfg_scale != 1.0):
             raise ValueError("impute_guidance: aggregate > 1 is not supported with y / cfg_scale (classifier-free guidance)")
+        op = self._operator(operator, aggregate, "impute_guidance")
+        if op is not None:
+            if y is not None or cfg_scale != 1.0:
+                raise ValueError("impute_guidance: operator is not supported with y / cfg_scale (classifier-free guidance)")
+            if mask is None:
+                mask = torch.ones(op.M, self.n_channels, dtype=torch.bool)
         guided, _pair = self._guided(y, cfg_scale)
         T, Cn = self.max_len, self.n_channels
         if not (isinstance(X, torch.Tensor) and isinstance(x0_obs, torch.Tensor)) or x0_obs.shape != X.shape or X.dim() != 3 \
@@ -844,7 +904,7 @@ class DiffusionSampler:
         if feature_std is not None and tuple(feature_std.shape) != (T, Cn):
             raise ValueError(f"impute_guidance: feature_std must have shape {(T, Cn)}, got {tuple(feature_std.shape)}")
         B = X.shape[0]
-        m_u8, per_series = self._mask_u8(mask, B, -(-T // aggregate), Cn, self.score_model.device)
+        m_u8, per_series = self._mask_u8(mask, B, -(-T // aggregate) if op is None else op.M, Cn, self.score_model.device)
         xd = _C.dev_f32(X.to(self.score_model.device), "X")
         x0 = _C.dev_f32(x0_obs.to(xd.device), "x0_obs")
         std = None if feature_std is None else _C.dev_f32(feature_std.to(xd.device), "feature_std")
@@ -860,6 +920,13 @@ class DiffusionSampler:
                                                  float(cfg_scale), _C.stream_of(xd))
             _C.check(rc, ctx)
             return g, rn2
+        if op is not None:
+            rc = _C.lib().fd_impute_guidance_op(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(),
+                                                m_u8.data_ptr(), int(per_series), _C.ptr(std), int(bool(fourier_transform)),
+                                                int(bool(jacobian)), g.data_ptr(), rn2.data_ptr(), B, 1, op.handle(ctx), mode,
+                                                _C.stream_of(xd))
+            _C.check(rc, ctx)
+            return g, rn2
         if aggregate > 1:
             rc = _C.lib().fd_impute_guidance_agg(h, C.byref(p), G.data_ptr(), float(timestep), xd.data_ptr(), x0.data_ptr(),
                                                  m_u8.data_ptr(), int(per_series), _C.ptr(std), int(bool(fourier_transform)),
@@ -873,15 +940,33 @@ class DiffusionSampler:
         _C.check(rc, ctx)
         return g, rn2
 
-    def observed_to_sample_space(self, observed: torch.Tensor, mask: torch.Tensor, *, fourier_transform: bool,
+    def observed_to_sample_space(self, observed: torch.Tensor, mask: Optional[torch.Tensor], *, fourier_transform: bool,
                                  feature_mean: Optional[torch.Tensor] = None,
-                                 feature_std: Optional[torch.Tensor] = None, aggregate: int = 1) -> torch.Tensor:
+                                 feature_std: Optional[torch.Tensor] = None, aggregate: int = 1, operator=None) -> torch.Tensor:
         """x0_obs = A^-1(where(mask, observed, 0)) on the device (what ``impute`` conditions on; the input of ``impute_project``).
         aggregate = w > 1: observed and mask over the J = ceil(T / w) windows, x0_obs = A^-1(P^+ where(mask, observed, 0)) (n, T, C),
-        P^+ the piecewise-constant lift."""
+        P^+ the piecewise-constant lift.  operator = P (``impute``): observed and mask over the M rows of P (mask None: all observed),
+        P^+ = pinv(P), the whole map in float64 on the host."""
         self._check_aggregate(aggregate, "observed_to_sample_space")
-        obs, mask_u8, _, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, aggregate)
-        return self._x0_obs(obs, mask_u8, fourier_transform, mean, std, aggregate, self.max_len)
+        op = self._operator(operator, aggregate, "observed_to_sample_space")
+        if op is not None and mask is None:
+            mask = torch.ones(op.M, self.n_channels, dtype=torch.bool)
+        obs, mask_u8, _, mean, std = self._conditioning(observed, mask, feature_mean, feature_std, aggregate, op)
+        return self._x0_obs(obs, mask_u8, fourier_transform, mean, std, aggregate, self.max_len, op)
+
+    def _operator(self, operator, aggregate: int, who: str, T="max_len") -> Optional[LinearOperator]:
+        """None, or the LinearOperator of ``operator`` (wrapped on the fly from an (M, T) array / tensor).  ValueError when it comes
+        together with aggregate > 1 or its T is not this sampler's max_len (T: as in ``_check_aggregate``)."""
+        if operator is None:
+            return None
+        if aggregate > 1:
+            raise ValueError(f"{who}: aggregate > 1 is not supported together with operator (window means are "
+                             "masks.window_mean_operator)")
+        op = as_operator(operator)
+        T = self.max_len if T == "max_len" else T
+        if T is not None and op.T != T:
+            raise ValueError(f"{who}: operator has T = {op.T} columns, expected {T}")
+        return op
 
     def _check_aggregate(self, aggregate, who: str, T="max_len") -> None:
         """ValueError unless aggregate is an int in [1, T] (T: this sampler's max_len, or None to leave the upper end open)."""
@@ -889,12 +974,13 @@ class DiffusionSampler:
         if isinstance(aggregate, bool) or not isinstance(aggregate, int) or aggregate < 1 or (T is not None and aggregate > T):
             raise ValueError(f"{who}: aggregate must be an int in [1, {'T' if T is None else T}], got {aggregate!r}")
 
-    def _conditioning(self, observed, mask, feature_mean, feature_std, aggregate: int = 1):
+    def _conditioning(self, observed, mask, feature_mean, feature_std, aggregate: int = 1, op: Optional[LinearOperator] = None):
         """Validated device copies: observed (n,T,C) f32, mask as uint8 (n,T,C) or (T,C), per-series flag, mean, std.  aggregate = w
-        > 1: observed and mask over the J = ceil(T / w) windows, (n,J,C) and (n,J,C) or (J,C); mean and std stay (T,C)."""
+        > 1: observed and mask over the J = ceil(T / w) windows, (n,J,C) and (n,J,C) or (J,C); mean and std stay (T,C).  op: over
+        the operator's M rows instead."""
         if not isinstance(mask, torch.Tensor):
             raise ValueError("observed and mask must be torch tensors")
-        J = -(-self.max_len // aggregate)
+        J = -(-self.max_len // aggregate) if op is None else op.M
         n = self._check_series(observed, "observed", J)
         if not observed.is_floating_point():
             raise ValueError(f"observed must be a floating-point tensor, got {observed.dtype}")
@@ -932,8 +1018,16 @@ class DiffusionSampler:
 
     @staticmethod
     def _x0_obs(obs: torch.Tensor, m_u8: torch.Tensor, fourier_transform: bool, mean, std, aggregate: int = 1,
-                T: Optional[int] = None) -> torch.Tensor:
+                T: Optional[int] = None, op: Optional[LinearOperator] = None) -> torch.Tensor:
         y0 = torch.where(m_u8.bool(), obs, torch.zeros((), dtype=obs.dtype, device=obs.device))   # NaN at unobserved entries: gone
+        if op is not None:     # A^-1(P^+ y0) once per call, in float64 on the host (not a hot path), then uploaded
+            v = torch.einsum("tm,nmc->ntc", torch.from_numpy(op.P_pinv), y0.double().cpu())
+            if fourier_transform:      # the packed ortho real DFT: Re X_0 .. Re X_{T/2}, then Im X_1 .. Im X_{ceil(T/2)-1}
+                Xf = torch.fft.rfft(v, dim=1, norm="ortho")
+                v = torch.cat([Xf.real, Xf.imag[:, 1:v.shape[1] - Xf.shape[1] + 1]], dim=1)
+            if std is not None:
+                v = (v - mean.double().cpu()) / std.double().cpu()
+            return v.float().to(obs.device).contiguous()
         if aggregate > 1:      # P^+: every entry takes its window's value
             y0 = y0.repeat_interleave(aggregate, dim=1)[:, :T].contiguous()
         if fourier_transform:

@@ -530,6 +530,47 @@ int fd_sampler_run_impute_dps_agg(fd_score* m, const fd_sde_params* sde, const f
                                   const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
                                   uint64_t seed, uint64_t offset, int B, int obs_replicas, int window, int mode, void* stream);
 
+/* Conditioning on a dense linear observation (NOT in the reference; replaces nothing in it): per channel y = P v for a matrix P
+ * (M x T) of full row rank that the caller supplies, shared by all series and channels, T the model's max_len, 1 <= M <= T <= 1024
+ * -- a band-limited recording, a moving average with overlapping windows, a blur, increments.  The window means above are one such P.
+ * The formulas are those of the window-mean entries with P, P^+ = pinv(P) and P^T general:
+ *   x' = x + dft(P^+ (m . P idft(sigma . d))) / sigma      (fourier == 0: x' = x + P^+ (m . P (sigma . d)) / sigma)
+ *   r = m . P idft(sigma . (x0_obs - x0_hat)) (M,C), u = sigma . diag(1/rho) F P^T r      (fourier == 0: P for P idft, u = sigma . P^T r)
+ * mask_u8 is (B / obs_replicas,M,C) when mask_per_series, else (M,C): 1 = row j of P is observed for that channel; x0_obs stays
+ * (B / obs_replicas,T,C): A^-1(P^+ where(m, y, 0)).  The replacement is the orthogonal projection onto {x : m . P A(x) = m . y} only when the
+ * rows of P are mutually orthogonal or every (series, channel) column of the mask is all 1 or all 0: the caller checks that, and the
+ * rank and conditioning of P (the f32 bases lose about cond(P) 2^-24 relative accuracy); the engine does not.  feat_std is read in
+ * BOTH domains.  No labels, no classifier-free guidance and no RePaint.
+ *
+ * fd_linop_create   (NOT in the reference; replaces nothing in it) the handle of one operator: P (M,T) and Pplus (T,M), row-major
+ *                   doubles on the HOST, copied to the device before the call returns.  FD_ERR_ARG: null pointer, M < 1, M > T or
+ *                   T > 1024.  The first call of an entry below for a (handle, domain) builds three f32 bases on the device in
+ *                   double (Mp x Tp, Tp x Mp and Tp x Mp floats, Mp = 16 ceil(M/16)) and waits for them; they belong to the handle.
+ * fd_linop_destroy  (NOT in the reference; replaces nothing in it) frees the handle and its device tables; the caller keeps it alive
+ *                   until the work that reads it was enqueued, and destroys it before its context.  NULL is allowed.
+ * fd_impute_project_op, fd_sampler_run_impute_op, fd_impute_guidance_op, fd_sampler_run_impute_dps_op
+ *                   (NOT in the reference; replace nothing in it) fd_impute_project_agg, fd_sampler_run_impute_agg,
+ *                   fd_impute_guidance_agg and fd_sampler_run_impute_dps_agg with the handle in the place of `window`: Philox layouts,
+ *                   noise tensors and obs_replicas as there.  FD_ERR_ARG: a null handle, a handle of another context, one whose T is
+ *                   not the call's, or M > T. */
+typedef struct fd_linop fd_linop;
+int fd_linop_create(fd_ctx* ctx, int T, int M, const double* P, const double* Pplus, fd_linop** out);
+int fd_linop_destroy(fd_linop* op);
+int fd_impute_project_op(fd_ctx* ctx, const float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                         const float* feat_std, int fourier, const float* G, float alpha, float s, const float* z, uint64_t seed,
+                         uint64_t offset, float* out, int B, int T, int C, fd_linop* op, void* stream);
+int fd_sampler_run_impute_op(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                             float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                             const float* feat_std, int fourier, const float* z_steps, const float* zobs_steps, uint64_t seed,
+                             uint64_t offset, int B, int obs_replicas, fd_linop* op, int mode, void* stream);
+int fd_impute_guidance_op(fd_score* m, const fd_sde_params* sde, const float* G, float t, const float* x, const float* x0_obs,
+                          const uint8_t* mask_u8, int mask_per_series, const float* feat_std, int fourier, int jacobian,
+                          float* g_out, double* rnorm2_out, int B, int obs_replicas, fd_linop* op, int mode, void* stream);
+int fd_sampler_run_impute_dps_op(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps,
+                                 float dt, float* x, const float* x0_obs, const uint8_t* mask_u8, int mask_per_series,
+                                 const float* feat_std, int fourier, float guidance_scale, int jacobian, const float* z_steps,
+                                 uint64_t seed, uint64_t offset, int B, int obs_replicas, fd_linop* op, int mode, void* stream);
+
 /* Probability-flow ODE extension (NOT in the reference, whose only sampler is Euler-Maruyama over the reverse SDE; Song et al. 2021,
  * Sec. 4.3): the deterministic ODE with the reverse SDE's marginals.  With a = a_x(t), g = g(t) of the SDE (VP: a = beta/2,
  * g = sqrt(beta); VE: a = 0, g = sigma_min sqrt(2 ln(sigma_max/sigma_min)) (sigma_max/sigma_min)^t) and s the score:
