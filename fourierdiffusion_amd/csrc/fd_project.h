@@ -84,6 +84,7 @@ size_t image_bytes(const Op& op, int T, int Tp, bool fourier) {
 //   T, -T, -T - 2^20                          fd_fourier.hip: the FFT twiddles and packing tables, built on the host
 //   -T - 2^21                                 fd_impute_basis: F and F^T of the packed real DFT
 //   -3 2^20 - ((window - 1) 1025 + T)         fd_agg_prepare: A_w and B_w; below every key above
+//   -8 2^20 - (2 S + window)                  fd_series_spectra (fd_spectral.hip): the double window and the [cos | sin] basis of nperseg S
 // The table of `key` (n floats), built on first use by fill(table) on stream s; null if it could not be built.  The build is
 // synchronised, once per (context, key): later callers may use another stream.
 template <class Fill>

@@ -34,6 +34,9 @@ from ..utils.posthoc import MAX_CLASSES as POSTHOC_MAX_CLASSES
 from ..utils.posthoc import MAX_D_MODEL as POSTHOC_MAX_D_MODEL
 from ..utils.posthoc import discriminative_score, fit_classifier, predictive_score
 from ..utils.sinkhorn import DEFAULT_REG, sinkhorn_divergence
+from ..utils.spectral import check_options as spectral_options
+from ..utils.spectral import pair_indices, resolve_segments, series_spectra
+from ..utils.spectral import series_shape as spectral_shape
 from ..utils.tensors import check_flat_array
 from ..utils.two_sample import DEFAULT_SCALES, MAX_COLUMNS, _check_scales, mmd_permutation_test
 from ..utils.wasserstein import WassersteinDistances
@@ -624,6 +627,110 @@ class TemporalDependence(Metric):
     @property
     def name(self) -> str:
         return "temporal_dependence"
+
+
+class SpectralDependence(Metric):
+    """Does the generator reproduce how the channels relate as a function of frequency?  Per series Welch's power spectral density of
+    every channel, the cross-spectral density of every channel pair and each channel's spectral centroid and entropy
+    (utils/spectral.py); then, between the samples and the real set,
+      psd_log_distance, psd_log_distance_max    mean / max over (bin >= 1, channel) of |10 log10(mean PSD of the samples / mean PSD of the
+                                                real set)|, in dB; each set-mean PSD floored at 1e-12 of the channel's mean total power
+      coherence_distance, coherence_distance_max  mean / max over (bin >= 1, c < d) of the absolute difference of the SET-LEVEL
+                                                magnitude-squared coherences |P_cd|^2 / (P_cc P_dd); omitted for one channel
+      phase_distance                            sum w |wrap(phase of the samples - phase of the real set)| / sum w over the same entries,
+                                                w the real set's coherence (radians); omitted for one channel or when sum w = 0
+      spectral_centroid_wasserstein, spectral_entropy_wasserstein   mean over channels of the Wasserstein-2 distance between the
+                                                DISTRIBUTIONS of the per-series values (MarginalWasserstein's arithmetic)
+      ..._holdout                               (with `holdout_samples`) against real series the model was not trained on
+      ..._self                                  (baseline) the two folds of the original samples
+    The set-level coherence averages over n * n_segments segments, so one segment per series (nperseg = T) is meaningful: a coupling
+    at a lag longer than TemporalDependence's cross lags, or one confined to a band, shows here.  `nperseg=None` is T for T < 32, else
+    T // 2; `noverlap=None` is nperseg // 2; `window` is "hann" or "boxcar".  `max_original` evaluates against a seeded subsample of
+    the real set.  The real set's features are computed once, here.  Needs (n, T, C) original samples: bound in the time view only."""
+    views = ("time",)
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 nperseg: Optional[int] = None, noverlap: Optional[int] = None, window: str = "hann",
+                 max_original: Optional[int] = None, random_seed: int = 0) -> None:
+        if len(tuple(original_samples.shape)) != 3:
+            raise ValueError(f"SpectralDependence needs the original samples as (n, T, C) series, got shape "
+                             f"{tuple(original_samples.shape)}: a flat (n, d) array has lost its time axis")
+        _, T, C = spectral_shape(original_samples, "original samples")
+        self.series_shape = (T, C)
+        self.nperseg, self.noverlap = resolve_segments(T, nperseg, noverlap)
+        spectral_options(window, "constant", (), C)
+        self.window = window
+        if max_original is not None and (isinstance(max_original, bool) or int(max_original) != max_original or max_original < 2):
+            raise ValueError(f"max_original={max_original} must be an integer >= 2")
+        if len(original_samples) < 1:
+            raise ValueError("SpectralDependence needs at least one original sample")
+        if holdout_samples is not None:
+            if len(holdout_samples) < 1:
+                raise ValueError("SpectralDependence needs at least one held-out sample")
+            if int(np.prod(tuple(holdout_samples.shape)[1:])) != T * C:
+                raise ValueError("original and held-out samples must have the same number of features")
+        super().__init__(original_samples=original_samples)
+        self.max_original, self.random_seed = max_original, random_seed
+        n = self.original_samples.shape[0]
+        if max_original is not None and n > max_original:
+            keep = torch.from_numpy(subsample_indices(n, int(max_original), random_seed)).to(self.original_samples.device)
+            self.original_samples = self.original_samples[keep].contiguous()
+            n = int(max_original)
+        self._real = self._features(self.original_samples)
+        self._held = self._features(check_flat_array(holdout_samples)) if holdout_samples is not None else None
+        self._folds = None
+        if n // 2 >= 1:
+            self._folds = (self._features(self.original_samples[: n // 2].contiguous()),
+                           self._features(self.original_samples[n // 2:].contiguous()))
+        self._baseline: Optional[dict[str, float]] = None
+
+    def _features(self, rows: torch.Tensor):
+        T, C = self.series_shape
+        if rows.dim() != 2 or rows.shape[1] != T * C:
+            raise ValueError(f"samples of {tuple(rows.shape[1:])} features, the original samples are series of shape {(T, C)}")
+        return series_spectra(rows.view(rows.shape[0], T, C), nperseg=self.nperseg, noverlap=self.noverlap, window=self.window,
+                              per_series=("summary",))
+
+    def _compare(self, samples, real, suffix: str) -> dict[str, float]:
+        C = self.series_shape[1]
+        out: dict[str, float] = {}
+        ps, pr = (torch.maximum(f.set_mean.psd, 1e-12 * f.set_mean.summary[:, 0][None, :]).cpu().numpy()[1:] for f in (samples, real))
+        live = (ps > 0) & (pr > 0)                                    # a channel that is constant in a whole set has no spectrum
+        d = np.where(live, np.abs(10.0 * np.log10(np.where(live, ps, 1.0) / np.where(live, pr, 1.0))), 0.0)
+        out[f"psd_log_distance{suffix}"], out[f"psd_log_distance_max{suffix}"] = float(d.mean()), float(d.max())
+        if C > 1:
+            c, e = pair_indices(C)
+            cs, cr = (f.set_mean.coherence().cpu().numpy()[1:, c, e] for f in (samples, real))
+            d = np.abs(cs - cr)
+            out[f"coherence_distance{suffix}"], out[f"coherence_distance_max{suffix}"] = float(d.mean()), float(d.max())
+            dphi = (samples.set_mean.phase() - real.set_mean.phase()).cpu().numpy()[1:, c, e]
+            dphi = np.abs((dphi + np.pi) % (2 * np.pi) - np.pi)
+            if cr.sum() > 0:
+                out[f"phase_distance{suffix}"] = float((cr * dphi).sum() / cr.sum())
+        for i, name in ((1, "spectral_centroid_wasserstein"), (2, "spectral_entropy_wasserstein")):
+            w = WassersteinDistances(original_data=real.summary[:, :, i], other_data=samples.summary[:, :, i],
+                                     seed=self.random_seed).marginal_distances()
+            out[f"{name}{suffix}"] = float(np.mean(w))
+        return out
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = self._features(check_flat_array(other_samples))
+        out = self._compare(samples, self._real, "")
+        if self._held is not None:
+            out.update(self._compare(samples, self._held, "_holdout"))
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, float]:
+        if self._folds is None:
+            return {}
+        if self._baseline is None:                                    # two folds of the original samples, as the Wasserstein metrics
+            self._baseline = self._compare(self._folds[0], self._folds[1], "_self")
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "spectral_dependence"
 
 
 class _PosthocScore(Metric):

@@ -948,6 +948,56 @@ int fd_series_dependence(fd_ctx* ctx, const float* x, int n, int T, int C, int a
                          float* out_ccf /* (n, Lx + 1, C, C) or NULL */, double* out_set_mean /* (F) or NULL */, void* work,
                          size_t work_bytes, void* stream);
 
+/* Spectral dependence: Welch's averaged periodogram of every series (NOT in the reference; scipy.signal.welch / csd's conventions at
+ * fs = 1, scaling = "density", one-sided; the metric is host arithmetic on the set means, utils/spectral.py).
+ * x (n, T, C) dense row-major fp32 device series with finite entries; S = nperseg in [2, T], noverlap in [0, S - 1], H = S - noverlap;
+ * segments start at 0, H, 2 H, ... while start + S <= T (a tail is dropped), nseg = (T - S) / H + 1; K = S / 2 + 1 bins, f_k = k / S;
+ * window 0 = boxcar, 1 = periodic Hann 0.5 - 0.5 cos(2 pi s / S); detrend 1 subtracts every segment's mean, 0 nothing.
+ * For one series, v = (segment - its mean) w:
+ *   F[k, c] = sum_s v[s, c] exp(-2 pi i k s / S)
+ *   P[k, c, d] = scale_k / (nseg sum w^2) sum_seg conj(F[k, c]) F[k, d],  scale_k = 2, but 1 at k = 0 and at the Nyquist bin of an even S
+ *   out_psd     (n, K, C) fp32 or NULL       P[k, c, c]
+ *   out_csd     (n, K, NP, 2) fp32 or NULL   (Re, Im) P[k, c, d] of the NP = C (C - 1) / 2 pairs c < d in row-major pair order
+ *   out_summary (n, C, 3) fp32 or NULL       total power sum_k psd; spectral centroid sum f_k psd_k / sum psd_k and spectral entropy
+ *               -sum p ln p / ln(K - 1), p_k = psd_k / sum psd, both over the bins 1..K-1 (bin 0 holds only leakage after detrending)
+ *   out_set_mean (F) DOUBLES, required      the mean over the n series of every fp32 feature as returned, in the order
+ *               psd | csd | summary, F = K C + 2 K NP + 3 C
+ * A channel whose S entries are bit-equal in every segment has v == 0 exactly under detrend (below): its psd, every csd entry it
+ * takes part in and its summaries are 0, not NaN; no other entry is affected.  K = 2 gives entropy 0.
+ * Arithmetic (csrc/fd_spectral.hip).  One fused kernel: a series is read once into the LDS.  The segment sum is a DOUBLE sum (16
+ * lanes per (segment, channel), strided, then a butterfly); the entry is ((double)S x - sum) (1 / S): on floats of a grid S x and the
+ * sum are exact, so x + 1000 gives the bits of x; S equal floats give 0.  It is multiplied by the double window and rounded to fp32
+ * ONCE.  The DFT is a product against a [cos | sin] basis built on the device in
+ * double (angle 2 pi (k s mod S) / S), rounded to fp32 once and cached on the context per (S, window); it runs on
+ * v_mfma_f32_16x16x4_f32 with fp32 accumulation (any S: no radix).  conj(F_c) F_d is summed over the segments in segment order in
+ * double, scaled and rounded to fp32; the summaries come from the double PSD.  fp32 enters three times: v, the basis with the DFT's
+ * accumulation, the returned value.
+ * Pure function per series: a series' features depend on that series and (T, C, S, noverlap, window, detrend) alone -- not on n, its
+ * position, the grid or which outputs are asked for.  The PSD goes through the cross-spectrum's code: csd of a channel copied into two
+ * columns has the PSD's bits as its real part and imaginary part 0.
+ * Set means: series are cut into chunks of 32; a chunk's features are added in double in series order by the one thread that owns
+ * the feature, into a cell of work; a second kernel adds the chunks of every 64 in chunk order and a third those sums in order: a
+ * grouping that depends on n alone.  No atomics: bit-identical between runs and for every grid (FDIFF_SPEC_SPLITS forces the
+ * workgroup count).
+ * Error against the float64 value, u = 2^-24, v = 2^-53, gamma = (S + 1) u / (1 - (S + 1) u): a segment entry is off by at most
+ * h_s = (u + 4 v) |v_s| + rho w_s, rho = (S + 2) v max |x| (0 without detrend); a cos or sin sum by at most
+ * eps_c = sum_s h_s + gamma sum_s (|v_s| + h_s), which scales with the segment's 1-norm (with sqrt(S x total power)), not with the
+ * bin's own magnitude; P[k, c, d] by at most scale_k / (nseg sum w^2) sum_seg (sqrt(2) (eps_c |F_d| + eps_d |F_c|) + 2 eps_c eps_d)
+ * + u |P|; the summaries by the quotient rule on these (tests/spectral_ref.py evaluates them per entry; DESIGN.md 3.34 derives them).
+ * Limits: T <= 1024, C <= 64, and the LDS plan of one series -- the series (4 T C bytes), the segment image and the DFT image
+ * (4 Np (Sp + Mp) bytes with Sp, Mp, Np = S, 2 K and nseg C rounded up to 16), the double PSD (8 K C), the window (8 Sp), the pair
+ * table (2 NP) and, while they take 8 KiB or less, the chunk sums (8 F) -- within 160 KiB: every datamodule shape at the default
+ * nperseg.  work: caller-owned device bytes, at least
+ * fd_series_spectra_workspace_bytes of the same shape.
+ * FD_ERR_ARG (nothing is launched): null x, n, T or C < 1, T > 1024 or C > 64, nperseg outside [2, T], noverlap outside
+ * [0, nperseg - 1], window or detrend neither 0 nor 1, more LDS than the plan may take, n F or n T C >= 2^31, null out_set_mean,
+ * out_csd with C = 1, a workspace that is null or too small. */
+int fd_series_spectra_workspace_bytes(fd_ctx* ctx, int n, int T, int C, int nperseg, int noverlap, size_t* bytes);
+int fd_series_spectra(fd_ctx* ctx, const float* x, int n, int T, int C, int nperseg, int noverlap, int window, int detrend,
+                      float* out_psd /* (n, K, C) or NULL */, float* out_csd /* (n, K, NP, 2) or NULL */,
+                      float* out_summary /* (n, C, 3) or NULL */, double* out_set_mean /* (F) */, void* work, size_t work_bytes,
+                      void* stream);
+
 /* Post-hoc discriminative and predictive scores (NOT in the reference; TimeGAN, Yoon et al. 2019, and TSGBench; DESIGN.md 3.31,
  * utils/posthoc.py): what a small network trained AFTER the fact needs around the causal LSTM backbone (fd_score_create_ex with
  * FD_BACKBONE_LSTM), whose output at time t sees the inputs <= t only -- out[:, t] regressed on x[:, t + 1] is a next-step
