@@ -446,44 +446,95 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
     };
     auto layer_ptr = [&](int l) -> const char* { return P.img_layers + (size_t)l * P.layer_stride; };
 
+    // Feature-padding guard of C-layout row tile dt in this lane (rows 16 dt + 4 g ... + 3).  g is masked to its two bits HERE and
+    // not in refresh_lane(): with D a compile-time constant the guard then folds to `true` for every row tile but the last one
+    // (16 dt + 12 < D), while `lane` and `g` stay opaque for every address of the units and the FFN loop.  The last row tile's
+    // guard is lane-divergent (D = 72: lane groups 0-1 live): callers take it as a SELECT on values and read their vectors at
+    // row_clamped() -- an `if` costs an exec-mask region per use, and each region ends a basic block.
+    // STRAIGHT is off where hipcc answers ANY change of these phases with more spills than the guarded form has (the allocation of
+    // the 4-tile ShapeModel kernel: 65 -> 89 spilled dwords from the folded guards alone; scratch 140 -> 148 B/lane in the ODE
+    // variant of <3,5,2,4>): those instantiations keep the guarded form (`if (live)` with the unmasked g).
+    constexpr bool STRAIGHT = !(MT == 4 && SH::T == 0 && (SH::D != 0 || (ODE && KS1 == 3 && DT == 5 && KSO == 2)));
+    auto row_live = [&](int dt) -> bool { return 16 * dt + 4 * (STRAIGHT ? (g & 3) : g) < D; };
+    auto row_clamped = [&](int dt) -> int { return row_live(dt) ? 16 * dt + 4 * (g & 3) : 0; };
+
     // LayerNorm of two C-layout tiles (DT row tiles each) over the D features of token lane&15, in place; both tiles in one
-    // basic block so that their reductions and LDS reads interleave
+    // call so that their reductions and LDS reads interleave (one basic block in the STRAIGHT form only: every `if (live)` of the
+    // guarded form is an exec-mask region that ends a block)
     auto layer_norm2 = [&](f32x4 (&va)[DT], f32x4 (&vb)[DT], const float* __restrict__ gamma, const float* __restrict__ beta) {
         float sa = 0.f, sb = 0.f;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-            if (16 * dt + 4 * g < D) {
-                sa += (va[dt][0] + va[dt][1]) + (va[dt][2] + va[dt][3]);
-                sb += (vb[dt][0] + vb[dt][1]) + (vb[dt][2] + vb[dt][3]);
+        for (int dt = 0; dt < DT; ++dt) {
+            const bool live = row_live(dt);
+            const float ta = (va[dt][0] + va[dt][1]) + (va[dt][2] + va[dt][3]);
+            const float tb = (vb[dt][0] + vb[dt][1]) + (vb[dt][2] + vb[dt][3]);
+            if constexpr (STRAIGHT) {
+                sa += live ? ta : 0.f;
+                sb += live ? tb : 0.f;
+            } else if (live) {
+                sa += ta;
+                sb += tb;
             }
+        }
         const float invD = 1.0f / (float)D;
-        const float ma = group_sum(sa) * invD, mb = group_sum(sb) * invD;
+        // The means are ROUNDED products: as one basic block, the subtractions below would otherwise absorb this multiply
+        // (v - s * invD as one fma, a different rounding from the guarded form's, whose subtractions sit in other blocks).
+        float ma, mb;
+        {
+#pragma clang fp contract(off)
+            ma = group_sum(sa) * invD;
+            mb = group_sum(sb) * invD;
+        }
         float qa = 0.f, qb = 0.f;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-            if (16 * dt + 4 * g < D) {
+        for (int dt = 0; dt < DT; ++dt) {
+            const bool live = row_live(dt);
+            if (STRAIGHT || live) {
+                // STRAIGHT: a dead row contributes fma(0, 0, q) = q, the same sum as skipping it.  The rounding is spelled out (fma
+                // per square; the first pair as fma(c0, c0, c1 c1), the second product rounded): left to -ffp-contract=fast, hipcc
+                // chooses fma or mul + add per basic block, and any change of these phases' block structure moved the samples
+                // by 7e-4 of scale after 20 steps.  (The guarded form before it had BOTH answers in one kernel -- fused in four
+                // row tiles, unfused in one -- so its bits are not reproduced by this or by any one spelling: DESIGN 3.2.)
+                float ca[4], cb[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float ca = va[dt][r] - ma, cb = vb[dt][r] - mb;
-                    qa += ca * ca;
-                    qb += cb * cb;
+                    ca[r] = (!STRAIGHT || live) ? va[dt][r] - ma : 0.f;
+                    cb[r] = (!STRAIGHT || live) ? vb[dt][r] - mb : 0.f;
+                }
+                if (dt == 0) {
+                    float pa, pb;
+                    {
+#pragma clang fp contract(off)
+                        pa = ca[1] * ca[1];
+                        pb = cb[1] * cb[1];
+                    }
+                    qa = __builtin_fmaf(ca[0], ca[0], pa);
+                    qb = __builtin_fmaf(cb[0], cb[0], pb);
+                }
+#pragma unroll
+                for (int r = (dt == 0 ? 2 : 0); r < 4; ++r) {
+                    qa = __builtin_fmaf(ca[r], ca[r], qa);
+                    qb = __builtin_fmaf(cb[r], cb[r], qb);
                 }
             }
-        const float ra = __builtin_amdgcn_rsqf(group_sum(qa) * invD + 1e-5f), rb2 = __builtin_amdgcn_rsqf(group_sum(qb) * invD + 1e-5f);
+        }
+        const float ra = __builtin_amdgcn_rsqf(__builtin_fmaf(group_sum(qa), invD, 1e-5f));
+        const float rb2 = __builtin_amdgcn_rsqf(__builtin_fmaf(group_sum(qb), invD, 1e-5f));
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-            const int d0 = 16 * dt + 4 * g;
-            if (d0 < D) {
-                const float4 gm = *reinterpret_cast<const float4*>(gamma + d0);
-                const float4 bt = *reinterpret_cast<const float4*>(beta + d0);
-                va[dt][0] = (va[dt][0] - ma) * ra * gm.x + bt.x;
-                va[dt][1] = (va[dt][1] - ma) * ra * gm.y + bt.y;
-                va[dt][2] = (va[dt][2] - ma) * ra * gm.z + bt.z;
-                va[dt][3] = (va[dt][3] - ma) * ra * gm.w + bt.w;
-                vb[dt][0] = (vb[dt][0] - mb) * rb2 * gm.x + bt.x;
-                vb[dt][1] = (vb[dt][1] - mb) * rb2 * gm.y + bt.y;
-                vb[dt][2] = (vb[dt][2] - mb) * rb2 * gm.z + bt.z;
-                vb[dt][3] = (vb[dt][3] - mb) * rb2 * gm.w + bt.w;
+            const bool live = row_live(dt);
+            if (STRAIGHT || live) {
+                const int dr = STRAIGHT ? row_clamped(dt) : 16 * dt + 4 * g;
+                const float4 gm = *reinterpret_cast<const float4*>(gamma + dr);
+                const float4 bt = *reinterpret_cast<const float4*>(beta + dr);
+                const float gmv[4] = {gm.x, gm.y, gm.z, gm.w}, btv[4] = {bt.x, bt.y, bt.z, bt.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float na = __builtin_fmaf((va[dt][r] - ma) * ra, gmv[r], btv[r]);
+                    const float nb = __builtin_fmaf((vb[dt][r] - mb) * rb2, gmv[r], btv[r]);
+                    va[dt][r] = (!STRAIGHT || live) ? na : 0.f;
+                    vb[dt][r] = (!STRAIGHT || live) ? nb : 0.f;
+                }
             } else {
                 va[dt] = f4zero();
                 vb[dt] = f4zero();
@@ -495,13 +546,19 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
     auto write_xfrags = [&](int tile, const f32x4 (&v)[DT]) {
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-            const int d0 = 16 * dt + 4 * g;
+            const int d0 = 16 * dt + 4 * (STRAIGHT ? (g & 3) : g);
+            const bool live = row_live(dt);
+            const unsigned one = (d0 == D) ? 0x00003F80u : 0u;      // bf16(1.0) in the low half
             u32x2 pk;
-            if (d0 < D) {
+            if constexpr (STRAIGHT) {
+                const unsigned p0 = cvt_pk_bf16(v[dt][0], v[dt][1]), p1 = cvt_pk_bf16(v[dt][2], v[dt][3]);
+                pk[0] = live ? p0 : one;
+                pk[1] = live ? p1 : 0u;
+            } else if (live) {
                 pk[0] = cvt_pk_bf16(v[dt][0], v[dt][1]);
                 pk[1] = cvt_pk_bf16(v[dt][2], v[dt][3]);
             } else {
-                pk[0] = (d0 == D) ? 0x00003F80u : 0u;      // bf16(1.0) in the low half
+                pk[0] = one;
                 pk[1] = 0u;
             }
             const int ks = dt >> 1, gd = 2 * (dt & 1) + (g >> 1);
@@ -591,15 +648,16 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                 }
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
-                    const int d0 = 16 * dt + 4 * g;
-                    if (d0 < D) {
+                    const bool live = row_live(dt);
+                    if (STRAIGHT || live) {
+                        const int dr = STRAIGHT ? row_clamped(dt) : 16 * dt + 4 * g;
                         const int tc = (t < T) ? t : T - 1;
-                        const float4 pe = *reinterpret_cast<const float4*>(P.params + P.pos + (size_t)tc * D + d0);
-                        const float4 te = *reinterpret_cast<const float4*>(temb + ser * D + d0);
-                        acc[dt][0] += pe.x + te.x;
-                        acc[dt][1] += pe.y + te.y;
-                        acc[dt][2] += pe.z + te.z;
-                        acc[dt][3] += pe.w + te.w;
+                        const float4 pe = *reinterpret_cast<const float4*>(P.params + P.pos + (size_t)tc * D + dr);
+                        const float4 te = *reinterpret_cast<const float4*>(temb + ser * D + dr);
+                        acc[dt][0] = (!STRAIGHT || live) ? acc[dt][0] + (pe.x + te.x) : 0.f;
+                        acc[dt][1] = (!STRAIGHT || live) ? acc[dt][1] + (pe.y + te.y) : 0.f;
+                        acc[dt][2] = (!STRAIGHT || live) ? acc[dt][2] + (pe.z + te.z) : 0.f;
+                        acc[dt][3] = (!STRAIGHT || live) ? acc[dt][3] + (pe.w + te.w) : 0.f;
                     } else {
                         acc[dt] = f4zero();
                     }
@@ -1297,9 +1355,11 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                     wo[dt][ks] = WO_LDS ? *reinterpret_cast<const bf16x8*>(wsl + ((dt * KSO + ks) * 64 + lane) * 16)
                                         : gfrag(limg + P.off_wo, dt * KSO + ks);
             {
-                // Both owned tiles in ONE basic block (a wave that owns a single tile runs its first tile twice and skips the
+                // Both owned tiles in one chain (a wave that owns a single tile runs its first tile twice and skips the
                 // second write): behind a `tt < ntile` branch each tile's out-proj -> residual -> LayerNorm -> fragment chain
-                // ran strictly after the other's (2.9 K cycles per tile in the sub-phase marks, no latency hidden).
+                // ran strictly after the other's (2.9 K cycles per tile in the sub-phase marks, no latency hidden).  It is ONE
+                // basic block up to the wave-uniform branches around the two fragment writes in the STRAIGHT form only; the
+                // guarded form has an exec-mask region per feature guard (53 of them in the benched kernel before STRAIGHT).
                 bool ok[2];
                 int tl[2];
 #pragma unroll
@@ -1325,9 +1385,10 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                 for (int oi = 0; oi < 2; ++oi)
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) {
-                        const int d0 = 16 * dt + 4 * g;
-                        if (d0 < D) {
-                            const float4 bo = *reinterpret_cast<const float4*>(lpar + 0 * D + d0);
+                        // (STRAIGHT) rows past D take a finite value from the clamped bias row: layer_norm2 keeps them out of its sums
+                        // and zeroes them
+                        if (STRAIGHT || row_live(dt)) {
+                            const float4 bo = *reinterpret_cast<const float4*>(lpar + 0 * D + (STRAIGHT ? row_clamped(dt) : 16 * dt + 4 * g));
                             res[oi][dt][0] += acc[oi][dt][0] + bo.x;
                             res[oi][dt][1] += acc[oi][dt][1] + bo.y;
                             res[oi][dt][2] += acc[oi][dt][2] + bo.z;
@@ -1733,7 +1794,8 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                     }
                 __syncthreads();
                 {
-                    // both owned tiles in one basic block (see the out-proj phase): a missing second tile is computed from the
+                    // both owned tiles in one chain (see the out-proj phase; one basic block in the STRAIGHT form, where hipcc also
+                    // issues the LDS reads of `other` ahead of their first use): a missing second tile is computed from the
                     // first one's operands and zeroed afterwards
                     bool okc[2];
 #pragma unroll
@@ -1743,10 +1805,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                         const int tts = okc[oi] ? ttc : FH;          // (tile FH of the quarter always exists when ntile > FH)
 #pragma unroll
                         for (int dt = 0; dt < DT; ++dt) {
-                            const int d0 = 16 * dt + 4 * g;
                             // every path below overwrites res[oi] completely: a partial / conditional update would
                             // keep the pre-FFN residual live across the whole loop (it cost 32 spilled registers)
-                            const int dr = (d0 < D) ? d0 : 0;
+                            const int dr = STRAIGHT ? row_clamped(dt) : (row_live(dt) ? 16 * dt + 4 * g : 0);
                             const f32x4 mine = acc[dt][ttc < MT ? ttc : 0];          // already contains the residual
                             const f32x4 other = xch[((mq * MT + tts) * DT + dt) * 64 + lane];
                             const float4 b2 = *reinterpret_cast<const float4*>(lpar + 1 * D + dr);
