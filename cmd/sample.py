@@ -20,7 +20,7 @@ import yaml  # noqa: E402
 
 from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
-from fourierdiffusion_amd.sampling.sampler import parse_labels  # noqa: E402
+from fourierdiffusion_amd.sampling.sampler import parse_covariates, parse_labels  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, env, init_process_group, shard_range  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
 from fourierdiffusion_amd.utils.fourier import destandardize_idft, idft  # noqa: E402
@@ -82,10 +82,16 @@ class SamplingRunner:
         num_batches = max(1, self.num_samples // bs)
         lo, hi = shard_range(num_batches, self.dist.rank, self.dist.world)       # independent units: no exchange
         n_local = (hi - lo) * min(bs, self.num_samples)
-        X = labels = None
+        X = labels = covariates = None
         if n_local:
             guide = {}
-            if self.score_model.n_classes > 0 or self.sampler.labels is not None or self.sampler.cfg_scale != 1.0:
+            cond_dim = int(getattr(self.score_model, "cond_dim", 0))
+            spec = getattr(self.sampler, "covariates", None)
+            if cond_dim > 0 or spec is not None:
+                # sampler.covariates: `data`, a list in data units or null; the rows used (model units) are written next to the samples
+                covariates = parse_covariates(spec, n_local, cond_dim, self.datamodule)
+                guide = {"y": covariates, "cfg_scale": self.sampler.cfg_scale}
+            elif self.score_model.n_classes > 0 or self.sampler.labels is not None or self.sampler.cfg_scale != 1.0:
                 # sampler.labels: a class, `balanced` or null; the chosen labels are written next to the samples
                 labels = parse_labels(self.sampler.labels, n_local, self.score_model.n_classes)
                 guide = {"y": labels, "cfg_scale": self.sampler.cfg_scale}
@@ -102,8 +108,10 @@ class SamplingRunner:
         if self.dist.world > 1:
             import torch.distributed as dist
             parts = [None] * self.dist.world
-            dist.all_gather_object(parts, (X, labels))                              # host-side gather of the results
+            dist.all_gather_object(parts, (X, labels, covariates))                  # host-side gather of the results
             X = torch.cat([p[0] for p in parts if p[0] is not None], dim=0)
+            cov = [p[2] for p in parts if p[0] is not None]
+            covariates = torch.cat(cov, dim=0) if cov and all(v is not None for v in cov) else None
             lab = [p[1] for p in parts if p[0] is not None]
             labels = torch.cat(lab, dim=0) if lab and all(v is not None for v in lab) else None
         if self.dist.is_main:
@@ -116,6 +124,8 @@ class SamplingRunner:
             torch.save(X, self.save_dir / "samples.pt")
             if labels is not None:
                 torch.save(labels, self.save_dir / "labels.pt")
+            if covariates is not None:
+                torch.save(covariates, self.save_dir / "covariates.pt")
 
 
 def main(argv=None) -> None:

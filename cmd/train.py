@@ -40,6 +40,24 @@ def check_labels(score_model, datamodule) -> None:
                          f"score_model.n_classes={hi + 1}")
 
 
+def check_covariates(score_model, datamodule) -> None:
+    """A covariate-conditional model needs a datamodule whose y is a float (n, cond_dim) tensor: fail before the first step."""
+    P = int(getattr(score_model, "cond_dim", 0))
+    if P <= 0:
+        return
+    y = getattr(datamodule, "y_train", None)
+    name = type(datamodule).__name__
+    if y is None:
+        raise ValueError(f"score_model.cond_dim = {P}, but {name} has no covariates (y_train is None): use a datamodule with float "
+                         "covariates (datamodule=synthetic_covariates) or score_model.cond_dim=0")
+    y = torch.as_tensor(y)
+    if not y.is_floating_point():
+        raise ValueError(f"score_model.cond_dim = {P}, but y_train of {name} holds {y.dtype}, not floats: integer classes belong to "
+                         "score_model=conditional (n_classes)")
+    if y.dim() != 2 or y.shape[1] != P:
+        raise ValueError(f"score_model.cond_dim = {P}, but y_train of {name} has shape {tuple(y.shape)}, not (n, {P})")
+
+
 class TrainingRunner:
     def __init__(self, cfg) -> None:
         torch.manual_seed(cfg.random_seed)
@@ -59,6 +77,7 @@ class TrainingRunner:
         if isinstance(self.score_model, partial):
             self.score_model = self.score_model(**get_training_params(self.datamodule, self.trainer))
         check_labels(self.score_model, self.datamodule)
+        check_covariates(self.score_model, self.datamodule)
         for callback in self.trainer.callbacks:
             if isinstance(callback, SamplingCallback):
                 callback.setup_datamodule(datamodule=self.datamodule)

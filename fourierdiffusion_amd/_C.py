@@ -90,6 +90,16 @@ _PROTOS = {
     "fd_score_get_labels": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
     "fd_score_set_label_dropout": (C.c_int, [_vp, C.c_float]),
     "fd_label_dropout": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _vp]),
+    "fd_score_layout_cov": (C.c_int, [C.POINTER(ModelDims), C.c_int, C.c_int, C.POINTER(ParamEntry), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int64)]),
+    "fd_score_create_cov": (C.c_int, [_vp, C.POINTER(ModelDims), C.c_int, C.c_int, C.POINTER(_vp)]),
+    "fd_score_set_covariates": (C.c_int, [_vp, _vp, C.c_int]),
+    "fd_score_get_covariates": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
+    "fd_score_set_cov_dropout": (C.c_int, [_vp, C.c_float]),
+    "fd_cov_dropout": (C.c_int, [_vp, _vp, C.c_int, C.c_float, C.c_uint64, C.c_uint64, _vp]),
+    "fd_cov_embed": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "fd_cov_embed_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        _vp]),
     "fd_score_prepare": (C.c_int, [_vp, _vp, _vp]),
     "fd_score_rebind": (C.c_int, [_vp, _vp]),
     "fd_score_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
@@ -167,6 +177,10 @@ _PROTOS = {
     "fd_sampler_run_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, C.c_float, _vp,
                                      C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_int, C.c_int,
+                                         _vp]),
+    "fd_sampler_run_cov": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_float, _vp, _vp, C.c_float, _vp,
+                                     C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_ode_cov": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_int, C.c_int,
                                          _vp]),
     "fd_prior_logp": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
@@ -307,11 +321,16 @@ def model_dims(n_channels, max_len, d_model, n_head, num_layers, dim_ff=2048) ->
     return ModelDims(int(n_channels), int(max_len), int(d_model), int(n_head), int(num_layers), int(dim_ff))
 
 
-def score_layout(dims: ModelDims, backbone: int = 0, d_mlp: int = 0, n_classes: int = 0):
+def score_layout(dims: ModelDims, backbone: int = 0, d_mlp: int = 0, n_classes: int = 0, cond_dim: int = 0):
     """[(name, offset, numel, shape, trainable)] + total float count, straight from the engine.  n_classes > 0 (transformer only):
-    the class-conditional layout, one trailing ``class_encoder.weight``."""
+    the class-conditional layout, one trailing ``class_encoder.weight``.  cond_dim > 0 (transformer only, never with classes): the
+    covariate layout, five trailing ``cov_encoder.*`` tensors."""
     n = C.c_int(0)
-    if n_classes > 0:
+    total_cov = C.c_int64(0)
+    if cond_dim > 0:
+        def layout(arr):
+            return lib().fd_score_layout_cov(C.byref(dims), int(n_classes), int(cond_dim), arr, C.byref(n), C.byref(total_cov))
+    elif n_classes > 0:
         def layout(arr):
             return lib().fd_score_layout_cond(C.byref(dims), int(n_classes), arr, C.byref(n))
     else:
@@ -329,7 +348,9 @@ def score_layout(dims: ModelDims, backbone: int = 0, d_mlp: int = 0, n_classes: 
     for e in arr:
         shape = (e.rows, e.cols) if e.cols else (e.rows,)
         out.append((e.name.decode(), int(e.offset), int(e.numel), shape, bool(e.trainable)))
-    if n_classes > 0:
+    if cond_dim > 0:
+        total = int(total_cov.value)
+    elif n_classes > 0:
         total = int(lib().fd_score_param_count_cond(C.byref(dims), int(n_classes)))
     else:
         total = int(lib().fd_score_param_count_ex(C.byref(dims), backbone, d_mlp))

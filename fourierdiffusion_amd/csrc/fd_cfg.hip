@@ -121,7 +121,7 @@ int cfg_check(fd_score* m, const void* G, const void* timesteps, const void* x, 
 int fd_labels_check(fd_score* m, int B, const char* who) {
     if (m->labels && m->labels_B != B)
         return fd_fail(m->ctx, FD_ERR_ARG, "%s: B=%d, but labels are bound for B=%d (fd_score_set_labels)", who, B, m->labels_B);
-    return FD_OK;
+    return fd_cov_check(m, B, who);
 }
 
 int fd_labels_prepare_train(fd_score* m, int B, uint64_t seed, uint64_t offset, hipStream_t s) {
@@ -213,10 +213,17 @@ int fd_guide_check(fd_score* m, float w, const char* who) {
     return FD_OK;
 }
 
-int fd_guide_begin(fd_score* m, const fd_guide* g, int* lab, float* x, int B, hipStream_t s) {
+// fd_cov.hip: the pair's covariates and keep bytes
+int fd_guide_begin_cov(fd_score* m, const fd_guide* g, void* own, int B, hipStream_t s);
+
+int fd_guide_begin(fd_score* m, const fd_guide* g, void* lab, float* x, int B, hipStream_t s) {
     if (!g || !g->pair) return FD_OK;
     const size_t n = (size_t)B * m->d.max_len * m->d.n_channels;
-    hipLaunchKernelGGL(k_cfg_labels, dim3((2 * B + kBlock - 1) / kBlock), dim3(kBlock), 0, s, g->y, lab, B, m->n_classes);
+    if (g->P > 0) {
+        if (int rc = fd_guide_begin_cov(m, g, lab, B, s)) return rc;
+    } else {
+        hipLaunchKernelGGL(k_cfg_labels, dim3((2 * B + kBlock - 1) / kBlock), dim3(kBlock), 0, s, g->y, (int*)lab, B, m->n_classes);
+    }
     FD_HIP(m->ctx, hipMemcpyAsync(x + n, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return FD_OK;
 }

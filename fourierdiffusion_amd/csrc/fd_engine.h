@@ -32,12 +32,19 @@ struct fd_train_mode_scope {
 };
 
 // The same for label dropout: the training forwards of an evaluation loop (fd_dps.hip, fd_likelihood.hip) read the bound labels as
-// they are -- fd_labels_prepare_train draws a model's label_dropout on every training forward otherwise
+// they are -- fd_labels_prepare_train draws a model's label_dropout on every training forward otherwise; covariate dropout
+// (fd_cov_prepare_train) likewise
 struct fd_label_dropout_scope {
     fd_score* m;
-    float saved;
-    fd_label_dropout_scope(fd_score* mm, float p) : m(mm), saved(mm->label_dropout) { m->label_dropout = p; }
-    ~fd_label_dropout_scope() { m->label_dropout = saved; }
+    float saved, saved_cov;
+    fd_label_dropout_scope(fd_score* mm, float p) : m(mm), saved(mm->label_dropout), saved_cov(mm->cov_dropout) {
+        m->label_dropout = p;
+        m->cov_dropout = p;
+    }
+    ~fd_label_dropout_scope() {
+        m->label_dropout = saved;
+        m->cov_dropout = saved_cov;
+    }
 };
 
 // the training arithmetic of an evaluation that differentiates the network: bf16 where the model has the bf16 training kernels

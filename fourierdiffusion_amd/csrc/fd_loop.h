@@ -40,35 +40,59 @@ int fd_step_loop_eval(fd_step_loop* lp, int k, const float* x);
 // Classifier-free guidance of a plain loop (fd_cfg.hip); a null guide is the plain loop.  pair: the two evaluations of a step run as one
 // forward on 2B rows, x (2B,T,C) holds the state twice and the step kernel combines the halves of the score; else one evaluation on B
 // rows with the labels y bound (null: the null token on every row).
+// A covariate guide (fd_cov.hip, fd_guide_plan_cov) carries c (B, P) in place of y: P > 0, y null.
 struct fd_guide {
     bool pair;
     const int* y;           // device int32[B]
     float w, omw;           // the guidance scale and 1 - w
+    const float* c = nullptr;      // device float[B, P]
+    int P = 0;
 };
 // What a guided loop runs (fd_cfg.hip): pair = labels present and w outside {0, 1}, or FDIFF_CFG_FORCE_PAIR; else one evaluation on B
 // rows with y bound (w = 0 or y null: the null token on every row)
 fd_guide fd_guide_plan(const int* y, float w);
+// the same for covariates c (B, P): pair = covariates present and w outside {0, 1}, or FDIFF_CFG_FORCE_PAIR
+fd_guide fd_guide_plan_cov(const float* c, int P, float w);
 // the checks of every guided entry point: a class-conditional model (FD_ERR_ARG otherwise) and a finite guidance scale
 int fd_guide_check(fd_score* m, float w, const char* who);
 inline int fd_guide_rows(const fd_guide* g, int B) { return g && g->pair ? 2 * B : B; }
-// the label vector of the paired forward, the last of the loop's own buffers
-inline size_t fd_guide_bytes(const fd_guide* g, int B) { return g && g->pair ? fd_ws::padded((size_t)2 * B * sizeof(int)) : 0; }
-// pair: lab[0 .. 2B) = (y, null tokens) and x[B .. 2B) = x[0 .. B); no-op otherwise
-int fd_guide_begin(fd_score* m, const fd_guide* g, int* lab, float* x, int B, hipStream_t s);
+// the label vector of the paired forward, the last of the loop's own buffers; a covariate guide: the pair's covariates (2B, P), then
+// its 2B keep bytes
+inline size_t fd_guide_cov_bytes(const fd_guide* g, int B) { return fd_ws::padded((size_t)2 * B * g->P * sizeof(float)); }
+inline size_t fd_guide_bytes(const fd_guide* g, int B) {
+    if (!g || !g->pair) return 0;
+    return g->P > 0 ? fd_guide_cov_bytes(g, B) + fd_ws::padded((size_t)2 * B) : fd_ws::padded((size_t)2 * B * sizeof(int));
+}
+// pair: lab[0 .. 2B) = (y, null tokens) -- a covariate guide: (c, c) and the keep bytes [1 .. 1 ; 0 .. 0] -- and x[B .. 2B) =
+// x[0 .. B); no-op otherwise
+int fd_guide_begin(fd_score* m, const fd_guide* g, void* lab, float* x, int B, hipStream_t s);
 // binds a guided loop's labels for its forwards; the caller's binding is back when the scope ends (the kernels have taken their
 // pointers at launch)
 struct fd_guide_scope {
     fd_score* m;
     const int* y;
     int B;
-    fd_guide_scope(fd_score* mm, const fd_guide* g, const int* lab, int rows) : m(mm), y(mm->labels), B(mm->labels_B) {
+    const float* c;
+    const unsigned char* keep;
+    int cB;
+    fd_guide_scope(fd_score* mm, const fd_guide* g, const void* lab, int rows)
+        : m(mm), y(mm->labels), B(mm->labels_B), c(mm->cov), keep(mm->cov_keep), cB(mm->cov_B) {
         if (!g) return;
-        m->labels = g->pair ? lab : g->y;
+        if (g->P > 0) {
+            m->cov = g->pair ? (const float*)lab : g->c;
+            m->cov_keep = g->pair ? (const unsigned char*)lab + fd_guide_cov_bytes(g, rows / 2) : nullptr;
+            m->cov_B = m->cov ? rows : 0;
+            return;
+        }
+        m->labels = g->pair ? (const int*)lab : g->y;
         m->labels_B = m->labels ? rows : 0;
     }
     ~fd_guide_scope() {
         m->labels = y;
         m->labels_B = B;
+        m->cov = c;
+        m->cov_keep = keep;
+        m->cov_B = cB;
     }
 };
 // the guided score of one element; the intrinsics keep the two products and the sum from being contracted into an fma

@@ -60,19 +60,51 @@ struct fd_score {
     float label_dropout = 0.f;      // training forwards replace a label by the null token with this probability (fd_score_set_label_dropout)
     int* y_eff = nullptr;           // engine-owned device int32[y_eff_cap]: the labels the last training forward really used
     int y_eff_cap = 0;
+    // ---- covariate conditioning (fd_score_create_cov, fd_cov.hip; not in the reference): a two-layer encoder of a float vector
+    // c_b (cond_dim), e(c) = W2 silu(W1 c + b1) + b2, and a learned null vector, the LAST five tensors of the layout; k_cov_embed adds
+    // e(c_b) or the null vector to the time embedding of series b.  cond_dim == 0: no covariates.  Never together with n_classes > 0.
+    int cond_dim = 0;
+    int64_t cov_w1 = 0, cov_b1 = 0, cov_w2 = 0, cov_b2 = 0, cov_null = 0;
+    const float* cov = nullptr;     // borrowed device float[cov_B, cond_dim] (fd_score_set_covariates), or null: every row reads the null vector
+    int cov_B = 0;
+    const unsigned char* cov_keep = nullptr;   // borrowed keep bytes of the bound rows (a guided pair's [1..1 ; 0..0]), or null: all kept
+    float cov_dropout = 0.f;        // training forwards read the null vector with this probability per row (fd_score_set_cov_dropout)
+    // engine-owned, grow-only: what the last training forward really used (its backward reads them again) and the encoder
+    // gradient's (h, dpre) rows
+    float* cov_eff = nullptr;       // float[cov_eff_cap, cond_dim]: copy of the bound covariates
+    unsigned char* keep_eff = nullptr;   // cov_eff_cap keep bytes behind covariate dropout
+    int cov_eff_cap = 0;
+    bool cov_eff_bound = false;     // covariates were bound at that forward (else every row read the null vector)
+    float* cov_bwd = nullptr;       // float[2, cov_bwd_cap, d_model]
+    int cov_bwd_cap = 0;
 };
 
 // the class-embedding operands of k_time_embed: y (B) int32 or null (every row the null token), table (K + 1, D) fp32; table == null:
 // an unlabelled model, nothing is added
+// the covariate operands of k_cov_embed, launched behind k_time_embed when P > 0: c (B, P) or null (every row the null vector), keep
+// (B) bytes or null (every row kept), the encoder's five tensors
+struct fd_cov {
+    const float* c = nullptr;
+    const unsigned char* keep = nullptr;
+    const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *nul = nullptr;
+    int P = 0;
+};
 struct fd_cls {
     const int* y = nullptr;
     const float* table = nullptr;
     int K = 0;
+    fd_cov cov{};
 };
-inline fd_cls fd_cls_eval(const fd_score* m) {      // the labels bound by fd_score_set_labels
+inline fd_cov fd_cov_of(const fd_score* m, const float* c, const unsigned char* keep) {
+    const float* P = m->params;
+    return fd_cov{c, keep, P + m->cov_w1, P + m->cov_b1, P + m->cov_w2, P + m->cov_b2, P + m->cov_null, m->cond_dim};
+}
+inline fd_cls fd_cls_eval(const fd_score* m) {      // the labels bound by fd_score_set_labels / the covariates by fd_score_set_covariates
+    if (m->cond_dim > 0) return fd_cls{nullptr, nullptr, 0, fd_cov_of(m, m->cov, m->cov_keep)};
     return m->n_classes > 0 ? fd_cls{m->labels, m->params + m->cls_w, m->n_classes} : fd_cls{};
 }
-inline fd_cls fd_cls_train(const fd_score* m) {     // the labels behind label dropout (fd_labels_prepare_train)
+inline fd_cls fd_cls_train(const fd_score* m) {     // the labels behind label dropout (fd_labels_prepare_train) / covariates (fd_cov_prepare_train)
+    if (m->cond_dim > 0) return fd_cls{nullptr, nullptr, 0, fd_cov_of(m, m->cov_eff_bound ? m->cov_eff : nullptr, m->keep_eff)};
     return m->n_classes > 0 ? fd_cls{m->y_eff, m->params + m->cls_w, m->n_classes} : fd_cls{};
 }
 // Philox counters of label dropout under the training call's (seed, offset): label b is lane b % 4 of counter offset + kLabelCtrBase
@@ -109,6 +141,19 @@ int fd_labels_prepare_train(fd_score* m, int B, uint64_t seed, uint64_t offset, 
 // d class_encoder.weight[k, :] (+)= sum over the rows b with y_eff[b] == k of dtemb[b, :], b ascending (no atomics); no-op when unlabelled
 int fd_class_table_backward(fd_score* m, const float* dtemb, float* grads, int B, int accumulate, hipStream_t s);
 void fd_labels_destroy(fd_score* m);
+
+// fd_cov.hip: covariate conditioning (not in the reference)
+constexpr int kMaxCondDim = 64;
+// temb[b, :] += keep_b ? e(c_b) : null, one workgroup per row behind k_time_embed; no-op when cov.P == 0
+void fd_cov_embed_launch(const fd_cov& cov, float* temb, int B, int D, hipStream_t s);
+// FD_ERR_ARG when covariates are bound for another batch size than B
+int fd_cov_check(fd_score* m, int B, const char* who);
+// a covariate model's training forward: copies the bound covariates and draws the keep bytes of covariate dropout from
+// Philox(seed, offset + kLabelCtrBase), the lane rule of k_label_dropout; a no-op on any other model
+int fd_cov_prepare_train(fd_score* m, int B, uint64_t seed, uint64_t offset, hipStream_t s);
+// the encoder's gradient from dtemb (B, D) of the last training forward: b ascending, no atomics; no-op without covariates
+int fd_cov_backward(fd_score* m, const float* dtemb, float* grads, int B, int accumulate, hipStream_t s);
+void fd_cov_destroy(fd_score* m);
 
 // fd_score_f32.hip
 namespace fdf32 {

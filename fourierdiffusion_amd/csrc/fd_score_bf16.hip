@@ -1174,7 +1174,7 @@ static MegaPlan plan_mega(const fd_score* m, int B) {
     if (!im || !im->mega) return MegaPlan{};
     // a class-conditional model's time embedding differs per series; the persistent kernel shares one per step (temb_table): not ok,
     // so that its forward takes the per-layer kernels and every loop runs step by step
-    if (m->n_classes > 0) return MegaPlan{};
+    if (m->n_classes > 0 || m->cond_dim > 0) return MegaPlan{};      // (covariates: e(c_b) per series, fd_cov.hip)
     return plan_mega_nw(m, B, 8);
 }
 
@@ -1643,7 +1643,7 @@ static int run_layers(fd_score* m, const std::vector<Row>& rows, const float* G,
     fd_ctx* ctx = m->ctx;
     const fd_bf16_images* im = m->bf16;
     if (!im || !im->supported || !im->mega || getenv("FDIFF_SAMPLER_UNFUSED_STEP")) return FD_ERR_UNSUPPORTED;
-    if (m->n_classes > 0) return FD_ERR_UNSUPPORTED;      // (k_unembed_step_embed shares one time embedding per step, as the persistent kernel)
+    if (m->n_classes > 0 || m->cond_dim > 0) return FD_ERR_UNSUPPORTED;      // (k_unembed_step_embed shares one time embedding per step, as the persistent kernel)
     const bool k35 = im->ks1 == 3 && im->dt == 5, k24 = im->ks1 == 2 && im->dt == 4, k12 = im->ks1 == 1 && im->dt == 2,
                k11 = im->ks1 == 1 && im->dt == 1;
     if (!(k35 || k24 || k12 || k11) || m->d.n_channels > 40 || m->d.d_model % 4 != 0) return FD_ERR_UNSUPPORTED;
@@ -1866,7 +1866,9 @@ extern "C" int fd_score_plan(fd_score* m, int B, int mode, char* out /* >= 192 b
         return FD_OK;
     }
     if (mode == FD_MODE_F32) {
-        snprintf(out, 192, "fp32 parity path (per-op kernels, fd_score_f32.hip)%s", m->n_classes > 0 ? "; class-conditional" : "");
+        char cov[48] = "";
+        if (m->cond_dim > 0) snprintf(cov, sizeof cov, "; covariate-conditional (%d)", m->cond_dim);
+        snprintf(out, 192, "fp32 parity path (per-op kernels, fd_score_f32.hip)%s%s", m->n_classes > 0 ? "; class-conditional" : "", cov);
         return FD_OK;
     }
     FD_REQUIRE(ctx, mode == FD_MODE_BF16, "fd_score_plan: unknown mode %d", mode);
@@ -1884,6 +1886,7 @@ extern "C" int fd_score_plan(fd_score* m, int B, int mode, char* out /* >= 192 b
         const bool fuse = im->mega && im->kso == 3 && (im->ks1 == 3 || im->ks1 == 2);
         char cls[48] = "";
         if (m->n_classes > 0) snprintf(cls, sizeof cls, "; class-conditional (%d classes)", m->n_classes);
+        if (m->cond_dim > 0) snprintf(cls, sizeof cls, "; covariate-conditional (%d)", m->cond_dim);
         snprintf(out, 192, "per-layer bf16 kernels (k_attention_bf16 + k_ffn_ln): attention %s, k_ffn_ln<%d,%d>%s%s",
                  hd > 32 ? "exact-f32 kernel (head_dim > 32) on bf16-MFMA projections"
                  : hd > 7 ? "bf16 k_attention_wide (one head per contraction) on bf16-MFMA projections"

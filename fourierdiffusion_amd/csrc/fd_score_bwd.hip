@@ -713,6 +713,7 @@ extern "C" int fd_score_backward(fd_score* m, const float* dout, float* grads, i
 
     if (int rc = fd_embed_backward(m, dh, sv.emb, dtemb, grads, B, skp, kSplitKFloats, s)) return rc;
     if (int rc = fd_class_table_backward(m, dtemb, grads, B, accumulate, s)) return rc;
+    if (int rc = fd_cov_backward(m, dtemb, grads, B, accumulate, s)) return rc;
     FD_LAUNCH_CHECK(ctx);
     return fd_take_deferred(ctx);
 }

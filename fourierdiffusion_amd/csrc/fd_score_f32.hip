@@ -38,7 +38,7 @@ struct LayoutBuilder {
 };
 
 int64_t build_layout(const fd_model_dims& d, fd_score* m, std::vector<fd_param_entry>* entries, int backbone = 0, int d_mlp = 0,
-                     int n_classes = 0) {
+                     int n_classes = 0, int cond_dim = 0) {
     LayoutBuilder lb;
     lb.out = entries;
     const int D = d.d_model, C = d.n_channels, T = d.max_len, F = d.dim_ff;
@@ -99,6 +99,16 @@ int64_t build_layout(const fd_model_dims& d, fd_score* m, std::vector<fd_param_e
     if (n_classes > 0) {
         const int64_t cls = lb.add("class_encoder.weight", n_classes + 1, D);
         if (m) { m->cls_w = cls; m->n_classes = n_classes; }
+    }
+    // covariate conditioning (not in the reference): the encoder e(c) = W2 silu(W1 c + b1) + b2 and its null vector, behind every
+    // other tensor as well (never together with a class table)
+    if (cond_dim > 0) {
+        const int64_t w1 = lb.add("cov_encoder.0.weight", D, cond_dim);
+        const int64_t b1 = lb.add("cov_encoder.0.bias", D, 0);
+        const int64_t w2 = lb.add("cov_encoder.2.weight", D, D);
+        const int64_t b2 = lb.add("cov_encoder.2.bias", D, 0);
+        const int64_t nul = lb.add("cov_encoder.null", D, 0);
+        if (m) { m->cov_w1 = w1; m->cov_b1 = b1; m->cov_w2 = w2; m->cov_b2 = b2; m->cov_null = nul; m->cond_dim = cond_dim; }
     }
     return lb.off;
 }
@@ -180,6 +190,35 @@ extern "C" int fd_score_create_cond(fd_ctx* ctx, const fd_model_dims* dims, int 
     return FD_OK;
 }
 
+// The covariate-conditional forms (include/fdiff_hip.h): transformer backbone, cond_dim in [0, 64] (0: the unlabelled layout, bit for
+// bit), never together with classes
+extern "C" int fd_score_layout_cov(const fd_model_dims* dims, int n_classes, int cond_dim, fd_param_entry* entries, int* n_entries,
+                                   int64_t* n_params) {
+    if (!dims_ok(dims) || !n_entries || n_classes < 0 || n_classes > kMaxClasses || cond_dim < 0 || cond_dim > kMaxCondDim ||
+        (n_classes > 0 && cond_dim > 0))
+        return FD_ERR_ARG;
+    std::vector<fd_param_entry> v;
+    const int64_t total = build_layout(*dims, nullptr, &v, FD_BACKBONE_TRANSFORMER, 0, n_classes, cond_dim);
+    if (entries) {
+        if (*n_entries < (int)v.size()) return FD_ERR_ARG;
+        memcpy(entries, v.data(), v.size() * sizeof(fd_param_entry));
+    }
+    *n_entries = (int)v.size();
+    if (n_params) *n_params = total;
+    return FD_OK;
+}
+
+extern "C" int fd_score_create_cov(fd_ctx* ctx, const fd_model_dims* dims, int n_classes, int cond_dim, fd_score** out) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, n_classes >= 0 && n_classes <= kMaxClasses, "fd_score_create_cov: n_classes=%d", n_classes);
+    FD_REQUIRE(ctx, cond_dim >= 0 && cond_dim <= kMaxCondDim, "fd_score_create_cov: cond_dim=%d (0 .. %d)", cond_dim, kMaxCondDim);
+    FD_REQUIRE(ctx, !(n_classes > 0 && cond_dim > 0), "fd_score_create_cov: n_classes=%d together with cond_dim=%d is not built",
+               n_classes, cond_dim);
+    if (int rc = fd_score_create_ex(ctx, dims, FD_BACKBONE_TRANSFORMER, 0, out)) return rc;
+    (*out)->nparams = build_layout(*dims, *out, nullptr, FD_BACKBONE_TRANSFORMER, 0, n_classes, cond_dim);
+    return FD_OK;
+}
+
 extern "C" int fd_score_create_ex(fd_ctx* ctx, const fd_model_dims* dims, int backbone, int d_mlp, fd_score** out) {
     if (!ctx) return FD_ERR_ARG;
     FD_REQUIRE(ctx, out != nullptr, "fd_score_create: null out");
@@ -215,6 +254,7 @@ extern "C" int fd_score_destroy(fd_score* m) {
     if (!m) return FD_ERR_ARG;
     fd_bf16_destroy(m);
     fd_labels_destroy(m);
+    fd_cov_destroy(m);
     if (m->prep_event) (void)hipEventDestroy(m->prep_event);
     if (m->img_event) (void)hipEventDestroy(m->img_event);
     delete m;
@@ -581,6 +621,7 @@ void time_embed_cls(const float* t, const float* W, const float* Wd, const float
                     fd_cls cls) {
     hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, (float*)nullptr, temb, D, cls.y, cls.table,
                        cls.K);
+    if (cls.cov.P > 0) fd_cov_embed_launch(cls.cov, temb, B, D, s);
 }
 // The weights-in-registers form for a channel count that is not a multiple of four (the reference's datasets: 1, 5, 13 channels;
 // BASELINE nasdaq: 6): scalar loads of the 4 x C weight slice and of the row's x, the same fma order over c -- bit-identical to
@@ -761,8 +802,7 @@ int fd_score_forward_f32(fd_score* m, const float* x, const float* t, float* out
     }
 
     const fd_cls cls = train ? fd_cls_train(m) : fd_cls_eval(m);
-    hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, P + m->tW, P + m->td_w,
-                       P + m->td_b, sv.emb, sv.temb, D, cls.y, cls.table, cls.K);
+    (void)fd_time_embed_train_cls(t, P + m->tW, P + m->td_w, P + m->td_b, sv.emb, sv.temb, B, D, s, cls);
     float* h_in = (L > 0) ? (train ? sv.layers[0].x0 : scratch.x0) : sv.hL;
     fdf32::embed(x, P + m->emb_w, P + m->emb_b, P + m->pos, sv.temb, h_in, M, T, C, D, s);
     for (int i = 0; i < L; ++i) {
@@ -878,6 +918,7 @@ extern "C" int fd_score_forward_train(fd_score* m, const float* x, const float* 
                        "max_len <= 1024); select FD_MODE_F32");
     if (int rc = fd_labels_check(m, B, "fd_score_forward_train")) return rc;
     if (int rc = fd_labels_prepare_train(m, B, seed, offset, (hipStream_t)stream)) return rc;
+    if (int rc = fd_cov_prepare_train(m, B, seed, offset, (hipStream_t)stream)) return rc;
     ++ctx->tr_fwd_serial;               // (whatever the flags of an earlier persistent forward said is history: fd_score_train_cluster_xcds)
     int rc = (m->backbone != FD_BACKBONE_TRANSFORMER)
                  ? fd_bb_forward(m, x, t, out, B, (hipStream_t)stream, true, dropout_p, seed, offset)
@@ -914,6 +955,7 @@ extern "C" int fd_score_train_dsm(fd_score* m, const float* x, const float* t, c
         return fd_fail(ctx, FD_ERR_UNSUPPORTED, "fd_score_train_dsm: the fused step exists on the bf16 transformer training path only");
     if (int rc = fd_labels_check(m, B, "fd_score_train_dsm")) return rc;
     if (int rc = fd_labels_prepare_train(m, B, seed, offset, (hipStream_t)stream)) return rc;
+    if (int rc = fd_cov_prepare_train(m, B, seed, offset, (hipStream_t)stream)) return rc;
     return fd_score_train_dsm_bf16(m, x, t, target, std, likelihood_weighting, grad_weight, B, dropout_p, seed, offset, loss_out, grads,
                                    accumulate, (hipStream_t)stream);
 }
@@ -978,6 +1020,7 @@ int fd_time_embed_train(const float* t, const float* W, const float* Wd, const f
 int fd_time_embed_train_cls(const float* t, const float* W, const float* Wd, const float* bd, float* emb, float* temb, int B, int D,
                             hipStream_t s, fd_cls cls) {
     hipLaunchKernelGGL(k_time_embed, dim3(B), dim3(128), D * sizeof(float), s, t, W, Wd, bd, emb, temb, D, cls.y, cls.table, cls.K);
+    if (cls.cov.P > 0) fd_cov_embed_launch(cls.cov, temb, B, D, s);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

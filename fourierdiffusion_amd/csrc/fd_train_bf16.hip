@@ -3129,6 +3129,7 @@ int tr_backward_t(fd_score* m, const float* dout, float* grads, int accumulate, 
     }
     int rc_embed = fd_embed_backward(m, tb.dh, tb.emb, tb.dtemb, grads, B, tb.skp, kSkpFloats, s);
     if (!rc_embed) rc_embed = fd_class_table_backward(m, tb.dtemb, grads, B, accumulate, s);
+    if (!rc_embed) rc_embed = fd_cov_backward(m, tb.dtemb, grads, B, accumulate, s);
     if (rc_embed) {
         // the weight-gradient launches on the side streams are still writing tb.part (arena memory): let them finish before the
         // caller sees the error and reuses or frees the arena

@@ -273,6 +273,46 @@ class SyntheticClassesDatamodule(SyntheticDatamodule):
         return "synthetic_classes"
 
 
+class SyntheticCovariatesDatamodule(SyntheticDatamodule):
+    """Sines with real-valued attributes (not in the reference): x_n = a sin(2 pi f n / T + phi) + 0.05 eps, the frequency f
+    (cycles per window) uniform on [1, 6], the amplitude a uniform on [0.5, 2], phi uniform on [0, 2 pi), eps ~ N(0, 1); every
+    channel of a series shares (f, a) and draws its own phase and noise.  ``y_train`` / ``y_test`` hold the two covariates (f, a)
+    as float32 (n, 2), standardised by the training split; ``cov_mean`` / ``cov_std`` (2,) are that split's statistics, and
+    ``covariates_in_data_units`` undoes it."""
+    F_RANGE, A_RANGE, NOISE = (1.0, 6.0), (0.5, 2.0), 0.05
+
+    def _file(self) -> Path:
+        return self.data_dir / f"sine_covariates_T{self.max_len}_C{self.n_channels}_N{self.num_samples}.npz"
+
+    def setup(self, stage: str = "fit") -> None:
+        d = np.load(self._file())
+        X, c = torch.from_numpy(d["X"]), torch.from_numpy(d["c"]).to(torch.float32)
+        self.X_train, self.X_test = X[: self.num_samples], X[self.num_samples:]
+        self.cov_mean = c[: self.num_samples].mean(dim=0)
+        self.cov_std = c[: self.num_samples].std(dim=0).clamp_min(1e-6)
+        c = (c - self.cov_mean) / self.cov_std
+        self.y_train, self.y_test = c[: self.num_samples].contiguous(), c[self.num_samples:].contiguous()
+        self._train_set = None
+
+    def covariates_in_data_units(self, c: torch.Tensor) -> torch.Tensor:
+        return c.cpu() * self.cov_std + self.cov_mean
+
+    def download_data(self) -> None:
+        rng = np.random.RandomState(self.random_seed)
+        n = 2 * self.num_samples
+        f = rng.uniform(*self.F_RANGE, size=n)
+        a = rng.uniform(*self.A_RANGE, size=n)
+        phase = rng.uniform(0.0, 2.0 * np.pi, size=(n, 1, self.n_channels))
+        noise = rng.normal(size=(n, self.max_len, self.n_channels))
+        timesteps = np.arange(self.max_len).reshape(1, -1, 1)
+        X = a[:, None, None] * np.sin(2.0 * np.pi * f[:, None, None] * timesteps / self.max_len + phase) + self.NOISE * noise
+        np.savez(self._file(), X=X.astype(np.float32), c=np.stack([f, a], axis=1).astype(np.float32))
+
+    @property
+    def dataset_name(self) -> str:
+        return "synthetic_covariates"
+
+
 class TensorDatamodule(Datamodule):
     """Datamodule over in-memory tensors (the role of the reference tests' DummyDatamodule,
     tests/test_datamodules.py:16-53)."""

@@ -18,6 +18,12 @@ more tensor, ``class_encoder.weight`` (K + 1, D), sits behind every other one in
 embedding of series b inside the engine's time-embedding kernel, row K being the null (unconditional) token that a missing label
 and, in training, a label dropped with probability ``label_dropout`` read.  ``DiffusionSampler.sample(y=, cfg_scale=)`` samples
 with classifier-free guidance.  ``n_classes = 0`` is the reference's model bit for bit.
+
+Extension (not in the reference): ``cond_dim = P > 0`` makes the transformer model covariate-conditional.  ``batch.y`` is then a float
+tensor (B, P) of real-valued attributes; a two-layer encoder e(c) = W2 silu(W1 c + b1) + b2 of hidden width d_model -- five more
+tensors ``cov_encoder.*`` behind every other one -- is added to the time embedding by the engine's k_cov_embed, and a learned null
+vector ``cov_encoder.null`` takes its place where the covariates are absent or, in training, dropped with probability
+``cond_dropout``.  ``DiffusionSampler.sample(y=c, cfg_scale=)`` guides on them.  Not together with ``n_classes``.
 """
 from __future__ import annotations
 
@@ -63,9 +69,21 @@ class ScoreModule:
         likelihood_weighting: bool = False,
         n_classes: int = 0,
         label_dropout: float = 0.1,
+        cond_dim: int = 0,
+        cond_dropout: float = 0.1,
     ) -> None:
         self.n_classes = int(n_classes)
         self.label_dropout = float(label_dropout)
+        self.cond_dim = int(cond_dim)
+        self.cond_dropout = float(cond_dropout)
+        if not 0 <= self.cond_dim <= 64:
+            raise ValueError(f"cond_dim must lie in [0, 64] (0: no covariates), got {cond_dim}")
+        if self.cond_dim > 0 and self._backbone != _C.FD_BACKBONE_TRANSFORMER:
+            raise ValueError(f"{type(self).__name__}: cond_dim > 0 (covariate conditioning) exists for the transformer backbone only")
+        if self.cond_dim > 0 and self.n_classes > 0:
+            raise ValueError("cond_dim > 0 together with n_classes > 0 is not built: condition on covariates or on classes")
+        if not 0.0 <= self.cond_dropout <= 1.0:
+            raise ValueError(f"cond_dropout must lie in [0, 1], got {cond_dropout}")
         if self.n_classes < 0:
             raise ValueError(f"n_classes must be >= 0, got {n_classes}")
         if self.n_classes > 0 and self._backbone != _C.FD_BACKBONE_TRANSFORMER:
@@ -95,6 +113,8 @@ class ScoreModule:
             num_training_steps=num_training_steps, lr_max=lr_max, likelihood_weighting=likelihood_weighting)
         if self.n_classes > 0:      # (only then: a checkpoint of an unlabelled model stays readable by the reference's constructor)
             self.hparams.update(n_classes=self.n_classes, label_dropout=self.label_dropout)
+        if self.cond_dim > 0:       # (only then, for the same reason)
+            self.hparams.update(cond_dim=self.cond_dim, cond_dropout=self.cond_dropout)
 
         self.training_loss_fn, self.validation_loss_fn = self.set_loss_fn()
 
@@ -102,7 +122,8 @@ class ScoreModule:
             raise AssertionError("embed_dim must be divisible by num_heads")
         self._dims = _C.model_dims(self.n_channels, self.max_len, self.d_model, self.n_head, self.num_layers,
                                    self.dim_feedforward)
-        self._layout, self._nparams = _C.score_layout(self._dims, self._backbone, self._d_mlp, self.n_classes)
+        self._layout, self._nparams = _C.score_layout(self._dims, self._backbone, self._d_mlp, self.n_classes,
+                                                       self.cond_dim)
         self._flat = torch.zeros(self._nparams, dtype=torch.float32)
         self._ema: Optional[torch.Tensor] = None              # averaged weights, same layout (enable_ema)
         self._ema_scope: Optional[torch.Tensor] = None        # inside use_ema(): the raw buffer that `_flat` stopped naming
@@ -153,6 +174,10 @@ class ScoreModule:
         self._init_backbone(v, linear)
         if "class_encoder.weight" in v:      # nn.Embedding's N(0, 1), drawn behind everything the reference's constructor draws
             init.normal_(v["class_encoder.weight"])
+        if "cov_encoder.0.weight" in v:      # two nn.Linear layers, drawn behind everything else; the null vector starts at zero
+            linear("cov_encoder.0")
+            linear("cov_encoder.2")
+            v["cov_encoder.null"].zero_()
 
     def _init_backbone(self, v, linear) -> None:
         init = torch.nn.init
@@ -331,7 +356,11 @@ class ScoreModule:
         ctx = _C.ctx(self._flat.device)
         if self._handle is None:
             h = C.c_void_p()
-            if self.n_classes > 0:
+            if self.cond_dim > 0:
+                rc = _C.lib().fd_score_create_cov(ctx, C.byref(self._dims), 0, self.cond_dim, C.byref(h))
+                _C.check(rc, ctx)
+                _C.check(_C.lib().fd_score_set_cov_dropout(h, self.cond_dropout), ctx)
+            elif self.n_classes > 0:
                 rc = _C.lib().fd_score_create_cond(ctx, C.byref(self._dims), self.n_classes, C.byref(h))
                 _C.check(rc, ctx)
                 _C.check(_C.lib().fd_score_set_label_dropout(h, self.label_dropout), ctx)
@@ -436,14 +465,17 @@ class ScoreModule:
         if yd is None:
             yield
             return
+        # a covariate model binds its float (B, P) matrix the same way (fd_score_set_covariates / fd_score_get_covariates)
+        get, put = ((_C.lib().fd_score_get_covariates, _C.lib().fd_score_set_covariates) if self.cond_dim > 0 else
+                    (_C.lib().fd_score_get_labels, _C.lib().fd_score_set_labels))
         old_y, old_B = C.c_void_p(), C.c_int(0)
         if restore:
-            _C.check(_C.lib().fd_score_get_labels(h, C.byref(old_y), C.byref(old_B)), ctx)
-        _C.check(_C.lib().fd_score_set_labels(h, yd.data_ptr(), int(yd.shape[0])), ctx)
+            _C.check(get(h, C.byref(old_y), C.byref(old_B)), ctx)
+        _C.check(put(h, yd.data_ptr(), int(yd.shape[0])), ctx)
         try:
             yield
         finally:
-            _C.lib().fd_score_set_labels(h, old_y, old_B.value)
+            put(h, old_y, old_B.value)
 
     def effective_labels(self, y, batch_size: int, key: int, offset: int, p: Optional[float] = None) -> torch.Tensor:
         """The labels a training forward with the Philox stream (key, offset) uses for ``y`` (fd_label_dropout): int32 device vector,
@@ -458,6 +490,67 @@ class ScoreModule:
         _C.check(rc, ctx)
         return out
 
+    # ------------------------------------------------------------------ covariates (not in the reference)
+    def covariates_on_device(self, c, batch_size: int, name: str = "y") -> Optional[torch.Tensor]:
+        """``c`` validated and uploaded: a float32 device matrix (batch_size, cond_dim), or None for ``c is None``.  c: a floating
+        tensor (batch_size, cond_dim), or (cond_dim,) to give every row the same covariates.  ValueError on a model without
+        covariates, a wrong shape, an integer tensor or a non-finite value -- checked on the host (a device tensor is read back)."""
+        if c is None:
+            return None
+        P = self.cond_dim
+        if P <= 0:
+            raise ValueError(f"{name} was given as covariates, but the model has none (cond_dim = 0)")
+        if not isinstance(c, torch.Tensor) or not c.is_floating_point():
+            what = c.dtype if isinstance(c, torch.Tensor) else type(c).__name__
+            raise ValueError(f"{name} must be a floating tensor of shape ({batch_size}, {P}) or ({P},), got {what}")
+        if c.dim() == 1 and c.shape[0] == P:
+            c = c.unsqueeze(0).expand(batch_size, P)
+        if tuple(c.shape) != (batch_size, P):
+            raise ValueError(f"{name} must have shape ({batch_size}, {P}) or ({P},), got {tuple(c.shape)}")
+        if not bool(torch.isfinite(c).all()):
+            raise ValueError(f"{name} must be finite")
+        return c.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def effective_keep(self, n: int, key: int, offset: int, p: Optional[float] = None) -> torch.Tensor:
+        """The keep bytes of covariate dropout a training forward with the Philox stream (key, offset) draws for n rows
+        (fd_cov_dropout): uint8 device vector, 0 where the row reads the null vector (p, default ``cond_dropout``)."""
+        if self.cond_dim <= 0:
+            raise ValueError("effective_keep: the model has no covariates (cond_dim = 0)")
+        ctx = _C.ctx(self.device)
+        out = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        rc = _C.lib().fd_cov_dropout(ctx, out.data_ptr(), int(n), float(self.cond_dropout if p is None else p), int(key), int(offset),
+                                     _C.stream_of(out))
+        _C.check(rc, ctx)
+        return out
+
+    def cov_embedding(self, c, keep=None) -> torch.Tensor:
+        """e (n, d_model) float32 on the device: the encoder's output for the rows of c (n, cond_dim), the null vector where
+        ``keep`` (n, bool / uint8) is zero -- the engine's own kernel on the model's current weights (fd_cov_embed)."""
+        if self.cond_dim <= 0:
+            raise ValueError("cov_embedding: the model has no covariates (cond_dim = 0)")
+        if not isinstance(c, torch.Tensor) or c.dim() != 2:
+            raise ValueError(f"c must be a tensor (n, {self.cond_dim})")
+        n = int(c.shape[0])
+        cd = self.covariates_on_device(c, n, "c")
+        kd = None if keep is None else torch.as_tensor(keep).to(device=self.device).ne(0).to(torch.uint8).contiguous()
+        if kd is not None and tuple(kd.shape) != (n,):
+            raise ValueError(f"keep must have shape ({n},), got {tuple(kd.shape)}")
+        ctx = _C.ctx(self.device)
+        v = {k: _C.dev_f32(t) for k, t in self._views.items() if k.startswith("cov_encoder.")}
+        out = torch.empty(n, self.d_model, dtype=torch.float32, device=self.device)
+        rc = _C.lib().fd_cov_embed(ctx, v["cov_encoder.0.weight"].data_ptr(), v["cov_encoder.0.bias"].data_ptr(),
+                                   v["cov_encoder.2.weight"].data_ptr(), v["cov_encoder.2.bias"].data_ptr(),
+                                   v["cov_encoder.null"].data_ptr(), cd.data_ptr(), _C.ptr(kd), out.data_ptr(), n, self.cond_dim,
+                                   self.d_model, _C.stream_of(out))
+        _C.check(rc, ctx)
+        return out
+
+    def _cond_on_device(self, y, batch_size: int, name: str = "y") -> Optional[torch.Tensor]:
+        """What ``_labels_bound`` binds for ``y``: the covariates of a covariate model, the labels of a labelled one, else None."""
+        if self.cond_dim > 0:
+            return self.covariates_on_device(y, batch_size, name)
+        return self.labels_on_device(y, batch_size, name) if self.n_classes > 0 else None
+
     # ------------------------------------------------------------------ forward / backward
     def forward(self, batch: DiffusableBatch) -> torch.Tensor:
         X = batch.X
@@ -471,7 +564,8 @@ class ScoreModule:
         out = torch.empty_like(Xd)
         B = Xd.shape[0]
         # a labelled model reads batch.y (None: the null token on every row); an unlabelled one ignores it, as the reference does
-        yd = self.labels_on_device(batch.y, B, "batch.y") if self.n_classes > 0 else None
+        # (a covariate model reads it as its float (B, P) covariates, None: the null vector on every row)
+        yd = self._cond_on_device(batch.y, B, "batch.y")
         if not self.training:
             mode = _PRECISIONS[self.precision_effective]
         with self._labels_bound(h, ctx, yd):
@@ -518,7 +612,7 @@ class ScoreModule:
         td = _C.dev_f32(timesteps.to(self.device), "timesteps")
         tg = _C.dev_f32(target, "target")
         sd = _C.dev_f32(std, "std")
-        yd = self.labels_on_device(y, Bn) if self.n_classes > 0 else None
+        yd = self._cond_on_device(y, Bn)
         grads, acc = self._grads_for_backward()
         loss = torch.empty(1, device=self.device, dtype=torch.float32)
         key, off = _rng.stream()
@@ -666,9 +760,11 @@ class MLPScoreModule(ScoreModule):
 
     def __init__(self, n_channels: int, max_len: int, noise_scheduler: SDE, fourier_noise_scaling: bool = True, d_model: int = 72,
                  d_mlp: int = 512, num_layers: int = 3, num_training_steps: int = 1000, lr_max: float = 1e-3,
-                 likelihood_weighting: bool = False, n_classes: int = 0) -> None:
+                 likelihood_weighting: bool = False, n_classes: int = 0, cond_dim: int = 0) -> None:
         if n_classes:
             raise ValueError("MLPScoreModule: n_classes > 0 (class conditioning) exists for the transformer backbone only")
+        if cond_dim:
+            raise ValueError("MLPScoreModule: cond_dim > 0 (covariate conditioning) exists for the transformer backbone only")
         self._d_mlp = int(d_mlp)
         self.d_mlp = int(d_mlp)
         super().__init__(n_channels=n_channels, max_len=max_len, noise_scheduler=noise_scheduler,
@@ -695,9 +791,11 @@ class LSTMScoreModule(ScoreModule):
 
     def __init__(self, n_channels: int, max_len: int, noise_scheduler: SDE, fourier_noise_scaling: bool = True, d_model: int = 72,
                  num_layers: int = 3, num_training_steps: int = 1000, lr_max: float = 1e-3,
-                 likelihood_weighting: bool = False, n_classes: int = 0) -> None:
+                 likelihood_weighting: bool = False, n_classes: int = 0, cond_dim: int = 0) -> None:
         if n_classes:
             raise ValueError("LSTMScoreModule: n_classes > 0 (class conditioning) exists for the transformer backbone only")
+        if cond_dim:
+            raise ValueError("LSTMScoreModule: cond_dim > 0 (covariate conditioning) exists for the transformer backbone only")
         super().__init__(n_channels=n_channels, max_len=max_len, noise_scheduler=noise_scheduler,
                          fourier_noise_scaling=fourier_noise_scaling, d_model=d_model, num_layers=num_layers, n_head=1,
                          num_training_steps=num_training_steps, lr_max=lr_max, likelihood_weighting=likelihood_weighting)

@@ -76,13 +76,15 @@ class SMCInfo:
 
 class DiffusionSampler:
     def __init__(self, score_model: ScoreModule, sample_batch_size: int, corrector_steps: int = 0, snr: float = 0.16,
-                 merge_batches: bool = True, cfg_scale: float = 1.0, labels=None) -> None:
+                 merge_batches: bool = True, cfg_scale: float = 1.0, labels=None, covariates=None) -> None:
         """corrector_steps > 0 turns the predictor-only sampler of the reference into a predictor-corrector one
         (`corrector_steps` Langevin steps at signal-to-noise ratio `snr` before every predictor step; an extension, not in
         the reference: default off).  cfg_scale / labels: the front end's guidance settings (cmd/conf/sampler/*.yaml), kept for
-        cmd/sample.py, which turns ``labels`` into the ``y`` of ``sample``; ``sample`` itself takes both as arguments."""
+        cmd/sample.py, which turns ``labels`` into the ``y`` of ``sample``; ``sample`` itself takes both as arguments.  covariates:
+        the same for a covariate-conditional model (``parse_covariates``)."""
         self.cfg_scale = float(cfg_scale)
         self.labels = labels
+        self.covariates = covariates
         self.corrector_steps = int(corrector_steps)
         self.snr = float(snr)
         self.score_model = score_model
@@ -133,7 +135,8 @@ class DiffusionSampler:
                 yb = None if labels is None else labels[lo:lo + bs].contiguous()
                 lo += bs
                 X = self._cfg_state(X, pair)      # (the state buffer is all a guided launch differs in, besides its entry point)
-                rc = _C.lib().fd_sampler_run_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), _C.ptr(yb),
+                run_guided = _C.lib().fd_sampler_run_cov if self.score_model.cond_dim > 0 else _C.lib().fd_sampler_run_cfg
+                rc = run_guided(h, C.byref(p), G.data_ptr(), ts_arr, N, dt, X.data_ptr(), _C.ptr(yb),
                                                  float(cfg_scale), _C.ptr(z), key, off, bs, mode, _C.stream_of(X))
             elif self.corrector_steps > 0:
                 zc = None
@@ -187,9 +190,10 @@ class DiffusionSampler:
         on an unlabelled model, or a scale that is not a finite number."""
         if isinstance(cfg_scale, bool) or not isinstance(cfg_scale, (int, float)) or not math.isfinite(cfg_scale):
             raise ValueError(f"cfg_scale must be a finite number, got {cfg_scale!r}")
-        if self.score_model.n_classes <= 0:
+        if self.score_model.n_classes <= 0 and getattr(self.score_model, "cond_dim", 0) <= 0:
             if y is not None or float(cfg_scale) != 1.0:
-                raise ValueError("y / cfg_scale need a class-conditional model (ScoreModule(n_classes=K)); this one has n_classes = 0")
+                raise ValueError("y / cfg_scale need a class-conditional model (ScoreModule(n_classes=K)) or a covariate-conditional "
+                                 "one (ScoreModule(cond_dim=P)); this one has n_classes = 0 and cond_dim = 0")
             return False, False
         guided = y is not None or float(cfg_scale) != 1.0
         # The engine takes the scale as a float and decides on that value (fd_guide_plan), so a scale that rounds to 0 or 1 there
@@ -200,14 +204,23 @@ class DiffusionSampler:
         return guided, pair
 
     def _labels(self, y, total: int) -> Optional[torch.Tensor]:
-        """The labels of all ``total`` returned samples as an int32 device vector (None: unconditional)."""
+        """The labels of all ``total`` returned samples as an int32 device vector (None: unconditional); on a covariate model the
+        covariates as a float32 device matrix (total, cond_dim), y being (total, cond_dim) or (cond_dim,) for every sample alike."""
+        if getattr(self.score_model, "cond_dim", 0) > 0:
+            if isinstance(y, torch.Tensor) and y.dim() == 2 and y.shape[0] != total:
+                raise ValueError(f"y must hold one covariate row per returned sample: {total} (whole batches of sample_batch_size), "
+                                 f"got {y.shape[0]}")
+            return self.score_model.covariates_on_device(y, total, "y")
         if isinstance(y, torch.Tensor) and y.dim() == 1 and y.shape[0] != total:
             raise ValueError(f"y must hold one label per returned sample: {total} (whole batches of sample_batch_size), got {y.shape[0]}")
         return self.score_model.labels_on_device(y, total, "y")
 
     def _series_labels(self, y, n: int, who: str) -> Optional[torch.Tensor]:
         """The labels of ``n`` conditioning series (``impute``, ``impute_guidance``, ``log_likelihood``: one label per series) as an
-        int32 device vector (None: unconditional)."""
+        int32 device vector (None: unconditional).  Covariates are not built there: ValueError."""
+        if getattr(self.score_model, "cond_dim", 0) > 0:
+            raise ValueError(f"{who}: covariates (y / cfg_scale on a covariate-conditional model) are not built here; call it with "
+                             "y=None to run the model on its null vector")
         if isinstance(y, torch.Tensor) and y.dim() == 1 and y.shape[0] != n:
             raise ValueError(f"{who}: y must hold one label per series: {n}, got {y.shape[0]}")
         return self.score_model.labels_on_device(y, n, "y")
@@ -294,7 +307,8 @@ class DiffusionSampler:
         dpm = solver in self._DPM_SOLVERS
         sid = self._DPM_SOLVERS[solver] if dpm else self._SOLVERS[solver]
         if yb is not None or w != 1.0:
-            rc = _C.lib().fd_sampler_run_ode_cfg(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), _C.ptr(yb), w, bs, mode,
+            run_guided = _C.lib().fd_sampler_run_ode_cov if self.score_model.cond_dim > 0 else _C.lib().fd_sampler_run_ode_cfg
+            rc = run_guided(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), _C.ptr(yb), w, bs, mode,
                                                  _C.stream_of(X))
         else:
             run = _C.lib().fd_sampler_run_dpm if dpm else _C.lib().fd_sampler_run_ode
@@ -332,7 +346,7 @@ class DiffusionSampler:
         if adaptive:
             rtol, atol, max_evals = float(rtol), float(atol), int(max_evals)
         n, reps, N, grid, drift = self._ll_plan(X, num_diffusion_steps, solver, estimator, n_probes, probes, rtol, atol, max_evals)
-        labels = self._series_labels(y, n, "log_likelihood")
+        labels = self._series_labels(y, n, "log_likelihood") if y is not None else None
         ctx, h, p, G, mode = self._engine_args()
         dev = self.score_model.device
         T, Cn = self.max_len, self.n_channels
@@ -1134,6 +1148,40 @@ def parse_labels(spec, n: int, n_classes: int, allow_balanced: bool = True) -> O
     return torch.full((n,), k, dtype=torch.int64)
 
 
+def parse_covariates(spec, n: int, cond_dim: int, datamodule=None) -> Optional[torch.Tensor]:
+    """The ``covariates`` setting of the sampler configs as the ``y`` of ``sample`` for n samples on a covariate-conditional model, a
+    float32 tensor (n, cond_dim) in the model's (standardised) units: None / "null" -> None (the null vector); a list of cond_dim
+    numbers in DATA units -> that row for every sample, standardised with the datamodule's ``cov_mean`` / ``cov_std`` when it has
+    them; "data" -> the datamodule's (already standardised) ``y_test`` rows, cycled.  ValueError otherwise, and for any covariates on
+    a model without them."""
+    if spec is None or (isinstance(spec, str) and spec.strip().lower() in ("null", "none", "")):
+        return None
+    if cond_dim <= 0:
+        raise ValueError(f"covariates={spec!r}, but the model has no covariates (score_model.cond_dim = 0)")
+    if isinstance(spec, str) and spec.strip().lower() == "data":
+        y = getattr(datamodule, "y_test", None)
+        name = type(datamodule).__name__
+        if y is None or not torch.as_tensor(y).is_floating_point():
+            raise ValueError(f"covariates=data, but {name} has no float covariates (y_test): use datamodule=synthetic_covariates, "
+                             "covariates=[v1, ..., vP] or covariates=null")
+        y = torch.as_tensor(y).to(torch.float32)
+        if y.dim() != 2 or y.shape[1] != cond_dim or y.shape[0] == 0:
+            raise ValueError(f"covariates=data: the covariates of {name} have shape {tuple(y.shape)}, the model has cond_dim = {cond_dim}")
+        return y[torch.arange(n) % y.shape[0]].contiguous()
+    if isinstance(spec, str) or isinstance(spec, bool) or not hasattr(spec, "__len__"):
+        raise ValueError(f"covariates must be 'data', a list of {cond_dim} numbers or null, got {spec!r}")
+    vals = list(spec)
+    if len(vals) != cond_dim or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in vals):
+        raise ValueError(f"covariates must be 'data', a list of {cond_dim} numbers or null, got {spec!r}")
+    row = torch.tensor([float(v) for v in vals], dtype=torch.float64)
+    if not bool(torch.isfinite(row).all()):
+        raise ValueError(f"covariates must be finite, got {spec!r}")
+    mean, std = getattr(datamodule, "cov_mean", None), getattr(datamodule, "cov_std", None)
+    if mean is not None and std is not None:
+        row = (row - torch.as_tensor(mean, dtype=torch.float64)) / torch.as_tensor(std, dtype=torch.float64)
+    return row.to(torch.float32).unsqueeze(0).expand(n, cond_dim).contiguous()
+
+
 def series_labels(spec, datamodule, n: int, n_classes: int) -> Optional[torch.Tensor]:
     """The ``labels`` setting of cmd/impute.py and cmd/likelihood.py as the ``y`` of ``impute`` / ``log_likelihood`` for the first n
     test series: None / "null" -> None (the model runs unconditionally), an int (or its string) -> that class for every series,
@@ -1163,9 +1211,9 @@ class ODESampler(DiffusionSampler):
     ``python cmd/sample.py sampler=ode num_diffusion_steps=50``, ``python cmd/sample.py sampler=dpm num_diffusion_steps=20``."""
 
     def __init__(self, score_model: ScoreModule, sample_batch_size: int, solver: str = "heun", merge_batches: bool = True,
-                 schedule: str = "time", cfg_scale: float = 1.0, labels=None) -> None:
+                 schedule: str = "time", cfg_scale: float = 1.0, labels=None, covariates=None) -> None:
         super().__init__(score_model=score_model, sample_batch_size=sample_batch_size, merge_batches=merge_batches,
-                         cfg_scale=cfg_scale, labels=labels)
+                         cfg_scale=cfg_scale, labels=labels, covariates=covariates)
         self._check_solver(solver, dpm=True)
         if schedule not in self._SCHEDULES:
             raise ValueError(f"schedule must be one of {list(self._SCHEDULES)}, got {schedule!r}")

@@ -52,7 +52,8 @@ def get_sde_loss_fn(
         if train and do_bwd and hasattr(model, "train_dsm"):
             # forward + loss + backward as one engine call where the model has it (bf16 transformer training path)
             fused = model.train_dsm(x_noisy, timesteps, target, std, likelihood_weighting=likelihood_weighting,
-                                    grad_weight=grad_weight, **({"y": batch.y} if getattr(model, "n_classes", 0) > 0 else {}))
+                                    grad_weight=grad_weight, **({"y": batch.y} if getattr(model, "n_classes", 0) > 0 or getattr(model, "cond_dim", 0) > 0
+                                                                  else {}))
             if fused is not None:
                 return fused
         if train:

@@ -248,6 +248,46 @@ int fd_score_set_label_dropout(fd_score* m, float p);
 int fd_label_dropout(fd_ctx* ctx, const int32_t* y, int32_t* y_out, int B, int n_classes, float p, uint64_t seed, uint64_t offset,
                      void* stream);
 
+/* Covariate-conditional score models (an extension, not in the reference).  A transformer-backbone model with cond_dim = P in
+ * [1, 64] reads a float vector c_b (P) per series through a two-layer encoder e(c) = W2 silu(W1 c + b1) + b2 of hidden width
+ * d_model, and owns five more tensors appended BEHIND every tensor of fd_score_layout (no existing offset moves):
+ * cov_encoder.0.weight (D, P), cov_encoder.0.bias (D), cov_encoder.2.weight (D, D), cov_encoder.2.bias (D), cov_encoder.null (D).
+ * One kernel behind the time-embedding kernel of every forward and training path ends the time embedding of series b with
+ * + (keep_b ? e(c_b) : null), in fp32.  cond_dim = 0 is fd_score_layout_cond / fd_score_create_cond exactly; cond_dim > 0 together
+ * with n_classes > 0 is FD_ERR_ARG.  As a class-conditional model, a covariate model runs the per-layer kernels and every sampling
+ * loop step by step (fd_score_plan says so).
+ *   fd_score_layout_cov       the layout (entries NULL: the count alone) and, n_params non-NULL, the float count of the flat buffer
+ *                             (an extension, not in the reference).
+ *   fd_score_create_cov       the model (an extension, not in the reference).
+ *   fd_score_set_covariates   binds a DEVICE float matrix (B, P) to the model (borrowed; c == NULL unbinds).  While covariates are
+ *                             bound, fd_score_forward, fd_score_forward_train, fd_score_train_dsm and fd_score_input_vjp with
+ *                             another B return FD_ERR_ARG.  With nothing bound every row reads the null vector (an extension, not
+ *                             in the reference).
+ *   fd_score_get_covariates   the binding as it stands (an extension, not in the reference).
+ *   fd_score_set_cov_dropout  p in [0, 1]: every TRAINING forward reads the null vector on a row with probability p, decided by the
+ *                             Philox stream of that call in the counter window and by the lane rule of label dropout: the keep
+ *                             bytes equal fd_label_dropout's output != n_classes for the same seed, offset and p.  Eval forwards
+ *                             never drop (an extension, not in the reference).
+ *   fd_cov_dropout            the keep bytes alone: keep[b] = 1 unless the training forward of (seed, offset) drops row b.  keep:
+ *                             device uint8[B] (an extension, not in the reference).
+ *   fd_cov_embed              the encoder kernel alone on raw device pointers: e[b, :] = keep_b ? e(c_b) : null, e (B, D); c NULL:
+ *                             every row the null vector; keep NULL: every row kept (an extension, not in the reference).
+ *   fd_cov_embed_backward     the encoder gradient alone from an injected dtemb (B, D): dW2, db2, dW1, db1 over the kept rows, dnull
+ *                             over the dropped ones, summed over b ascending without atomics (bit-reproducible); accumulate != 0
+ *                             adds to the outputs.  Uses the context workspace (an extension, not in the reference). */
+int fd_score_layout_cov(const fd_model_dims* dims, int n_classes, int cond_dim, fd_param_entry* entries, int* n_entries,
+                        int64_t* n_params);
+int fd_score_create_cov(fd_ctx* ctx, const fd_model_dims* dims, int n_classes, int cond_dim, fd_score** out);
+int fd_score_set_covariates(fd_score* m, const float* c, int B);
+int fd_score_get_covariates(fd_score* m, const float** c, int* B);
+int fd_score_set_cov_dropout(fd_score* m, float p);
+int fd_cov_dropout(fd_ctx* ctx, uint8_t* keep, int B, float p, uint64_t seed, uint64_t offset, void* stream);
+int fd_cov_embed(fd_ctx* ctx, const float* w1, const float* b1, const float* w2, const float* b2, const float* nul, const float* c,
+                 const uint8_t* keep, float* e, int B, int P, int D, void* stream);
+int fd_cov_embed_backward(fd_ctx* ctx, const float* w1, const float* b1, const float* w2, const float* c, const uint8_t* keep,
+                          const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, float* dnull, int B, int P, int D,
+                          int accumulate, void* stream);
+
 /* Derive the engine-side weight images from the flat fp32 parameters (device pointer):
  * max_norm-renormed positional table (the reference renorms in place inside forward,
  * transformer.py:13-15,27), bf16 MFMA-fragment-ordered matrices, folded biases.
@@ -623,6 +663,15 @@ int fd_sampler_run_cfg(fd_score* m, const fd_sde_params* sde, const float* G, co
                        const int32_t* y, float w, const float* z_steps, uint64_t seed, uint64_t offset, int B, int mode, void* stream);
 int fd_sampler_run_ode_cfg(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
                            float* x, const int32_t* y, float w, int B, int mode, void* stream);
+
+/* The same two loops on a covariate-conditional model (an extension, not in the reference): c device float (B, P) covariates or NULL,
+ * the score w s(x, t, c) + (1 - w) s(x, t, null).  w == 1: one evaluation per step with c bound; w == 0 or c == NULL: one evaluation
+ * on the null vector, x (B,T,C); otherwise one forward on 2B rows (the covariates twice, the second half reading the null vector), x
+ * a (2B,T,C) buffer, and the fused step kernels of the class-guided loops.  FD_ERR_ARG on a model without covariates. */
+int fd_sampler_run_cov(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, float dt, float* x,
+                       const float* c, float w, const float* z_steps, uint64_t seed, uint64_t offset, int B, int mode, void* stream);
+int fd_sampler_run_ode_cov(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
+                           float* x, const float* c, float w, int B, int mode, void* stream);
 
 /* Likelihood extension (NOT in the reference; Song et al. 2021, Sec. 4.3 and App. D.2): the exact log-density of the
  * probability-flow ODE above,
