@@ -22,7 +22,9 @@ lowpass), the observation is P applied to the test split, every full-resolution 
 results.yaml records `operator` (kind, its parameters, M and cond(P)) and `max_abs_err_operator`, the largest deviation of P applied
 to the result from the observation over the observed rows.  Not with aggregate > 1, labels / cfg_scale, resample or conditioning=smc.
 multivariate_scores=true (K > 1) adds the scores that see the joint draw (energy score, variogram score with the `variogram` block's
-order / max_lag / weights, rank histogram and its reliability index), on channels divided by their standard deviation.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
+order / max_lag / weights, rank histogram and its reliability index), on channels divided by their standard deviation.
+multivariate_ranks=[average,band_depth,dominance,mst] (any subset, K > 1) adds the multivariate rank histograms, one count per series:
+`rank_histogram_<kind>`, `rank_reliability_index_<kind>` and `n_series_ranked`.  num_series=n keeps the first n test series.  With several processes (torch.distributed.run) the rows are sharded over the ranks, as cmd/sample.py shards its batches."""
 from __future__ import annotations
 
 import logging
@@ -38,7 +40,7 @@ import yaml  # noqa: E402
 from fourierdiffusion_amd import _rng  # noqa: E402
 from fourierdiffusion_amd.config import compose, instantiate, load_yaml, save_yaml  # noqa: E402
 from fourierdiffusion_amd.parallel import bind_device, init_process_group, shard_range  # noqa: E402
-from fourierdiffusion_amd.sampling.forecast import ensemble_scores, multivariate_scores  # noqa: E402
+from fourierdiffusion_amd.sampling.forecast import PRERANKS, ensemble_scores, multivariate_rank_histogram, multivariate_scores  # noqa: E402
 from fourierdiffusion_amd.sampling.masks import LinearOperator, apply_operator, observation_mask, operator_from_config, window_means  # noqa: E402
 from fourierdiffusion_amd.sampling.sampler import series_labels  # noqa: E402
 from fourierdiffusion_amd.utils.extraction import dict_to_str, get_best_checkpoint, get_model_type  # noqa: E402
@@ -72,6 +74,12 @@ def ensemble_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor) -
     return out
 
 
+def channel_std(truth: torch.Tensor) -> torch.Tensor:
+    """Per-channel standard deviation of the scored truth split (float64; 1 where it is 0): the scale of the scores that mix channels."""
+    std = truth.double().reshape(-1, truth.shape[-1]).std(0, unbiased=False)
+    return torch.where(std > 0, std, torch.ones_like(std))
+
+
 def multivariate_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor, opts=None) -> dict:
     """The multivariate scores of an ensemble X (n, K, T, C), K > 1 (sampling.forecast.multivariate_scores: energy score, variogram
     score, rank histogram), with every channel divided by the standard deviation of the scored truth split (float64; 1 where it
@@ -80,12 +88,27 @@ def multivariate_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tenso
         raise ValueError("multivariate_scores=true needs an ensemble: set num_samples_per_series=K > 1, got samples of shape "
                          f"{tuple(X.shape)}")
     opts = opts or {}
-    std = truth.double().reshape(-1, truth.shape[-1]).std(0, unbiased=False)
-    std = torch.where(std > 0, std, torch.ones_like(std))
+    std = channel_std(truth)
     max_lag = opts.get("max_lag", None)
     m = multivariate_scores(X, truth, mask, order=float(opts.get("order", 0.5)), max_lag=None if max_lag is None else int(max_lag),
                             weights=str(opts.get("weights", "inverse_lag")), scale=std).metrics
     return {**m, "multivariate_scale": "channel_std"}
+
+
+def multivariate_rank_results(X: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor, kinds) -> dict:
+    """The multivariate rank histograms of an ensemble X (n, K, T, C), K > 1 (sampling.forecast.multivariate_rank_histogram), for
+    every pre-rank in `kinds`: `rank_histogram_<kind>` (a list), `rank_reliability_index_<kind>` and `n_series_ranked`.  Channels
+    are divided by the standard deviation of the scored truth split as in multivariate_results (it matters for mst only)."""
+    if X.dim() != 4 or int(X.shape[1]) < 2:
+        raise ValueError("multivariate_ranks needs an ensemble: set num_samples_per_series=K > 1, got samples of shape "
+                         f"{tuple(X.shape)}")
+    std = channel_std(truth)
+    out = {}
+    for kind, r in multivariate_rank_histogram(X, truth, mask, [str(k) for k in kinds], scale=std).items():
+        out[f"rank_reliability_index_{kind}"] = r["reliability_index"]
+        out[f"rank_histogram_{kind}"] = [float(v) for v in r["histogram"]]
+        out["n_series_ranked"] = r["n_series_ranked"]
+    return out
 
 
 class ImputationRunner:
@@ -132,6 +155,11 @@ class ImputationRunner:
         self.variogram = dict(cfg.get("variogram", None) or {})
         if self.multivariate and self.num_samples < 2:
             raise ValueError("multivariate_scores=true needs an ensemble: set num_samples_per_series=K > 1")
+        self.rank_kinds = [str(k) for k in (cfg.get("multivariate_ranks", None) or [])]
+        if [k for k in self.rank_kinds if k not in PRERANKS]:
+            raise ValueError(f"multivariate_ranks must be a list out of {PRERANKS}, got {self.rank_kinds}")
+        if self.rank_kinds and self.num_samples < 2:
+            raise ValueError("multivariate_ranks needs an ensemble: set num_samples_per_series=K > 1")
         best_checkpoint_path = get_best_checkpoint(self.save_dir / "checkpoints")
         model_type = get_model_type(train_cfg)
         self.score_model = model_type.load_from_checkpoint(checkpoint_path=best_checkpoint_path,
@@ -215,6 +243,8 @@ class ImputationRunner:
             results["impute"] = {"mask_kind": str(self.mask_cfg.kind), **scores}
             if self.multivariate and (~fine).any():
                 results["impute"].update(multivariate_results(X, truth, fine, self.variogram))
+            if self.rank_kinds and (~fine).any():
+                results["impute"].update(multivariate_rank_results(X, truth, fine, self.rank_kinds))
             if w > 1:
                 results["impute"]["aggregate"] = w
                 if mask.any():

@@ -21,6 +21,7 @@ FD_MODE_BF16 = 1
 FD_COMM_ID_BYTES = 128
 FD_BACKBONE_TRANSFORMER, FD_BACKBONE_MLP, FD_BACKBONE_LSTM = 0, 1, 2
 FD_VARIOGRAM_HALF, FD_VARIOGRAM_ONE, FD_VARIOGRAM_TWO = 0, 1, 2
+FD_PRERANK_AVERAGE, FD_PRERANK_BAND_DEPTH, FD_PRERANK_DOMINANCE, FD_PRERANK_MST = 0, 1, 2, 3
 FD_POSTHOC_CLASSIFY, FD_POSTHOC_PREDICT = 0, 1
 FD_POSTHOC_MAX_CLASSES = 256
 
@@ -220,6 +221,9 @@ _PROTOS = {
     "fd_variogram_score": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fd_ensemble_ranks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "fd_multivariate_ranks_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_multivariate_ranks": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                        _vp, C.c_size_t, _vp]),
     "fd_kernel_quadforms_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_kernel_quadforms": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, _vp, C.c_int, C.c_int,
                                       _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -334,6 +334,96 @@ def reliability_index(hist: torch.Tensor) -> float:
     return float((f - 1.0 / f.numel()).abs().sum())
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# Multivariate rank histograms (fd_multivariate_ranks).  The rank histogram above is per entry, so it too is blind to
+# members permuted independently at every entry.  A pre-rank maps every point of a series (the truth and the K members) to one number
+# that sees all of its hidden entries; the rank of the truth's pre-rank among the members' feeds the same histogram, one count per
+# series.
+PRERANKS = ("average", "band_depth", "dominance", "mst")
+_PRERANK_KINDS = {"average": _C.FD_PRERANK_AVERAGE, "band_depth": _C.FD_PRERANK_BAND_DEPTH, "dominance": _C.FD_PRERANK_DOMINANCE,
+                  "mst": _C.FD_PRERANK_MST}
+MAX_RANKED_SAMPLES = 1023                                               # the truth is the 1024th point of a series
+
+
+@dataclass
+class MultivariateRanks:
+    """prerank: float64 (n, K + 1), column 0 the truth's; below, equal: int32 (n,), the members whose pre-rank lies below the
+    truth's / equals it; hidden: int32 (n,), the hidden entries per series.  A series with a NaN at a hidden entry has
+    below = equal = -1 and pre-ranks -1 (NaN for "mst"); a series without a hidden entry has equal pre-ranks (below 0, equal K)."""
+    prerank: torch.Tensor
+    below: torch.Tensor
+    equal: torch.Tensor
+    hidden: torch.Tensor
+
+
+def _check_prerank(kind) -> str:
+    if kind not in PRERANKS:
+        raise ValueError(f"kind must be one of {PRERANKS}, got {kind!r}")
+    return kind
+
+
+def multivariate_rank_counts(samples: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor, kind: str, *, scale=None,
+                             device: Optional[torch.device] = None) -> MultivariateRanks:
+    """Pre-ranks of the truth and of the K <= 1023 members of every series over its hidden entries (mask False), and the truth's
+    rank among them.  kind: "average" (the sum over the hidden entries of the per-entry ranks), "band_depth" (the pairs of points
+    whose band holds the point, summed likewise), "dominance" (the points that lie at or below the point at every hidden entry)
+    or "mst" (the length of the Euclidean minimum spanning tree of the other points).  samples (n, K, T, C), truth (n, T, C),
+    mask bool (n, T, C) or (T, C), True = observed.  ``scale`` broadcasts to (T, C) and divides samples and truth first, as in
+    ``energy_score``: it matters for "mst" only, the other kinds are invariant under a positive scale per entry."""
+    kind = _check_prerank(kind)
+    n, K, T, Cn = _check_ensemble(samples, truth)
+    if K > MAX_RANKED_SAMPLES:
+        raise ValueError(f"the ensemble size must lie in [1, {MAX_RANKED_SAMPLES}] for multivariate ranks, got {K}")
+    mask = _check_mask(mask, n, T, Cn)
+    sc = _check_scale(scale, T, Cn)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    h, L = _C.ctx(dev), _C.lib()
+    code = _PRERANK_KINDS[kind]
+    per_series = mask.dim() == 3
+    sc_d = None if sc is None else sc.to(dev)
+    out = MultivariateRanks(prerank=torch.empty((n, K + 1), dtype=torch.float64), below=torch.empty(n, dtype=torch.int32),
+                            equal=torch.empty(n, dtype=torch.int32), hidden=torch.empty(n, dtype=torch.int32))
+    step = max(1, CHUNK_BYTES // (4 * K * T * Cn))
+    if kind == "mst":                                                   # the (K + 1)^2 distances of a series live in the workspace
+        step = max(1, min(step, CHUNK_BYTES // (8 * (K + 1) * (K + 1))))
+    need = ctypes.c_size_t(0)
+    for lo in range(0, n, step):
+        nb = min(step, n - lo)
+        xs = _C.dev_f32(samples[lo:lo + nb].to(dev), "samples")
+        y = _C.dev_f32(truth[lo:lo + nb].to(dev), "truth")
+        if sc_d is not None:
+            xs, y = (xs.double() / sc_d).float(), (y.double() / sc_d).float()
+        m8 = (mask[lo:lo + nb] if per_series else mask).to(torch.uint8).contiguous().to(dev)
+        _C.check(L.fd_multivariate_ranks_workspace_bytes(h, code, nb, K, T, Cn, ctypes.byref(need)), h)
+        work = torch.empty(max(1, need.value), dtype=torch.uint8, device=dev)
+        pr = torch.empty((nb, K + 1), dtype=torch.float64, device=dev)
+        ob, oe, oh = (torch.empty(nb, dtype=torch.int32, device=dev) for _ in range(3))
+        _C.check(L.fd_multivariate_ranks(h, code, xs.data_ptr(), y.data_ptr(), m8.data_ptr(), int(per_series), nb, K, T, Cn,
+                                         pr.data_ptr(), ob.data_ptr(), oe.data_ptr(), oh.data_ptr(), work.data_ptr(), work.numel(),
+                                         _C.stream_of(xs)), h)
+        out.prerank[lo:lo + nb], out.below[lo:lo + nb] = pr.cpu(), ob.cpu()
+        out.equal[lo:lo + nb], out.hidden[lo:lo + nb] = oe.cpu(), oh.cpu()
+    return out
+
+
+def multivariate_rank_histogram(samples: torch.Tensor, truth: torch.Tensor, mask: torch.Tensor,
+                                kinds: Sequence[str] = PRERANKS[:2], *, scale=None,
+                                device: Optional[torch.device] = None) -> Dict[str, dict]:
+    """{kind: {"histogram": float64 (K + 1,), "reliability_index": float, "n_series_ranked": int}} of ``multivariate_rank_counts``:
+    ``rank_histogram`` over the series that have a hidden entry, one count per series, ties spread uniformly.  NaN when no series
+    has a hidden entry or one of them holds a NaN there."""
+    if isinstance(kinds, str) or len(tuple(kinds)) == 0:
+        raise ValueError(f"kinds must be a non-empty sequence out of {PRERANKS}, got {kinds!r}")
+    kinds = tuple(_check_prerank(k) for k in kinds)
+    K = int(samples.shape[1]) if isinstance(samples, torch.Tensor) and samples.dim() == 4 else 0
+    out = {}
+    for kind in kinds:
+        r = multivariate_rank_counts(samples, truth, mask, kind, scale=scale, device=device)
+        hist = rank_histogram(r.below, r.equal, r.hidden == 0, K)
+        out[kind] = {"histogram": hist, "reliability_index": reliability_index(hist), "n_series_ranked": int((r.hidden > 0).sum())}
+    return out
+
+
 def _mean_where(v: torch.Tensor, defined: torch.Tensor) -> float:
     return float(v[defined].mean()) if bool(defined.any()) else math.nan
 

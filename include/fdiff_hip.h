@@ -871,6 +871,34 @@ int fd_variogram_score(fd_ctx* ctx, const float* samples, const float* truth, co
 int fd_ensemble_ranks(fd_ctx* ctx, const float* samples, const float* truth, int n, int K, int T, int C, int32_t* below,
                       int32_t* equal, void* stream);
 
+/* Multivariate rank histograms of a sample ensemble, per series (NOT in the reference; Gneiting et al. 2008, Thorarinsdottir,
+ * Scheuerer and Heinz 2016, Smith and Hansen 2004 / Wilks 2004): the ranks of fd_ensemble_ranks are per entry and cannot tell a
+ * coherent ensemble from one whose members were permuted independently at every entry; the rank of the truth under a pre-rank
+ * that sees the whole series can.  samples, truth, mask_u8, mask_per_series as in fd_energy_score, but 1 <= K <= 1023.  For one
+ * series S = {x_0 = truth, x_1 .. x_K}, m = K + 1 points, H its hidden entries (mask 0); for candidate j and entry e, over all m
+ * points i (j included), b = #{i : x_i[e] < x_j[e]} and a = #{i : x_i[e] > x_j[e]}, on the fp32 values as stored.  prerank[s][j]:
+ *   FD_PRERANK_AVERAGE     sum_{e in H} (m - a), the count of x_i[e] <= x_j[e]
+ *   FD_PRERANK_BAND_DEPTH  sum_{e in H} [C(m,2) - C(b,2) - C(a,2)], the pairs of points whose closed band holds x_j[e] (without
+ *                          ties (m - r)(r - 1) + (m - 1) at rank r = b + 1)
+ *   FD_PRERANK_DOMINANCE   #{i : x_i[e] <= x_j[e] for every e in H}, i = j included
+ *   FD_PRERANK_MST         the length of the Euclidean minimum spanning tree, over H, of S without x_j (0 when fewer than two points
+ *                          remain): differences, squares and sums in double from the fp32 inputs, in ascending entry order
+ * below[s] = #{j >= 1 : prerank[s][j] < prerank[s][0]}, equal[s] = #{j >= 1 : prerank[s][j] == prerank[s][0]}, hidden[s] = |H|
+ * (hidden may be NULL).  The three integer kinds accumulate in int64 and are written exactly as doubles.  Observed entries are
+ * skipped by select: whatever they hold, NaN included, has no effect.  A NaN at a hidden entry, in the truth or in any member,
+ * poisons that series and no other: below = equal = -1, its pre-ranks -1 (NaN for FD_PRERANK_MST).  A series without a hidden
+ * entry has equal pre-ranks: below 0, equal K, hidden 0.  No atomics: two runs are bit-identical, and a series' outputs do not
+ * depend on n or on its position (csrc/fd_mvrank.hip).  work: caller-owned device bytes, at least
+ * fd_multivariate_ranks_workspace_bytes of the same kind and shape (FD_PRERANK_MST keeps the (n, m, m) distance matrices there).
+ * FD_ERR_ARG: null pointer, an unknown kind, a shape < 1, K outside [1, 1023], a workspace that is too small, T*C >= 2^31 - 64,
+ * C(m,2) * T*C >= 2^53, or n too large for one launch (2^31 workgroups). */
+enum { FD_PRERANK_AVERAGE = 0, FD_PRERANK_BAND_DEPTH = 1, FD_PRERANK_DOMINANCE = 2, FD_PRERANK_MST = 3 };
+int fd_multivariate_ranks_workspace_bytes(fd_ctx* ctx, int kind, int n, int K, int T, int C, size_t* bytes);
+int fd_multivariate_ranks(fd_ctx* ctx, int kind, const float* samples, const float* truth, const uint8_t* mask_u8,
+                          int mask_per_series, int n, int K, int T, int C, double* prerank /* (n, K + 1) */,
+                          int32_t* below /* (n) */, int32_t* equal /* (n) */, int32_t* hidden /* (n) or NULL */, void* work,
+                          size_t work_bytes, void* stream);
+
 /* Quadratic forms of the kernel two-sample test (NOT in the reference; Gretton et al. 2012: the unbiased MMD^2 with a permutation
  * p-value is host arithmetic on them, utils/two_sample.py).  z (N, d) dense row-major fp32 device rows with finite entries, the two
  * samples stacked; member (N, P) device bytes, 0 / non-zero = outside / inside the first group: column 0 the observed split, every
