@@ -19,6 +19,10 @@ struct fd_bf16_images {
     int nlp = 0;
     bool ffn32_stale = false;                      // skipped by the last (training-step) rebuild
     size_t off_ffn32 = 0, ffn32_layer_bytes = 0;   // pair-form FFN image of the layer (32x32x16 H; 0 bytes: not built)
+    // FD_RELU_CLAMP: the pair-form image holds 2^-k W1 | b1 and 2^k W2; a weight that would leave bf16's normal range (or a
+    // non-finite one) is counted into *ffn32_bad by the build, read back once per rebuild: the model then runs without the image
+    int* ffn32_bad = nullptr;   // device counter
+    bool ffn32_ok = true;       // the last build's verdict (P.off_ffn32 = 0 when false: the 16x16x32 loop on the unscaled image)
     // ---- training (fd_train_bf16.hip): transposed-weight images of the backward pass, built lazily with the others
     bool train = false;         // bf16 training kernels instantiated for this model
     char* bimg = nullptr;       // per layer: FFN backward blocks (chunk-major, same block count as the forward image),

@@ -100,7 +100,18 @@ int fd_mega_launch(fd_ctx* ctx, const fd_mega_params& P, int ks1, int dt, int ks
         if (wanted) {
             void* fn = nullptr;
             std::string why;
-            if (fd_mega_rtc_get(ctx, key, &fn, &why, /*compile=*/describe == nullptr)) {      // (a description compiles nothing)
+            bool got = fd_mega_rtc_get(ctx, key, &fn, &why, /*compile=*/describe == nullptr);      // (a description compiles nothing)
+#if FD_RELU_CLAMP
+            // a hiprtc that cannot assemble the pair form's clamped conversion: the same shape without the pair form, i.e. the
+            // 16x16x32 loop on the UNSCALED image -- never the unclamped loop on the scaled image or the other way round
+            if (!got && key.ffn32) {
+                key.ffn32 = 0;
+                std::string why16;
+                got = fd_mega_rtc_get(ctx, key, &fn, &why16, describe == nullptr);
+                if (!got) key.ffn32 = 1;
+            }
+#endif
+            if (got) {
                 if (describe) {
                     snprintf(describe, 192, "k_mega<%d,%d,%d,%d,ShapeStatic<%d,%d,%d,%d,%d,%d,%d,%d,%d> (hiprtc)> S=%d NPG=%d rot=%d grid=%d lds=%zu%s", ks1, dt,
                              kso, mt, P.T, P.D, P.C, P.H, P.S, P.NPG, P.rot, P.L, P.F, P.S, P.NPG, P.rot, grid, lds, key.ffn32 ? " ffn32" : "");

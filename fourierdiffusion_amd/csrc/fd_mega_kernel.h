@@ -218,6 +218,18 @@ __device__ __forceinline__ void relu_split32(const f32x16& h, bf16x8& t0, bf16x8
     t0 = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
     t1 = __builtin_bit_cast(bf16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
 }
+#if FD_RELU_CLAMP
+// relu + conversion in one instruction (FD_RELU_CLAMP, fd_mega_params.h): the VOP3 clamp bit, which hipcc has no route to -- a
+// source-level clamp becomes one v_max_f32 ... clamp per value.  NO wait states are placed for an inline-asm read of an MFMA result
+// (see cvt_pk_bf16): the pair-form loop alone calls these, on the H of the PREVIOUS item -- behind that item's W2 MFMAs, and behind an
+// explicit pad in front of its first step (tests/test_mega_relu_clamp_isa.py counts the distance in the benched kernel's ISA).
+// volatile: keeps the statements in source order between the MFMAs they are written between (sched_group_barrier does not see them).
+__device__ __forceinline__ unsigned cvt_pk_bf16_relu01(float lo, float hi) {
+    unsigned r;
+    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+#endif
 __device__ __forceinline__ bf16x8 frag_zero() {
     u32x4 z = {0u, 0u, 0u, 0u};
     return __builtin_bit_cast(bf16x8, z);
@@ -425,6 +437,11 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
         if (P.prof && blockIdx.x == 0 && wave == 0 && (step < 4 || phase == 0) && prof_cnt < 3990) {
             const unsigned long long tm = __builtin_readcyclecounter();
             if (lane == 0) {
+#if FD_RELU_CLAMP
+                // (opaque: as a constant hipcc builds the (phase, time) register tuple of every mark ahead of the step loop and keeps
+                //  or spills it across the whole kernel -- five 16-byte spills in the benched instantiation)
+                asm volatile("" : "+s"(phase));
+#endif
                 P.prof[2 * prof_cnt] = (unsigned long long)phase;
                 P.prof[2 * prof_cnt + 1] = tm;
             }
@@ -1623,11 +1640,84 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             acc[dt][a0 + 1] = MFMA(w2[dt], t1, acc[dt][a0 + 1]);
                         }
                     };
+#if FD_RELU_CLAMP
+                    // relu + split of the pair tile `gp` (relu_split32 with the relu inside the conversion: 8 conversions, 4 swaps) in the
+                    // shadow of the NM MFMAs of the next H, `mfma(q)` issuing its q-th.  sched_group_barrier does not count inline asm as
+                    // VALU, so the interleave is pinned by source order between sched_barriers: one MFMA, then two VALU statements.
+                    auto split_under = [&](const f32x16& gp, bf16x8& t0, bf16x8& t1, auto&& mfma, auto nmc) {
+                        constexpr int NM = decltype(nmc)::value;
+                        unsigned lo[4], hi[4];
+#pragma unroll
+                        for (int q = 0; q < (NM > 6 ? NM : 6); ++q) {
+                            if (q < NM) mfma(q);
+                            if (q < 6) {
+                                __builtin_amdgcn_sched_barrier(0);
+                                if (q < 4) {
+                                    lo[q] = cvt_pk_bf16_relu01(gp[2 * q], gp[2 * q + 1]);
+                                    hi[q] = cvt_pk_bf16_relu01(gp[8 + 2 * q], gp[8 + 2 * q + 1]);
+                                } else {
+#pragma unroll
+                                    for (int d = 2 * (q - 4); d < 2 * (q - 4) + 2; ++d) {
+                                        const u32x2 r = __builtin_amdgcn_permlane16_swap(lo[d], hi[d], false, false);
+                                        lo[d] = r.x;
+                                        hi[d] = r.y;
+                                    }
+                                }
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
+                        t0 = __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
+                        t1 = __builtin_bit_cast(bf16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+                    };
+                    // the same for the single tile's two 16x16 tiles (relu_pack: 4 conversions); the trailing s_nop 1 stands between the
+                    // last conversion and the W2 MFMA that reads it as its B operand (VALU write -> MFMA read, not padded for inline asm)
+                    auto pack_under = [&](const f32x4& g0, const f32x4& g1, auto&& mfma, auto nmc) -> bf16x8 {
+                        constexpr int NM = decltype(nmc)::value;
+                        unsigned pk[4];
+#pragma unroll
+                        for (int q = 0; q < (NM > 2 ? NM : 2); ++q) {
+                            if (q < NM) mfma(q);
+                            if (q < 2) {
+                                __builtin_amdgcn_sched_barrier(0);
+                                pk[2 * q] = q == 0 ? cvt_pk_bf16_relu01(g0[0], g0[1]) : cvt_pk_bf16_relu01(g1[0], g1[1]);
+                                pk[2 * q + 1] = q == 0 ? cvt_pk_bf16_relu01(g0[2], g0[3]) : cvt_pk_bf16_relu01(g1[2], g1[3]);
+                                if (q == 1 && NM <= 2) asm volatile("s_nop 1");
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
+                        return __builtin_bit_cast(bf16x8, u32x4{pk[0], pk[1], pk[2], pk[3]});
+                    };
+                    auto mfma_pair = [&](int pp) {
+                        return [&, pp](int q) {
+                            if (q == 0) hp = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                            hp = MFMA32(w1[q], xp[pp][q], hp);
+                        };
+                    };
+                    auto mfma_single = [&](int q) {
+                        if constexpr (SINGLE) {
+                            if (q == 0) h0 = f4zero();
+                            if (q == 1) h1 = f4zero();
+                            if (q & 1) h1 = MFMA(w1s[1][q >> 1], xs[q >> 1], h1);
+                            else h0 = MFMA(w1s[0][q >> 1], xs[q >> 1], h0);
+                        }
+                    };
+                    auto no_mfma = [](int) {};
+                    (void)h_single;
+                    using NM_pair = std::integral_constant<int, KS32>;
+                    using NM_single = std::integral_constant<int, 2 * KS1>;
+                    using NM_none = std::integral_constant<int, 0>;
+#endif
                     load_w1(0);
                     load_w1s(0);
                     load_w2(0);
                     h_pair(0);
                     __builtin_amdgcn_sched_barrier(0);
+#if FD_RELU_CLAMP
+                    // the first step converts this H behind ONE MFMA of the next: the XDL write -> VALU read wait states (12 for the
+                    // 8-pass 32x32x16) that every later item gets from the W2 MFMAs of the item in between
+                    asm volatile("s_nop 11");
+                    __builtin_amdgcn_sched_barrier(0);
+#endif
                     constexpr int TREM = (SH::S * SH::KT) % MQ;
                     constexpr bool LIGHT_OK = FD_DMA_LIGHT && (2 * TREM == MQ) && (SH::rot == TREM);
 #if FD_FFN_PRIO
@@ -1643,6 +1733,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             {   // item 0 = pair 0 (H in flight); H of pair 1 shadows its relu, the next step's W1 reads trail its W2
                                 const f32x16 gp = hp;
                                 bf16x8 t0, t1;
+#if FD_RELU_CLAMP
+                                split_under(gp, t0, t1, mfma_pair(1), NM_pair{});
+#else
                                 h_pair(1);
                                 relu_split32(gp, t0, t1);
 #pragma unroll
@@ -1650,6 +1743,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                     SGB(SG_MFMA, 1);
                                     SGB(SG_VALU, 4);
                                 }
+#endif
                                 __builtin_amdgcn_sched_barrier(0);
                                 if (NEXT) load_w1(st + 1);
                                 w2_pair(t0, t1, std::integral_constant<int, 0>{});
@@ -1664,6 +1758,10 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             {   // item 1 = pair 1; H of the next step's pair 0 shadows its relu
                                 const f32x16 gp = hp;
                                 bf16x8 t0, t1;
+#if FD_RELU_CLAMP
+                                if constexpr (NEXT) split_under(gp, t0, t1, mfma_pair(0), NM_pair{});
+                                else split_under(gp, t0, t1, no_mfma, NM_none{});
+#else
                                 if (NEXT) h_pair(0);
                                 relu_split32(gp, t0, t1);
 #pragma unroll
@@ -1671,6 +1769,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                     SGB(SG_MFMA, 1);
                                     SGB(SG_VALU, 4);
                                 }
+#endif
                                 __builtin_amdgcn_sched_barrier(0);
                                 if (dma_now) issue_ffn_half(st + 3);         // (even tile splits: the F-half wave sets take turns)
                                 w2_pair(t0, t1, std::integral_constant<int, 2>{});
@@ -1681,6 +1780,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             {   // item 0 = the pair (H in flight); the single tile's H shadows its relu
                                 const f32x16 gp = hp;
                                 bf16x8 t0, t1;
+#if FD_RELU_CLAMP
+                                split_under(gp, t0, t1, mfma_single, NM_single{});
+#else
                                 h_single();
                                 relu_split32(gp, t0, t1);
 #pragma unroll
@@ -1693,6 +1795,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                     SGB(SG_MFMA, 1);
                                     SGB(SG_VALU, 4);
                                 }
+#endif
                                 __builtin_amdgcn_sched_barrier(0);
                                 if (NEXT) {
                                     load_w1(st + 1);
@@ -1712,6 +1815,11 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                             }
                             {   // item 1 = the single tile; H of the next step's pair shadows its relu, the weight DMA trails its W2
                                 const f32x4 g0 = h0, g1 = h1;
+#if FD_RELU_CLAMP
+                                bf16x8 hb;
+                                if constexpr (NEXT) hb = pack_under(g0, g1, mfma_pair(0), NM_pair{});
+                                else hb = pack_under(g0, g1, no_mfma, NM_none{});
+#else
                                 if (NEXT) h_pair(0);
                                 const bf16x8 hb = relu_pack(g0, g1);
 #pragma unroll
@@ -1720,6 +1828,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                     SGB(SG_VALU, 2);
                                 }
                                 SGB(SG_MFMA, KS32 - 4);
+#endif
                                 __builtin_amdgcn_sched_barrier(0);
                                 if (dma_now) {
                                     issue_ffn_half(st + 3);
@@ -1759,6 +1868,9 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mega(const fd_mega_params P) {
                                 ++st;
                             }
                         }
+#if FD_RELU_CLAMP
+#pragma nounroll   // (two steps: unrolled, hipcc spilled accumulators of the four-tile waves in them)
+#endif
                         for (; st < NS - 1; ++st) step32(st, Fc{}, Tc{});
                         step32(st, Fc{}, Fc{});
                     }

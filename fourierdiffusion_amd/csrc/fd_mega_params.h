@@ -9,7 +9,21 @@
 #ifndef FD_W1_SWAP34
 #define FD_W1_SWAP34 1      // pair-form W1 image rows stored with index bits 3 <-> 4 swapped (LDS bank slots; 0 = natural order, A/B builds)
 #endif
-#define FD_MEGA_FORWARD 0   // one score-network forward: x, tvec -> score_out
+// Pair-form FFN (off_ffn32 image, ffn_loop32): the relu rides in the conversion.  v_cvt_pk_bf16_f32 is VOP3 and its clamp bit clamps
+// the result to [0, 1] (scripts/ubench/cvt_clamp_probe.hip, profiles/cvt_clamp_probe.txt: every non-NaN input, both halves), so with
+// W1 | b1 stored as 2^-k w the hidden value h 2^-k lies in (0, 1] whenever h > 0 and the clamped conversion IS relu + pack; W2 stored
+// as 2^k w undoes the scale inside the second product.  Powers of two commute with bf16 rounding and fp32 accumulation: same bits.
+// k = 40: a hidden pre-activation saturates only at 2^40 (LayerNorm'd inputs of O(1) against weights of O(1) stay below 2^10), and
+// every scaled weight stays a normal bf16 for 2^-86 <= |W1|, |b1| and |W2| < 2^87 -- checked when the image is built; a model that
+// fails gets no pair-form image and runs the 16x16x32 loop.  0 = the relu as v_pk_max_i16 on an unscaled image (A/B builds).
+// Both macros change the image: fd_bf16_image_layout_defines() carries them to the run-time compilation and its cache key.
+#ifndef FD_RELU_CLAMP
+#define FD_RELU_CLAMP 1
+#endif
+#ifndef FD_RELU_CLAMP_SHIFT
+#define FD_RELU_CLAMP_SHIFT 40
+#endif
+#define FD_MEGA_FORWARD 0  // one score-network forward: x, tvec -> score_out
 #define FD_MEGA_SAMPLE 1    // nsteps x {forward, reverse-SDE step}, x updated in place
 #define FD_MEGA_ODE 2       // nsteps x {forward, probability-flow ODE stage}: nsteps counts score evaluations, x updated in place
 

@@ -88,8 +88,17 @@ __device__ void build_ffn_block(const float* __restrict__ W1, const float* __res
 //   j >= DT (dt)  : 16x16x32 A fragment of W2 rows d = 16 dt + (l & 15); k-slot e of lane row q = l >> 4 is hidden unit
 //                   fbase + 16 (q & 1) + 8 (e >> 2) + 4 (q >> 1) + (e & 3): the order in which four v_permlane16_swap leave a
 //                   relu'd 32x32 C tile in the two 16x16x32 B fragments of the pair (relu_split32 in fd_mega.hip)
+//
+// FD_RELU_CLAMP (fd_mega_params.h): W1 | b1 are stored as 2^-k w and W2 as 2^k w, k = FD_RELU_CLAMP_SHIFT, scaled in fp32 before the
+// conversion -- exact, and the same bf16 mantissas, as long as the scaled weight is a normal bf16: 2^(k-126) <= |w| for W1 | b1 (or
+// w == 0) and |w| < 2^(127-k) for W2.  Anything else (non-finite values too) is counted into *bad: fd_bf16_prepare reads the counter
+// back and a model that fails runs without this image (the 16x16x32 loop on the unscaled off_ffn image).
 __device__ void build_ffn32_block(const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ W2,
-                                  __bf16* __restrict__ img, int D, int F, int DT, int blk, int lane) {
+                                  __bf16* __restrict__ img, int D, int F, int DT, int blk, int lane, int* __restrict__ bad) {
+#if FD_RELU_CLAMP
+    const float w1_min = ldexpf(1.f, FD_RELU_CLAMP_SHIFT - 126), w2_lim = ldexpf(1.f, 127 - FD_RELU_CLAMP_SHIFT);
+    int nbad = 0;
+#endif
     const int NB = 2 * DT;
     const int j = blk % NB, fh = (blk / NB) & 1, c = blk / (2 * NB);
     const int fbase = fh * (F / 2) + c * 32;
@@ -102,15 +111,27 @@ __device__ void build_ffn32_block(const float* __restrict__ W1, const float* __r
             float v = 0.f;
             if (k < D) v = W1[(size_t)f * D + k];
             else if (k == D) v = b1[f];
+#if FD_RELU_CLAMP
+            nbad += !(v == 0.f || (fabsf(v) >= w1_min && fabsf(v) <= 3.0e38f));
+            v = ldexpf(v, -FD_RELU_CLAMP_SHIFT);
+#endif
             dst[e] = (__bf16)v;
         }
     } else {
         const int d = 16 * (j - DT) + (lane & 15), q = lane >> 4;
         for (int e = 0; e < 8; ++e) {
             const int f = fbase + 16 * (q & 1) + 8 * (e >> 2) + 4 * (q >> 1) + (e & 3);
-            dst[e] = (__bf16)((d < D) ? W2[(size_t)d * F + f] : 0.f);
+            float v = (d < D) ? W2[(size_t)d * F + f] : 0.f;
+#if FD_RELU_CLAMP
+            nbad += !(fabsf(v) < w2_lim);
+            v = ldexpf(v, FD_RELU_CLAMP_SHIFT);
+#endif
+            dst[e] = (__bf16)v;
         }
     }
+#if FD_RELU_CLAMP
+    if (nbad) atomicAdd(bad, nbad);
+#endif
 }
 
 // ------------------------------------------------------------------ persistent-kernel weight images
@@ -215,6 +236,7 @@ struct fd_img_build {
     const long long* lofs;     // [L][12] fd_layer_off
     char* mimg; size_t off_layers, layer_stride, off_wk, off_wv, off_wq, off_wo, off_ffn, off_lpar, off_ffn32;
     int n_ffn32;               // blocks of the pair-form FFN image per layer (0: not built)
+    int* ffn32_bad;            // FD_RELU_CLAMP: count of pair-form weights outside the range the scaled image can hold
     char* ffn; size_t ffn_layer_bytes;
     char* bimg; size_t b_layer_stride, boff_ffn, boff_wot, boff_win;
     int D, F, H, hd, KS1, DT, KSO, NP;
@@ -258,7 +280,7 @@ __global__ __launch_bounds__(64) void k_build_layer_images(const fd_img_build B)
         return;
     }
     blk -= B.n_lp;
-    if (blk < B.n_ffn32) { build_ffn32_block(P + lo[4], P + lo[5], P + lo[6], (__bf16*)(limg + B.off_ffn32), B.D, B.F, B.DT, blk, lane); return; }
+    if (blk < B.n_ffn32) { build_ffn32_block(P + lo[4], P + lo[5], P + lo[6], (__bf16*)(limg + B.off_ffn32), B.D, B.F, B.DT, blk, lane, B.ffn32_bad); return; }
     blk -= B.n_ffn32;
     if (!B.train) return;
     char* bl = B.bimg + (size_t)l * B.b_layer_stride;
@@ -984,7 +1006,7 @@ int fd_bf16_create(fd_score* m) {
         im->ffn32_layer_bytes = (im->mega && im->ks1 == 3 && im->dt == 5) ? (size_t)2 * (F / 64) * 2 * im->dt * KB : 0;
         im->layer_stride = im->off_ffn32 + im->ffn32_layer_bytes;
         const size_t total = im->off_layers + im->layer_stride * L;
-        if (hipMalloc((void**)&im->mimg, total) != hipSuccess) {
+        if (hipMalloc((void**)&im->mimg, total) != hipSuccess || (im->ffn32_layer_bytes && hipMalloc((void**)&im->ffn32_bad, sizeof(int)) != hipSuccess)) {
             fd_bf16_destroy(m);
             return fd_fail(m->ctx, FD_ERR_HIP, "fd_bf16_create: hipMalloc of the persistent-kernel images failed");
         }
@@ -1030,6 +1052,7 @@ void fd_bf16_destroy(fd_score* m) {
     if (!m->bf16) return;
     if (m->bf16->ffn) (void)hipFree(m->bf16->ffn);
     if (m->bf16->mimg) (void)hipFree(m->bf16->mimg);
+    if (m->bf16->ffn32_bad) (void)hipFree(m->bf16->ffn32_bad);
     if (m->bf16->layer_off_tab) (void)hipFree(m->bf16->layer_off_tab);
     if (m->bf16->bimg) (void)hipFree(m->bf16->bimg);
     if (m->bf16->pimg) (void)hipFree(m->bf16->pimg);
@@ -1057,6 +1080,10 @@ int fd_bf16_prepare(fd_score* m, hipStream_t s, bool training_only, bool ffn32_o
     B.off_wk = im->off_wk; B.off_wv = im->off_wv; B.off_wq = im->off_wq; B.off_wo = im->off_wo; B.off_ffn = im->off_ffn;
     B.off_lpar = im->off_lpar; B.n_lp = im->mimg ? im->nlp : 0;
     B.off_ffn32 = im->off_ffn32; B.n_ffn32 = (im->mega && !training_only) ? (int)(im->ffn32_layer_bytes / 1024) : 0;
+    B.ffn32_bad = im->ffn32_bad;
+    const bool check_ffn32 = FD_RELU_CLAMP && B.n_ffn32 > 0 && im->ffn32_bad && L > 0;
+    if (check_ffn32 && hipMemsetAsync(im->ffn32_bad, 0, sizeof(int), s) != hipSuccess)
+        return fd_fail(m->ctx, FD_ERR_HIP, "fd_bf16_prepare: reset of the pair-form range counter failed");
     B.ffn = im->ffn; B.ffn_layer_bytes = im->ffn_layer_bytes;
     B.bimg = im->bimg; B.b_layer_stride = im->b_layer_stride; B.boff_ffn = im->boff_ffn; B.boff_wot = im->boff_wot; B.boff_win = im->boff_win;
     B.D = D; B.F = F; B.H = H; B.hd = hd; B.KS1 = im->ks1; B.DT = im->dt; B.KSO = im->kso; B.NP = im->np;
@@ -1099,6 +1126,12 @@ int fd_bf16_prepare(fd_score* m, hipStream_t s, bool training_only, bool ffn32_o
                            (__bf16*)(im->mimg + im->off_unemb), im->ks1, C, D, H, hd, D, 1.f);
     }
     FD_LAUNCH_CHECK(m->ctx);
+    if (check_ffn32) {      // one read-back per rebuild of the inference images (a training step's rebuild skips the image and this)
+        int nbad = 0;
+        if (hipMemcpyAsync(&nbad, im->ffn32_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return fd_fail(m->ctx, FD_ERR_HIP, "fd_bf16_prepare: read-back of the pair-form range counter failed");
+        im->ffn32_ok = nbad == 0;
+    }
     return FD_OK;
 }
 
@@ -1195,7 +1228,7 @@ static int fill_mega_params(const fd_score* m, const MegaPlan& pl, int B, fd_meg
     P.layer_stride = im->layer_stride;
     P.off_wk = im->off_wk; P.off_wv = im->off_wv; P.off_wq = im->off_wq; P.off_wo = im->off_wo; P.off_ffn = im->off_ffn;
     P.off_lpar = im->off_lpar; P.nlp = im->nlp;
-    P.off_ffn32 = im->ffn32_layer_bytes ? im->off_ffn32 : 0;
+    P.off_ffn32 = (im->ffn32_layer_bytes && im->ffn32_ok) ? im->off_ffn32 : 0;
     return FD_OK;
 }
 
@@ -1900,4 +1933,6 @@ extern "C" int fd_score_plan(fd_score* m, int B, int mode, char* out /* >= 192 b
 // compilation (fd_mega_rtc.hip) passes them on, so that a variant build of the image builder never meets a default-macro kernel.
 #define FD_STR2(x) #x
 #define FD_STR(x) FD_STR2(x)
-const char* fd_bf16_image_layout_defines() { return "-DFD_W1_SWAP34=" FD_STR(FD_W1_SWAP34); }
+const char* fd_bf16_image_layout_defines() {
+    return "-DFD_W1_SWAP34=" FD_STR(FD_W1_SWAP34) " -DFD_RELU_CLAMP=" FD_STR(FD_RELU_CLAMP) " -DFD_RELU_CLAMP_SHIFT=" FD_STR(FD_RELU_CLAMP_SHIFT);
+}
