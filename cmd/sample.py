@@ -116,6 +116,10 @@ class SamplingRunner:
             labels = torch.cat(lab, dim=0) if lab and all(v is not None for v in lab) else None
         if self.dist.is_main:
             results = {"num_samples": int(X.shape[0]), "sample_mean": float(X.mean()), "sample_std": float(X.std())}
+            info = getattr(self.sampler, "last_info", None)
+            if info is not None:      # sampler=ode_adaptive: what the tolerance cost (this rank's rows)
+                results.update(nfe_mean=float(info.nfe.double().mean()), nfe_max=int(info.nfe.max()),
+                               n_not_converged=int((~info.converged).sum()), row_evals_launched=int(info.row_evals_launched))
             if self.metrics is not None:
                 # reference cmd/sample.py:84-86; the classes the samples were drawn for go to the label-aware metrics only
                 results.update(self.metrics(X, other_labels=labels))

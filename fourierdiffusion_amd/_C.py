@@ -183,6 +183,12 @@ _PROTOS = {
                                      C.c_uint64, C.c_uint64, C.c_int, C.c_int, _vp]),
     "fd_sampler_run_ode_cov": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_int, C.c_int,
                                          _vp]),
+    "fd_sampler_run_ode_adaptive": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                              _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_ode_adaptive_cfg": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                  C.c_int, _vp, _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "fd_sampler_run_ode_adaptive_cov": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                  C.c_int, _vp, _vp, C.c_float, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "fd_prior_logp": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "fd_likelihood_run_adaptive": (C.c_int, [_vp, C.POINTER(SdeParams), _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,

@@ -26,6 +26,9 @@ marginals (Song et al. 2021, Sec. 4.3) by Euler or Heun, the whole loop one engi
 (hydra: ``sampler=ode``).  ``solver="ddim"`` / ``"dpmpp2m"`` sample the same ODE with the data-prediction exponential integrator
 (DPM-Solver++, Lu et al. 2022: one evaluation per step, first order or second-order multistep; fd_sampler_run_dpm), and
 ``schedule="logsnr"`` puts any solver on a grid uniform in the log signal-to-noise ratio (hydra: ``sampler=dpm``).
+``sample_ode_adaptive`` / ``encode_adaptive`` / ``decode_adaptive`` take a tolerance instead of a step count: Dormand-Prince 5(4)
+under the step control of scipy's RK45, every row on its own grid (fd_sampler_run_ode_adaptive; ``AdaptiveODESampler``, hydra:
+``sampler=ode_adaptive``); they evaluate the network step by step and report what the tolerance cost (``ODEInfo``).
 
 Likelihood (an extension, not in the reference): ``log_likelihood`` evaluates log p(x) under the probability-flow ODE
 (Song et al. 2021, Sec. 4.3, App. D.2): the ODE runs data -> latents with the divergence integral along it, one engine call
@@ -72,6 +75,23 @@ class SMCInfo:
     resampled: torch.Tensor
     ancestors: torch.Tensor
     degenerate: torch.Tensor
+
+
+@dataclass
+class ODEInfo:
+    """What the adaptive ODE calls (``sample_ode_adaptive``, ``encode_adaptive``, ``decode_adaptive``) report with return_info, for
+    n rows (CPU tensors).  nfe (n,) int64: score evaluations as scipy's nfev (2 + 6 per attempted step); converged (n,) bool;
+    status (n,) int64: 1 converged, 2 step under scipy's min_step, 3 the next attempt would pass max_evals; grid (n, S) float64: the
+    accepted times, the start first, NaN-padded; rtol, atol: as given; row_evals_launched: the state rows the engine launched,
+    summed over the evaluations of every launch; row_evals_needed = nfe.sum(), what the rows themselves consumed."""
+    nfe: torch.Tensor
+    converged: torch.Tensor
+    status: torch.Tensor
+    grid: torch.Tensor
+    rtol: float
+    atol: float
+    row_evals_launched: int
+    row_evals_needed: int
 
 
 class DiffusionSampler:
@@ -254,7 +274,8 @@ class DiffusionSampler:
         if solver in self._DPM_SOLVERS:
             raise ValueError(f"solver {solver!r} integrates from noise to data only (sample_ode, decode); encode takes "
                              f"{sorted(self._SOLVERS)}")
-        hint = " (rk45 is available for log_likelihood only)" if solver == "rk45" else ""
+        hint = (" (rk45 takes a tolerance, not a step count: sample_ode_adaptive, encode_adaptive, decode_adaptive; "
+                "log_likelihood(solver='rk45'))") if solver == "rk45" else ""
         allowed = sorted(self._SOLVERS) + (sorted(self._DPM_SOLVERS) if dpm else [])
         raise ValueError(f"solver must be one of {allowed}, got {solver!r}{hint}")
 
@@ -315,6 +336,130 @@ class DiffusionSampler:
             rc = run(h, C.byref(p), G.data_ptr(), ts_arr, N, sid, X.data_ptr(), bs, mode, _C.stream_of(X))
         _C.check(rc, ctx)
         return X[:bs]
+
+    # ------------------------------------------------------------ adaptive ODE (extension, not in the reference)
+    def sample_ode_adaptive(self, num_samples: int, rtol: float = 1e-5, atol: float = 1e-5, max_evals: int = RK45_MAX_EVALS,
+                            prior_noise: Optional[Sequence[torch.Tensor]] = None, y=None, cfg_scale: float = 1.0,
+                            return_info: bool = False, compact_granule: int = 0):
+        """Samples by the probability-flow ODE from t = 1 to t = eps with Dormand-Prince 5(4) under the step control of scipy's
+        RK45 (Song et al. 2021's black-box sampler; fd_sampler_run_ode_adaptive): a tolerance instead of a step count, every row
+        on its own grid, at most ``max_evals`` score evaluations per row.  Launches are the reference's batches of
+        ``sample_batch_size`` rows (half of that for a guided loop in its two-evaluation form); nothing is merged, the loop
+        evaluates the network step by step.  prior_noise[b], y, cfg_scale as ``sample_ode``.  compact_granule: rows by which the
+        running count must fall before the launches shrink to the running rows (0: FDIFF_RK_COMPACT_GRANULE, else the engine's
+        default -- 1 for the transformer in fp32, off otherwise, by measurement: DESIGN 3.37; guided calls never compact).
+        Returns a CPU tensor (n, max_len, n_channels); with return_info, (samples, ODEInfo).  Without it a row that did not
+        converge raises RuntimeError."""
+        t0, rtol, atol, max_evals = self._adaptive_plan(rtol, atol, max_evals)
+        guided, pair = self._guided(y, cfg_scale)
+        bs = self.sample_batch_size
+        sizes = [min(num_samples - b * bs, bs) for b in range(max(1, num_samples // bs))]
+        if pair and prior_noise is None:
+            half = max(1, bs // 2)
+            sizes = [min(half, n - lo) for n in sizes for lo in range(0, n, half)]
+        labels = self._labels(y, sum(sizes)) if guided else None
+        out, infos, lo = [], [], 0
+        for b, nb in enumerate(sizes):
+            X = self.sample_prior(nb, noise=None if prior_noise is None else prior_noise[b])
+            yb = None if labels is None else labels[lo:lo + nb].contiguous()
+            lo += nb
+            infos.append(self._run_ode_adaptive(X, 1.0, t0, rtol, atol, max_evals, yb, float(cfg_scale), guided, compact_granule))
+            out.append(X.cpu())
+        return self._adaptive_result(out, infos, rtol, atol, max_evals, return_info, "sample_ode_adaptive")
+
+    def encode_adaptive(self, X: torch.Tensor, rtol: float = 1e-5, atol: float = 1e-5, max_evals: int = RK45_MAX_EVALS,
+                        return_info: bool = False, y=None, cfg_scale: float = 1.0, compact_granule: int = 0):
+        """Latents of X (n, max_len, n_channels): the probability-flow ODE from t = eps to t = 1 to the tolerance rtol / atol
+        (``sample_ode_adaptive``'s integrator, run upward).  y (one label / covariate row per series) and cfg_scale encode along the
+        guided field.  Returns a CPU tensor, or (latents, ODEInfo)."""
+        return self._map_ode_adaptive(X, True, rtol, atol, max_evals, return_info, y, cfg_scale, compact_granule, "encode_adaptive")
+
+    def decode_adaptive(self, latents: torch.Tensor, rtol: float = 1e-5, atol: float = 1e-5, max_evals: int = RK45_MAX_EVALS,
+                        return_info: bool = False, y=None, cfg_scale: float = 1.0, compact_granule: int = 0):
+        """Series from latents at t = 1: the same integration from t = 1 down to t = eps (``sample_ode_adaptive`` from given
+        latents).  Returns a CPU tensor, or (series, ODEInfo)."""
+        return self._map_ode_adaptive(latents, False, rtol, atol, max_evals, return_info, y, cfg_scale, compact_granule,
+                                      "decode_adaptive")
+
+    def _adaptive_plan(self, rtol, atol, max_evals) -> tuple:
+        """Validates the tolerances of the adaptive calls before any engine work: (eps, rtol, atol, max_evals)."""
+        def number(v):
+            try:
+                return None if isinstance(v, bool) else float(v)
+            except (TypeError, ValueError):
+                return None
+        for name, v in (("rtol", rtol), ("atol", atol)):
+            f = number(v)
+            if f is None or not math.isfinite(f) or not f > 0:
+                raise ValueError(f"{name} must be a finite number > 0, got {v!r}")
+        f = number(max_evals)
+        if f is None or not math.isfinite(f) or f != int(f) or f < 8:
+            raise ValueError(f"max_evals must be an integer >= 8 (the initial step and one attempt), got {max_evals!r}")
+        sch = self.noise_scheduler
+        if sch.G is None:
+            raise RuntimeError("the noise scheduler has no noise scaling yet (set_noise_scaling)")
+        eps = float(sch.eps)
+        if not (math.isfinite(eps) and eps < 1.0):
+            raise ValueError(f"the adaptive ODE integrates between eps and 1: need eps < 1, got {sch.eps}")
+        return eps, float(rtol), float(atol), int(max_evals)
+
+    def _map_ode_adaptive(self, X, to_noise, rtol, atol, max_evals, return_info, y, cfg_scale, compact_granule, who):
+        eps, rtol, atol, max_evals = self._adaptive_plan(rtol, atol, max_evals)
+        n = self._check_series(X, "X" if to_noise else "latents")
+        guided, pair = self._guided(y, cfg_scale)
+        labels = self._labels(y, n) if guided else None
+        dev = self.score_model.device
+        per = max(1, self.sample_batch_size // 2) if pair else self.sample_batch_size
+        t0, t1 = (eps, 1.0) if to_noise else (1.0, eps)
+        out, infos = [], []
+        for lo in range(0, n, per):
+            xb = X[lo:lo + per].to(device=dev, dtype=torch.float32).contiguous().clone()
+            yb = None if labels is None else labels[lo:lo + per].contiguous()
+            infos.append(self._run_ode_adaptive(xb, t0, t1, rtol, atol, max_evals, yb, float(cfg_scale), guided, compact_granule))
+            out.append(xb.cpu())
+        return self._adaptive_result(out, infos, rtol, atol, max_evals, return_info, who)
+
+    def _run_ode_adaptive(self, X, t0, t1, rtol, atol, max_evals, yb, w, guided, compact_granule):
+        """One launch: X (bs,T,C) device float32 integrated in place from t0 to t1; (nfe, status, grid, row-evaluations launched)."""
+        self.score_model.eval()
+        ctx, h, p, G, mode = self._engine_args()
+        bs, gcap = X.shape[0], 1 + (max_evals - 2) // 6
+        nfe = torch.empty(bs, device=X.device, dtype=torch.int32)
+        st = torch.empty(bs, device=X.device, dtype=torch.int32)
+        grid = torch.empty((bs, gcap), device=X.device, dtype=torch.float64)
+        launched = C.c_longlong(0)
+        head = (h, C.byref(p), G.data_ptr(), t0, t1, rtol, atol, max_evals, X.data_ptr())
+        tail = (C.byref(launched), bs, mode, _C.stream_of(X))
+        if guided:
+            run = _C.lib().fd_sampler_run_ode_adaptive_cov if self.score_model.cond_dim > 0 else _C.lib().fd_sampler_run_ode_adaptive_cfg
+            rc = run(*head, _C.ptr(yb), w, nfe.data_ptr(), st.data_ptr(), grid.data_ptr(), gcap, *tail)
+        else:
+            rc = _C.lib().fd_sampler_run_ode_adaptive(*head, nfe.data_ptr(), st.data_ptr(), grid.data_ptr(), gcap, int(compact_granule),
+                                                      *tail)
+        _C.check(rc, ctx)
+        return nfe.cpu(), st.cpu(), grid.cpu(), int(launched.value)
+
+    @staticmethod
+    def _adaptive_result(out, infos, rtol, atol, max_evals, return_info, who):
+        X = torch.cat(out, dim=0)
+        status = torch.cat([i[1] for i in infos]).to(torch.int64)
+        converged = status == 1
+        if not return_info:
+            bad = int((~converged).sum())
+            if bad:
+                raise RuntimeError(f"{who}: {bad} of {converged.numel()} rows did not converge within max_evals={max_evals} evaluations "
+                                   f"at rtol={rtol}, atol={atol} (return_info=True returns their last accepted states and statuses)")
+            return X
+        width = max(int((~torch.isnan(i[2])).sum(dim=1).max()) for i in infos)
+        grid = torch.full((X.shape[0], width), float("nan"), dtype=torch.float64)
+        lo = 0
+        for i in infos:
+            w_i = min(width, i[2].shape[1])
+            grid[lo:lo + i[2].shape[0], :w_i] = i[2][:, :w_i]
+            lo += i[2].shape[0]
+        nfe = torch.cat([i[0] for i in infos]).to(torch.int64)
+        return X, ODEInfo(nfe=nfe, converged=converged, status=status, grid=grid, rtol=rtol, atol=atol,
+                          row_evals_launched=sum(i[3] for i in infos), row_evals_needed=int(nfe.sum()))
 
     # ------------------------------------------------------------ likelihood (extension, not in the reference)
     _LL_SOLVERS = {"euler": 0, "heun": 1, "rk45": 2}
@@ -1224,3 +1369,23 @@ class ODESampler(DiffusionSampler):
                prior_noise: Optional[Sequence[torch.Tensor]] = None, y=None, cfg_scale: float = 1.0) -> torch.Tensor:
         return self.sample_ode(num_samples, num_diffusion_steps, solver=self.solver, prior_noise=prior_noise, schedule=self.schedule,
                                y=y, cfg_scale=cfg_scale)
+
+
+class AdaptiveODESampler(DiffusionSampler):
+    """A DiffusionSampler whose ``sample`` integrates the probability-flow ODE to a tolerance (``sample_ode_adaptive``: Dormand-Prince
+    5(4) under scipy's RK45 step control) instead of over a step count: ``python cmd/sample.py sampler=ode_adaptive
+    sampler.rtol=1e-3 sampler.atol=1e-3``.  ``num_diffusion_steps`` is ignored.  ``last_info`` holds the ODEInfo of the last call (a
+    row that did not converge is reported there -- cmd/sample.py writes ``n_not_converged`` -- rather than raised)."""
+
+    def __init__(self, score_model: ScoreModule, sample_batch_size: int, rtol: float = 1e-5, atol: float = 1e-5,
+                 max_evals: int = RK45_MAX_EVALS, cfg_scale: float = 1.0, labels=None, covariates=None) -> None:
+        super().__init__(score_model=score_model, sample_batch_size=sample_batch_size, merge_batches=False, cfg_scale=cfg_scale,
+                         labels=labels, covariates=covariates)
+        _, self.rtol, self.atol, self.max_evals = self._adaptive_plan(rtol, atol, max_evals)
+        self.last_info: Optional[ODEInfo] = None
+
+    def sample(self, num_samples: int, num_diffusion_steps: Optional[int] = None,
+               prior_noise: Optional[Sequence[torch.Tensor]] = None, y=None, cfg_scale: float = 1.0) -> torch.Tensor:
+        X, self.last_info = self.sample_ode_adaptive(num_samples, rtol=self.rtol, atol=self.atol, max_evals=self.max_evals,
+                                                     prior_noise=prior_noise, y=y, cfg_scale=cfg_scale, return_info=True)
+        return X

@@ -673,6 +673,41 @@ int fd_sampler_run_cov(fd_score* m, const fd_sde_params* sde, const float* G, co
 int fd_sampler_run_ode_cov(fd_score* m, const fd_sde_params* sde, const float* G, const float* timesteps, int n_steps, int solver,
                            float* x, const float* c, float w, int B, int mode, void* stream);
 
+/* Adaptive ODE sampling, encoding and decoding (NOT in the reference; Song et al. 2021's black-box RK45 sampler):
+ *   fd_sampler_run_ode_adaptive: integrates every row of x (B,T,C) in place from t0 to t1 (finite, t0 != t1: t0 > t1 samples /
+ *                      decodes, t0 < t1 encodes; FD_ERR_ARG otherwise) by Dormand-Prince 5(4) with the step control of
+ *                      scipy.integrate.RK45 as fd_likelihood_run_adaptive below states it, with scipy's `direction`: t_new = t +
+ *                      direction h_abs, clamped when direction (t_new - t1) > 0, min_step = 10 |nextafter(t, direction inf) - t|.
+ *                      The state is the T*C values alone (RMS error norm over them).  Each row has its own grid; a row that stops
+ *                      early keeps its last accepted state.  Device outputs: nfe_out[b] scipy's nfev (2 + 6 per attempted step),
+ *                      status_out[b] 1 converged, 2 step under min_step, 3 the next attempt would pass max_evals (>= 8); grid_out
+ *                      (nullable) (B, grid_cap) doubles: the accepted times, t0 first, NaN-padded, grid_cap >= 1 + (max_evals - 2)
+ *                      / 6.  rtol, atol > 0.  Every evaluation is the sampler's forward (mode: FD_MODE_F32 exact, FD_MODE_BF16 the
+ *                      per-layer bf16 kernels) + one stage kernel; controller float64 per row, x and the stage vectors fp32;
+ *                      fixed-order reductions: bit-reproducible.
+ *                      Compaction: the forward runs on the rows still running once the count the host has read (one attempt late)
+ *                      is below the launched rows by compact_granule rows; compact_granule 0: FDIFF_RK_COMPACT_GRANULE, else the
+ *                      library's default (1 for the transformer in FD_MODE_F32, else off: measured); FDIFF_RK_COMPACT=0 keeps
+ *                      every launch at B rows.  Which evaluations a row sees does not depend on it (the bf16 kernels round a row
+ *                      differently at a different row count, as for any change of B).  *row_evals_out (HOST, nullable): the
+ *                      state rows launched, summed over the evaluations.
+ *                      The state lives in a context-owned buffer outside the workspace (grown on first use: synchronising).
+ *                      SYNCHRONISES the stream once per attempted step, as fd_likelihood_run_adaptive.
+ *   fd_sampler_run_ode_adaptive_cfg / _cov: the same under classifier-free guidance, y / c and w as fd_sampler_run_ode_cfg / _cov.
+ *                      x stays (B,T,C) in every form: the pair form runs one forward on 2B rows of the loop's own input buffer and
+ *                      the stage kernel combines the two halves of the score.  Guided loops run uncompacted (so does the plain
+ *                      entry point when labels or covariates are bound to the model); row_evals_out counts state rows, each of
+ *                      which is two network rows in the pair form. */
+int fd_sampler_run_ode_adaptive(fd_score* m, const fd_sde_params* sde, const float* G, double t0, double t1, double rtol, double atol,
+                                int max_evals, float* x, int* nfe_out, int* status_out, double* grid_out, int grid_cap,
+                                int compact_granule, long long* row_evals_out, int B, int mode, void* stream);
+int fd_sampler_run_ode_adaptive_cfg(fd_score* m, const fd_sde_params* sde, const float* G, double t0, double t1, double rtol,
+                                    double atol, int max_evals, float* x, const int32_t* y, float w, int* nfe_out, int* status_out,
+                                    double* grid_out, int grid_cap, long long* row_evals_out, int B, int mode, void* stream);
+int fd_sampler_run_ode_adaptive_cov(fd_score* m, const fd_sde_params* sde, const float* G, double t0, double t1, double rtol,
+                                    double atol, int max_evals, float* x, const float* c, float w, int* nfe_out, int* status_out,
+                                    double* grid_out, int grid_cap, long long* row_evals_out, int B, int mode, void* stream);
+
 /* Likelihood extension (NOT in the reference; Song et al. 2021, Sec. 4.3 and App. D.2): the exact log-density of the
  * probability-flow ODE above,
  *   log p_0(x_0) = log p_1(x_1) + int_eps^1 div v(x(t), t) dt,   div v = -a T C - 0.5 g^2 tr(diag(G_k^2) ds/dx)

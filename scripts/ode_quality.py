@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sample quality against the number of score evaluations: reverse-SDE sampling (Euler-Maruyama, the reference's sampler) against the
-probability-flow ODE (Heun, Euler, deterministic DDIM, DPM-Solver++ 2M; on the time-uniform grid and on the log-SNR grid) on one
-trained model.
+probability-flow ODE (Heun, Euler, deterministic DDIM, DPM-Solver++ 2M; on the time-uniform grid and on the log-SNR grid; and the
+adaptive Dormand-Prince sampler at rtol = atol = 1e-3 and 1e-5, the ODE's own solution to that tolerance) on one trained model.
 
 A default-width transformer (D = 72, L = 10, H = 12, VP-SDE, Fourier noise scaling) is trained on SyntheticDatamodule (sines, generated
 locally from the seed; frequency domain, standardised), then every sampler draws `--num-samples` series; the series are mapped back to
@@ -28,6 +28,9 @@ ROWS = [("sde", 1000), ("sde", 100), ("sde", 50), ("heun", 10), ("heun", 25), ("
 ROWS = [(k, n, "time") for k, n in ROWS] + \
        [(k, n, sc) for k in ("ddim", "dpmpp2m") for sc in ("time", "logsnr") for n in (10, 15, 20, 30, 50)] + \
        [("heun", 10, "logsnr"), ("heun", 25, "logsnr"), ("heun", 50, "logsnr"), ("euler", 50, "logsnr"), ("euler", 100, "logsnr")]
+# the adaptive sampler (Dormand-Prince 5(4), sample_ode_adaptive) at rtol = atol: the ODE's own solution to that tolerance, the point
+# the fixed-grid ODE rows converge to; evaluations are per row (nfe mean / max), launches of `--adaptive-batch` rows
+RK45_TOLS = (1e-3, 1e-5)
 
 
 def main() -> None:
@@ -40,6 +43,7 @@ def main() -> None:
     ap.add_argument("--C", type=int, default=4)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--adaptive-batch", type=int, default=512)
     args = ap.parse_args()
     from fourierdiffusion_amd.dataloaders.datamodules import SyntheticDatamodule
     from fourierdiffusion_amd.models.score_models import ScoreModule
@@ -90,6 +94,23 @@ def main() -> None:
         rec = {"sampler": kind, "schedule": schedule, "steps": N, "evals": N * (2 if kind == "heun" else 1),
                "ms_per_series": 1e3 * sec / X.shape[0],
                **sw(Xt), **mw(Xt), "finite": bool(torch.isfinite(Xt).all())}
+        print(json.dumps(rec), flush=True)
+        rows.append(rec)
+    adaptive = DiffusionSampler(score_model=model, sample_batch_size=args.adaptive_batch)
+    for tol in RK45_TOLS:
+        torch.manual_seed(args.seed)
+        run = lambda: adaptive.sample_ode_adaptive(args.num_samples, rtol=tol, atol=tol, return_info=True)      # noqa: E731
+        run()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        X, info = run()
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        Xt = destandardize_idft(X, mean, std)
+        rec = {"sampler": "rk45", "schedule": "adaptive", "rtol": tol, "atol": tol, "evals": float(info.nfe.double().mean()),
+               "nfe_max": int(info.nfe.max()), "n_not_converged": int((~info.converged).sum()),
+               "row_evals_launched": info.row_evals_launched, "row_evals_needed": info.row_evals_needed,
+               "ms_per_series": 1e3 * sec / X.shape[0], **sw(Xt), **mw(Xt), "finite": bool(torch.isfinite(Xt).all())}
         print(json.dumps(rec), flush=True)
         rows.append(rec)
     if args.out:
