@@ -576,6 +576,29 @@ def engine_philox_words(seed: int, offset: int, n: int) -> Array:
     return philox4x32_10(counter, key)
 
 
+def engine_u01(words: Array) -> Array:
+    """fd_u01, in float32 exactly as the header spells it: (float(word >> 8) + 0.5f) * 2^-24.  For word >> 8 >= 2^23 the sum is
+    not representable and rounds to even, so the upper half of the range holds only multiples of 2^-23 and word >> 8 == 0xFFFFFF
+    gives exactly 1.0; the smallest value is 0.5 * 2^-24.  Returns float32."""
+    top = (np.asarray(words, dtype=np.uint32) >> np.uint32(8)).astype(np.float32)     # 24 bits: exact in float32
+    return ((top + np.float32(0.5)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+
+
+def engine_randn(seed: int, offset: int, n: int) -> Array:
+    """What fd_randn(seed, offset, n) draws, in float64 from the float32 uniforms: element e takes counter offset + e // 4 and lane
+    e % 4; words (x, y) of a counter give elements 0, 1 = r cos(2 pi u2), r sin(2 pi u2) with u1 = u01(x), u2 = u01(y),
+    r = sqrt(-2 ln u1); words (z, w) give elements 2, 3 the same way.  u1 == 1.0 gives (+0, +-0)."""
+    ng = (n + 3) // 4
+    u = engine_u01(engine_philox_words(seed, offset, ng)).astype(np.float64)          # (ng, 4)
+    out = np.empty((ng, 4), dtype=np.float64)
+    for a in (0, 2):
+        r = np.sqrt(-2.0 * np.log(u[:, a]))
+        ang = 2.0 * np.pi * u[:, a + 1]
+        out[:, a] = r * np.cos(ang)
+        out[:, a + 1] = r * np.sin(ang)
+    return out.reshape(-1)[:n]
+
+
 def dropout_decisions16(words: Array, p: float) -> Array:
     """fd_drop16: (n, 4) uint32 generator output -> (n,) uint16, bit e = keep decision e: the 16-bit little-endian window at
     byte offset e of the 128-bit output (wrapping) >= thr16 = round(p * 65536)."""
