@@ -24,6 +24,7 @@ FD_VARIOGRAM_HALF, FD_VARIOGRAM_ONE, FD_VARIOGRAM_TWO = 0, 1, 2
 FD_PRERANK_AVERAGE, FD_PRERANK_BAND_DEPTH, FD_PRERANK_DOMINANCE, FD_PRERANK_MST = 0, 1, 2, 3
 FD_POSTHOC_CLASSIFY, FD_POSTHOC_PREDICT = 0, 1
 FD_POSTHOC_MAX_CLASSES = 256
+FD_SIG_BASEPOINT, FD_SIG_LEAD_LAG, FD_SIG_TIME = 1, 2, 4
 
 
 class FdError(RuntimeError):
@@ -243,6 +244,9 @@ _PROTOS = {
     "fd_series_spectra_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fd_series_spectra": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                     C.c_size_t, _vp]),
+    "fd_series_signature_workspace_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fd_series_signature": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                      _vp]),
     "fd_posthoc_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int,
                                    C.c_int, _vp, _vp, _vp, _vp]),
     "fd_posthoc_head": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),

@@ -14,7 +14,8 @@ and kurtosis between the samples and the real set; and `DiscriminativeScore` / `
 and TSGBench (utils/posthoc.py): a small causal LSTM trained on the engine after the fact, to tell the samples from real series, and
 to forecast real series after training on the samples; and `ClassificationScore`, the first metric that reads a LABEL (TSTR / TRTS
 classification accuracy, utils/posthoc.py): a K-way classifier trained after the fact on the samples with the classes they were drawn
-for and tested on real series, and the other way round."""
+for and tested on real series, and the other way round; and `SignatureDistance`, the first metric that reads the ORDER of events inside a
+series (utils/signature.py): Sig-W1 and the signature MMD between the expected path signatures of the two sets."""
 from __future__ import annotations
 
 import inspect
@@ -33,6 +34,9 @@ from ..utils.neighbours import MAX_K, ball_counts, knn
 from ..utils.posthoc import MAX_CLASSES as POSTHOC_MAX_CLASSES
 from ..utils.posthoc import MAX_D_MODEL as POSTHOC_MAX_D_MODEL
 from ..utils.posthoc import discriminative_score, fit_classifier, predictive_score
+from ..utils.signature import _series_shape as signature_shape
+from ..utils.signature import check_options as signature_options
+from ..utils.signature import expected_signature_distance, series_signature
 from ..utils.sinkhorn import DEFAULT_REG, sinkhorn_divergence
 from ..utils.spectral import check_options as spectral_options
 from ..utils.spectral import pair_indices, resolve_segments, series_spectra
@@ -731,6 +735,88 @@ class SpectralDependence(Metric):
     @property
     def name(self) -> str:
         return "spectral_dependence"
+
+
+class SignatureDistance(Metric):
+    """Does the generator reproduce the ORDER of events inside a series?  The path signature of every series (utils/signature.py): the
+    iterated integrals up to `depth` of the path through its points -- level 2 holds the Levy areas (which channel leads which), the
+    levels above asymmetries in time that no autocorrelation, spectrum or marginal sees (a series played backwards keeps all three).
+    Between the samples and the real set,
+      sig_w1            ||E S(samples) - E S(real)||_2, the Sig-W1 distance of Ni et al. 2021
+      sig_w1_levels     the same norm level by level (a list of `depth` values)
+      sig_mmd2          the unbiased MMD^2 under the linear kernel on signatures (Chevyrev & Oberhauser): it can be slightly negative
+      ..._holdout       (with `holdout_samples`) against real series the model was not trained on
+      ..._self          (baseline) the two folds of the original samples
+    `time_augment` appends a time channel (without it the signature does not see the speed along the path), `basepoint` starts every
+    path at 0 so that the starting value counts, `lead_lag` doubles the channels into lead and lag copies (the quadratic variation
+    shows at level 2); `path_scale` multiplies every channel.  With `standardise` every set is centred and scaled per channel by the
+    pooled mean and 1 / deviation of the ORIGINAL samples, computed once here in float64; a constant channel gets scale 0 and
+    contributes exact zeros.  The real set's signature statistics are computed once, here.  No p-value is computed:
+    `mmd_permutation_test(sig_a, sig_b)` on the feature rows of `series_signature(..., per_series=("sig",))` already gives one.
+    Needs (n, T, C) original samples: bound in the time view only."""
+    views = ("time",)
+
+    def __init__(self, original_samples: np.ndarray | torch.Tensor, holdout_samples: Optional[np.ndarray | torch.Tensor] = None,
+                 depth: int = 3, time_augment: bool = True, basepoint: bool = False, lead_lag: bool = False, path_scale: float = 1.0,
+                 standardise: bool = True) -> None:
+        if len(tuple(original_samples.shape)) != 3:
+            raise ValueError(f"SignatureDistance needs the original samples as (n, T, C) series, got shape "
+                             f"{tuple(original_samples.shape)}: a flat (n, d) array has lost its time axis")
+        n, T, C = signature_shape(original_samples, "original samples")
+        self.series_shape = (T, C)
+        self.depth, self.d, self.features = signature_options(n, C, depth, time_augment, lead_lag)
+        self.time_augment, self.basepoint, self.lead_lag = bool(time_augment), bool(basepoint), bool(lead_lag)
+        self.path_scale, self.standardise = path_scale, bool(standardise)
+        if holdout_samples is not None:
+            if len(holdout_samples) < 1:
+                raise ValueError("SignatureDistance needs at least one held-out sample")
+            if int(np.prod(tuple(holdout_samples.shape)[1:])) != T * C:
+                raise ValueError("original and held-out samples must have the same number of features")
+        super().__init__(original_samples=original_samples)
+        self.channel_offset = self.channel_scale = None
+        if self.standardise:
+            x = self.original_samples.cpu().numpy().astype(np.float64).reshape(-1, C)
+            self.channel_offset = x.mean(axis=0)
+            sd = x.std(axis=0)
+            self.channel_scale = np.where(sd > 0, 1.0 / np.where(sd > 0, sd, 1.0), 0.0)
+        self._real = self._features(self.original_samples)
+        self._held = self._features(check_flat_array(holdout_samples)) if holdout_samples is not None else None
+        self._folds = None
+        if n // 2 >= 1:
+            self._folds = (self._features(self.original_samples[: n // 2].contiguous()),
+                           self._features(self.original_samples[n // 2:].contiguous()))
+        self._baseline: Optional[dict[str, Any]] = None
+
+    def _features(self, rows: torch.Tensor):
+        T, C = self.series_shape
+        if rows.dim() != 2 or rows.shape[1] != T * C:
+            raise ValueError(f"samples of {tuple(rows.shape[1:])} features, the original samples are series of shape {(T, C)}")
+        return series_signature(rows.view(rows.shape[0], T, C), depth=self.depth, time_augment=self.time_augment,
+                                basepoint=self.basepoint, lead_lag=self.lead_lag, channel_offset=self.channel_offset,
+                                channel_scale=self.channel_scale, path_scale=self.path_scale)
+
+    @staticmethod
+    def _compare(samples, real, suffix: str) -> dict[str, Any]:
+        return {f"{key}{suffix}": val for key, val in expected_signature_distance(samples, real).items()}
+
+    def __call__(self, other_samples: np.ndarray | torch.Tensor) -> dict[str, Any]:
+        samples = self._features(check_flat_array(other_samples))
+        out = self._compare(samples, self._real, "")
+        if self._held is not None:
+            out.update(self._compare(samples, self._held, "_holdout"))
+        return out
+
+    @property
+    def baseline_metrics(self) -> dict[str, Any]:
+        if self._folds is None:
+            return {}
+        if self._baseline is None:                                    # two folds of the original samples, as the Wasserstein metrics
+            self._baseline = self._compare(self._folds[0], self._folds[1], "_self")
+        return dict(self._baseline)
+
+    @property
+    def name(self) -> str:
+        return "signature_distance"
 
 
 class _PosthocScore(Metric):

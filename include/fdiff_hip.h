@@ -1110,6 +1110,44 @@ int fd_series_spectra(fd_ctx* ctx, const float* x, int n, int T, int C, int nper
                       float* out_summary /* (n, C, 3) or NULL */, double* out_set_mean /* (F) */, void* work, size_t work_bytes,
                       void* stream);
 
+/* Path signatures (NOT in the reference; Sig-W1 of Ni et al. 2021, the signature MMD of Chevyrev & Oberhauser; the metrics are host
+ * arithmetic on the outputs, utils/signature.py): the iterated integrals up to depth m of the piecewise linear path
+ * through a series.  x (n, T, C) dense row-major fp32 device series with finite entries, n >= 1, 2 <= T <= 1024, 1 <= C <= 64,
+ * 1 <= depth <= 6; channel_offset, channel_scale (C) device DOUBLES or NULL (0 and 1).  The path, in this order:
+ *   1. p[t, c] = scale_c (x[t, c] - offset_c), in double
+ *   2. FD_SIG_BASEPOINT: the point 0 is prepended (the signature then sees the starting value, not only the increments)
+ *   3. D[s] = p[s + 1] - p[s] over S = T - 1 segments (T with a basepoint)
+ *   4. FD_SIG_LEAD_LAG: 2 S segments over 2 C channels [lead_0..lead_{C-1}, lag_0..lag_{C-1}]; segment 2 k moves the lead channels by
+ *      D[k], segment 2 k + 1 the lag channels by D[k]
+ *   5. FD_SIG_TIME: one last channel that moves by 1.0 / S' per segment, S' the final number of segments
+ * d = the final channel count, D = d + d^2 + ... + d^depth <= 8192 features: levels 1..depth concatenated, a level row-major over its
+ * words with the first letter slowest.  Per segment and level-k word w (Chen's identity with the exponential of a linear segment, in
+ * Horner form; every read is of the state before the segment):
+ *   acc = D[w_1] / k;   acc = (acc + S_j[w_1..w_j]) D[w_{j+1}] / (k - j) for j = 1..k-1;   S_k[w] += acc
+ *   sig    (n, D) fp32 or NULL      the state after the last segment, rounded once
+ *   sqnorm (n) DOUBLES or NULL      sum_w S_w^2 of the double state
+ *   mean   (D) DOUBLES, required    the mean over the n series of the double state
+ * Arithmetic (csrc/fd_signature.hip).  The state and every operation are double, nothing is contracted into an fma: a repeated point
+ * (a zero increment) leaves every bit of the state alone unless FD_SIG_TIME is set, and a channel with scale 0 gives exact zeros in
+ * every word that holds its letter.  With u = 2^-53, l = sum_s ||D[s]||_1 and M_k = l^k / k!, a level-k entry is within
+ * b_k = 32 S' u M_k of the exact value of the float64 path (tests/signature_ref.py; DESIGN.md 3.39 derives it).
+ * Pure function per series: a series' sig and sqnorm depend on that series, (T, C, depth, flags) and the offsets and scales alone --
+ * not on n, its position, the grid or which outputs are asked for.
+ * Set mean: series are cut into chunks of 32; a chunk's states are added in double in series order by the one thread that owns the
+ * word, the chunk sums go to work, a second kernel adds the chunks of every 64 in chunk order and a third those sums in order: a
+ * grouping that depends on n alone.  No atomics: bit-identical between runs and for every grid (FDIFF_SIG_SPLITS forces the workgroup
+ * count).  work: caller-owned device bytes, at least fd_series_signature_workspace_bytes of the same shape.
+ * FD_ERR_ARG (nothing is launched): null x, n < 1, T < 2, C < 1, T > 1024 or C > 64, depth outside [1, 6], flags outside [0, 7],
+ * D > 8192, n D or n T C >= 2^31, null mean, a workspace that is null or too small. */
+#define FD_SIG_BASEPOINT 1
+#define FD_SIG_LEAD_LAG 2
+#define FD_SIG_TIME 4
+int fd_series_signature_workspace_bytes(fd_ctx* ctx, int n, int T, int C, int depth, int flags, size_t* bytes);
+int fd_series_signature(fd_ctx* ctx, const float* x, int n, int T, int C, int depth, int flags,
+                        const double* channel_offset /* (C) or NULL */, const double* channel_scale /* (C) or NULL */,
+                        float* sig /* (n, D) or NULL */, double* sqnorm /* (n) or NULL */, double* mean /* (D) */, void* work,
+                        size_t work_bytes, void* stream);
+
 /* Post-hoc discriminative and predictive scores (NOT in the reference; TimeGAN, Yoon et al. 2019, and TSGBench; DESIGN.md 3.31,
  * utils/posthoc.py): what a small network trained AFTER the fact needs around the causal LSTM backbone (fd_score_create_ex with
  * FD_BACKBONE_LSTM), whose output at time t sees the inputs <= t only -- out[:, t] regressed on x[:, t + 1] is a next-step
