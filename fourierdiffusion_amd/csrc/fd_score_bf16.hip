@@ -1329,6 +1329,41 @@ int fd_score_forward_bf16(fd_score* m, const float* x, const float* t, float* ou
     return FD_OK;
 }
 
+// Attention of the unfused form, from the packed projections qkv (B*T, 3D) to att (B*T, D): the packed bf16 kernel (head_dim <= 7),
+// else the wide one (head_dim 8 .. 32), else -- head_dim > 32, K / V^T of a series beyond the LDS, FDIFF_ATTN_F32 -- the exact-f32
+// kernel.  One chain for the layer stack below and for fd_attention_forward's kind 0.
+static int attention_unfused(fd_ctx* ctx, const float* qkv, float* att, int B, int T, int H, int hd, hipStream_t s) {
+    int arc = getenv("FDIFF_ATTN_F32") ? FD_ERR_UNSUPPORTED : fd_attention_bf16(ctx, qkv, att, B, T, H, hd, s);
+    if (arc == FD_ERR_UNSUPPORTED && hd > 7 && !getenv("FDIFF_ATTN_F32"))       // head_dim 8 .. 32: one head per contraction
+        arc = fd_attention_bf16_wide(ctx, qkv, att, B, T, H, hd, s);
+    if (arc == FD_ERR_UNSUPPORTED) {
+        fd_attention_f32(qkv, att, nullptr, B, T, H, hd, 0.f, 0, 0, s);
+        arc = FD_OK;
+    }
+    return arc;
+}
+
+// The attention kernels on their own (include/fdiff_hip.h): kind 0 = the chain above, 1 = exact f32, 2 = bf16 packed, 3 = bf16 wide.
+extern "C" int fd_attention_forward(fd_ctx* ctx, const float* qkv, float* out, int B, int T, int H, int head_dim, int kind, void* stream) {
+    if (!ctx) return FD_ERR_ARG;
+    FD_REQUIRE(ctx, qkv && out && (const float*)out != qkv, "fd_attention_forward: null or aliased pointer");
+    FD_REQUIRE(ctx, B > 0 && T > 0 && H > 0 && head_dim > 0 && head_dim <= 64 && H <= 65535 && B <= 65535,
+               "fd_attention_forward: bad shape B=%d T=%d H=%d head_dim=%d (head_dim 1..64, B and H up to 65535)", B, T, H, head_dim);
+    FD_REQUIRE(ctx, (long long)B * T * 3 * H * head_dim < 2147483647LL, "fd_attention_forward: too large");
+    FD_REQUIRE(ctx, kind >= 0 && kind <= 3, "fd_attention_forward: unknown kind %d", kind);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = FD_OK;
+    if (kind == 0) rc = attention_unfused(ctx, qkv, out, B, T, H, head_dim, s);
+    else if (kind == 1) fd_attention_f32(qkv, out, nullptr, B, T, H, head_dim, 0.f, 0, 0, s);
+    else if (kind == 2) rc = fd_attention_bf16(ctx, qkv, out, B, T, H, head_dim, s);
+    else rc = fd_attention_bf16_wide(ctx, qkv, out, B, T, H, head_dim, s);
+    if (rc == FD_ERR_UNSUPPORTED)
+        return fd_fail(ctx, rc, "fd_attention_forward: kind %d has no kernel for T=%d head_dim=%d", kind, T, head_dim);
+    if (rc != FD_OK) return rc;
+    FD_LAUNCH_CHECK(ctx);
+    return FD_OK;
+}
+
 // the encoder layers of the step-by-step path: lb.h0 = layer input on entry, the last layer's output on return
 static int bf16_layer_stack(fd_score* m, int B, LayerBufs& lb, hipStream_t s) {
     fd_ctx* ctx = m->ctx;
@@ -1366,13 +1401,7 @@ static int bf16_layer_stack(fd_score* m, int B, LayerBufs& lb, hipStream_t s) {
             if (pbf) prc = fd_linear_bf16(ctx, h0, imq->pimg + (size_t)i * imq->p_layer_stride, qkv, M, 3 * D, D, imq->ks1, s);
             if (prc == FD_ERR_UNSUPPORTED) fdgemm::linear_fwd(h0, P + lo.in_w, P + lo.in_b, qkv, M, 3 * D, D, false, s);
             else if (prc != FD_OK) return prc;
-            arc = getenv("FDIFF_ATTN_F32") ? FD_ERR_UNSUPPORTED : fd_attention_bf16(ctx, qkv, att, B, T, H, hd, s);
-            if (arc == FD_ERR_UNSUPPORTED && hd > 7 && !getenv("FDIFF_ATTN_F32"))       // head_dim 8 .. 32: one head per contraction
-                arc = fd_attention_bf16_wide(ctx, qkv, att, B, T, H, hd, s);
-            if (arc == FD_ERR_UNSUPPORTED) {
-                fd_attention_f32(qkv, att, nullptr, B, T, H, hd, 0.f, 0, 0, s);
-                arc = FD_OK;
-            }
+            arc = attention_unfused(ctx, qkv, att, B, T, H, hd, s);
         }
         if (arc != FD_OK) return arc;
         const fd_bf16_images* im = m->bf16;

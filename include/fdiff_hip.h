@@ -193,6 +193,14 @@ int fd_positional_add(fd_ctx* ctx, const float* x, float* table, float* out, int
                       void* stream);
 int fd_time_embed_add(fd_ctx* ctx, const float* x, const float* t, const float* W, const float* Wd,
                       const float* bd, float* out, int B, int T, int D, void* stream);
+/* The self-attention kernels of the score network on their own (the network calls them through its layer stack; the tests pin each
+ * kernel class to float64 attention through this entry): out = softmax(q k^T / sqrt(head_dim)) v per head, eval mode (no dropout).
+ *   qkv (B*T, 3*H*head_dim) fp32 rows [q | k | v], out (B*T, H*head_dim) fp32, heads concatenated (torch MHA layout); head_dim 1..64.
+ *   kind 0: the dispatch of the bf16 mode's unfused layer form -- packed bf16 kernel (head_dim <= 7), wide bf16 kernel (8..32), and
+ *           the exact-f32 kernel for head_dim > 32 or when K / V^T of one head and series exceed the LDS
+ *        1: exact f32 (any head_dim);  2: bf16 packed, two heads per MFMA (head_dim <= 7);  3: bf16 wide, one head per MFMA (<= 32)
+ * Kinds 2 and 3 return FD_ERR_UNSUPPORTED where the kernel has no instantiation or its LDS image does not fit (no fallback). */
+int fd_attention_forward(fd_ctx* ctx, const float* qkv, float* out, int B, int T, int H, int head_dim, int kind, void* stream);
 
 int64_t fd_score_param_count(const fd_model_dims* dims);
 int fd_score_layout(const fd_model_dims* dims, fd_param_entry* entries, int* n_entries);

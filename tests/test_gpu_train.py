@@ -75,10 +75,89 @@ def test_gradient_accumulation_and_zero_grad():
     assert float(m.grads.abs().max()) == 0.0
 
 
+def _float64_loss_and_grads(sd, cfg, X, t, z):
+    """The DSM loss of O.dsm_loss (likelihood_weighting=False) restated in torch on tests/autograd_ref.net, float64, and its
+    gradient per state-dict key.  ``pos_encoder.embedding.weight`` is differentiated as the renormed rows the forward adds (the
+    reference renorms in place under no_grad, so its autograd sees exactly those rows)."""
+    from . import autograd_ref as AR
+    n = AR.net(sd, cfg["H"])
+    leaves = {"embedder.weight": n.We, "embedder.bias": n.be, "unembedder.weight": n.Wu, "unembedder.bias": n.bu,
+              "time_encoder.dense.weight": n.Wd, "time_encoder.dense.bias": n.bd, "pos_encoder.embedding.weight": n.pe}
+    leaves.update({"backbone." + k: p for k, p in n.enc.named_parameters()})
+    for p in leaves.values():
+        p.requires_grad_(True)
+    sde = O.SDEParams("vp", 0.1, 20.0, O.noise_scaling(cfg["T"], True))
+    Xn, target, std = O.perturb(sde, X, t, z)
+    score = n.forward(torch.tensor(Xn), t)
+    w = torch.tensor(1.0 / np.sum(1.0 / std ** 2, axis=1))
+    loss = (w[:, None, None] * (score + torch.tensor(target)) ** 2).reshape(len(t), -1).mean(dim=-1).mean()
+    grads = torch.autograd.grad(loss, list(leaves.values()))
+    assert abs(loss.item() - O.loss_fn(sd, sde, X, t, z, cfg["H"], False)) <= 1e-12 * abs(loss.item())      # the restated loss IS the oracle's
+    return loss.item(), {k: g.numpy() for k, g in zip(leaves, grads)}, Xn
+
+
+def _kink_free_seed(sd, cfg, B, tag):
+    """The first input seed at which no FFN pre-activation of the float64 restatement lies within tau_of (4 x the largest float32-
+    minus-float64 pre-activation difference of the restatement) of its relu kink -- so the float32 and float64 restatements agree on
+    the sign of every pre-activation.  A condition on the inputs, evaluated on the CPU; the engine is not consulted."""
+    from . import autograd_ref as AR
+    sde = O.SDEParams("vp", 0.1, 20.0, O.noise_scaling(cfg["T"], True))
+    for seed in range(64):
+        X = W.randn(f"wh_x_{tag}", (B, cfg["T"], cfg["C"]), seed)
+        z = W.randn(f"wh_z_{tag}", (B, cfg["T"], cfg["C"]), seed)
+        t = W.uniform(f"wh_t_{tag}", (B,), seed, 0.05, 1.0)
+        Xn = O.perturb(sde, X, t, z)[0]
+        a64 = AR.preacts(sd, Xn, t, cfg["H"])
+        a32 = AR.preacts(sd, Xn, t, cfg["H"], dtype=torch.float32)
+        tau = 4.0 * max(float(np.abs(p - q).max()) for p, q in zip(a32, a64))      # (= autograd_ref.tau_of)
+        if all(np.abs(a).min() > tau for a in a64):
+            assert all(np.array_equal(p > 0, q > 0) for p, q in zip(a32, a64))
+            return seed, X, t, z
+    raise AssertionError("no kink-free input seed among 64")
+
+
+@pytest.mark.parametrize("D,H", [(48, 4), (96, 4), (80, 2)], ids=["head_dim_12", "head_dim_24", "head_dim_40"])
+def test_loss_and_gradients_vs_float64_at_wider_heads(D, H):
+    """The exact-f32 training path at head_dim 12, 24 and 40 -- attn_bwd_t<16>, <32>, <64>, which every bf16-mode model of these
+    widths trains on and no other gradient test reaches (theirs stop at head_dim 8).  fp32 mode, dropout 0, injected t and z; loss
+    and every parameter gradient against float64 torch autograd through tests/autograd_ref.net (equal to the oracle's forward,
+    tests/test_autograd_ref_cpu.py), at this file's bounds: loss rtol 2e-5, each tensor within 2e-4 of its max |grad|.
+    The inputs are chosen kink-free (``_kink_free_seed``): the gradient jumps where an FFN pre-activation changes sign, and an
+    fp32 engine and a float64 reference on different sides of a kink would disagree by far more than rounding, neither being wrong."""
+    from fourierdiffusion_amd.utils.losses import get_sde_loss_fn
+    cfg = dict(T=37, C=3, D=D, L=2, H=H)
+    B = 3
+    m, sch, sd = make_model(cfg, precision="fp32")
+    m.dropout = 0.0
+    seed, X, t, z = _kink_free_seed(sd, cfg, B, f"{D}_{H}")
+    lref, gref, _ = _float64_loss_and_grads(sd, cfg, X, t, z)
+    m.zero_grad()
+    loss = get_sde_loss_fn(sch, train=True, likelihood_weighting=False)(m, batch_of(X, t), noise=dev(z))
+    assert m.train_mode_effective == "fp32"
+    np.testing.assert_allclose(loss.item(), lref, rtol=2e-5)
+    worst = ("", 0.0)
+    for k, gt in m.grad_views().items():
+        if k == "time_encoder.W":                               # requires_grad=False in the reference
+            assert float(gt.abs().max()) == 0.0
+            continue
+        ref = gref.pop(k)
+        assert ref.shape == tuple(gt.shape), k
+        scale = max(np.abs(ref).max(), 1e-12)
+        err = np.abs(host(gt) - ref).max() / scale
+        print(f"[wider heads] d_model {D} / {H} heads, seed {seed}: {k}: max err / max |grad| = {err:.3e}")
+        assert err < 2e-4, (k, err)
+        worst = max(worst, (k, err), key=lambda e: e[1])
+    assert not gref, sorted(gref)                               # every reference gradient was compared
+    from .gpu_util import log_line
+    log_line(f"[wider heads] d_model {D} / {H} heads (head_dim {D // H}), input seed {seed}: loss rel err "
+             f"{abs(loss.item() - lref) / abs(lref):.2e}; worst gradient {worst[0]} {worst[1]:.3e} of max |grad| (bound 2e-4)")
+
+
 CFG_D10 = dict(T=12, C=2, D=10, L=1, H=2)      # d_model % 4 != 0: the dropout sites cannot ride in the GEMM epilogues
+CFG_HD24 = dict(T=12, C=2, D=48, L=1, H=2)     # head_dim 24: the attention-probability dropout is regenerated in attn_bwd_t<32>
 
 
-@pytest.mark.parametrize("cfg", [CFG_TINY, CFG_D10], ids=["tiny", "d_model_10"])
+@pytest.mark.parametrize("cfg", [CFG_TINY, CFG_D10, CFG_HD24], ids=["tiny", "d_model_10", "head_dim_24"])
 def test_dropout_forward_backward_consistency(cfg):
     """dropout p=0.1: masks are regenerated in backward from the same Philox key.  With the key pinned through
     torch.manual_seed the loss is a deterministic function of the parameters; check grad . v against a central

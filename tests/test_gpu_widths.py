@@ -33,6 +33,12 @@ WIDTHS = {
     "d64_h16": (dict(T=100, C=12, D=64, L=2, H=16), "bf16", "per-layer"),        # head_dim 4, four k-steps of head slots
     "d160_h8": (dict(T=32, C=3, D=160, L=2, H=8), "fp32", "fp32"),               # beyond every bf16 instantiation
     "d42_h6": (dict(T=32, C=3, D=42, L=2, H=6), "fp32", "fp32"),                 # d_model % 4 != 0
+    # head_dim classes beyond 16 and the scalar staging of the wide kernel (kernel by kernel: test_gpu_attention_kernels.py)
+    "d128_h4": (dict(T=50, C=3, D=128, L=2, H=4), "bf16", "k_attention_wide"),   # head_dim 32: k_attention_wide<32>, 16-byte staging
+    "d72_h4": (dict(T=33, C=3, D=72, L=2, H=4), "bf16", "k_attention_wide"),     # head_dim 18: wide<32>, scalar staging, odd key-tile count
+    "d40_h4": (dict(T=40, C=3, D=40, L=2, H=4), "bf16", "k_attention_wide"),     # head_dim 10: wide<16>, scalar staging
+    "d128_h2": (dict(T=40, C=3, D=128, L=2, H=2), "bf16", "exact-f32 kernel (head_dim > 32)"),   # head_dim 64: bf16 FFN + k_attention_f32<64>
+    "d96_h2": (dict(T=40, C=3, D=96, L=2, H=2), "bf16", "exact-f32 kernel (head_dim > 32)"),     # head_dim 48: the same; fp32 mode runs f32<64> too
 }
 
 
@@ -65,7 +71,7 @@ def test_forward_both_modes_vs_oracle(name):
         np.testing.assert_allclose(out, ref, atol=2e-5, rtol=0)
 
 
-@pytest.mark.parametrize("name", ["d64_h8", "d64_h8_long", "d128_h8", "d160_h8"])
+@pytest.mark.parametrize("name", ["d64_h8", "d64_h8_long", "d128_h8", "d160_h8", "d128_h4"])
 def test_sampler_default_precision_at_other_widths(name):
     """DiffusionSampler.sample with ``precision`` left at its default ("bf16"), as test_sampler.py of the reference drives it
     (tests/test_sampler.py: any model the config builds must sample): 10 reverse-diffusion steps with injected normals
@@ -141,6 +147,25 @@ def test_training_falls_back_and_says_so_at_other_widths():
     X = dev(W.randn("wd_train_x", (4, cfg["T"], cfg["C"]), 5))
     torch.manual_seed(3)
     m.zero_grad()
+    before = m.flat_parameters.clone()
     loss = m.training_step(DiffusableBatch(X=X), 0)
     opt.step()
     assert m.train_mode_effective == "fp32" and torch.isfinite(loss) and torch.isfinite(m.flat_parameters).all()
+    # the step moved every trainable tensor (head_dim 16: the exact-f32 attention backward attn_bwd_t<16> feeds in_proj and all below)
+    for pname, off, numel, _, trainable in m._layout:
+        moved = float((m.flat_parameters[off:off + numel] - before[off:off + numel]).abs().max())
+        assert (moved > 0) == bool(trainable), (pname, moved)
+    # and the fallback computes the reference's loss: dropout off, injected t and z, against the float64 oracle at the fp32 bound
+    from fourierdiffusion_amd.utils.losses import get_sde_loss_fn
+    m2, sch, sd = make_model(cfg, precision="bf16")
+    m2.train_precision = "bf16"
+    m2.dropout = 0.0
+    Xn = W.randn("wd_train_x", (4, cfg["T"], cfg["C"]), 5)
+    z = W.randn("wd_train_z", (4, cfg["T"], cfg["C"]), 5)
+    t = W.uniform("wd_train_t", (4,), 5, 0.05, 1.0)
+    m2.zero_grad()
+    got = get_sde_loss_fn(sch, train=True)(m2, DiffusableBatch(X=dev(Xn), y=None, timesteps=dev(t)), noise=dev(z)).item()
+    ref = O.loss_fn(sd, oracle_sde("vp", (0.1, 20.0), True, cfg["T"]), Xn, t, z, cfg["H"], False)
+    assert m2.train_mode_effective == "fp32"
+    np.testing.assert_allclose(got, ref, rtol=2e-5)
+    assert torch.isfinite(m2.grads).all() and float(m2.grads.abs().max()) > 0
